@@ -2,21 +2,25 @@
 """bench.py — images/sec of the PGGAN train step on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--depth D] [--alpha A] [--fmap-base F] [--config {2,3,4,5}]
-                    [--no-cpu] [--no-per-depth] [--no-configs]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-per-depth] [--no-configs] [--no-kernel-timing] [--no-d-step]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is one Trainer.train() iteration (reference trainer.py:85-115): wgan_gp_D_loss + backward
 (3 D passes batched, G forward, gradient-penalty double backward) + Adam(D), then wgan_gp_G_loss +
-backward + Adam(G), on one synthetic minibatch already resident in HBM.  Headline workload (BASELINE.json config 5):
+backward + Adam(G), on one synthetic minibatch already resident in HBM; Adam at learning rate BENCH_LR = 0, so that every step
+runs on the seeded weights and computes the same on every run.  Headline workload (BASELINE.json config 5):
 the 1024x1024 growth stage (depth 8) of the default-width (fmap_base 4096) CelebA-HQ-shape network with
 the reference's per-depth minibatch (3 per GPU, plugins.py:20), fp32.  Data-parallel: one process
 per GPU, minibatch per rank fixed (weak scaling), RCCL sum-all-reduce of each network's flat gradient buffer
 (bucketed, overlapped with the backward sweeps) through the library's C-ABI.  ``--gpus N`` with N > 1 and no
 WORLD_SIZE in the environment launches the N ranks itself (torch.distributed.run) and fails loudly when fewer than N
-devices are visible.  Rank 0 prints ONE JSON line (the last line of stdout), at most 6 KB: the contract keys, ``roofline``,
-``cpu_baseline``, the D+GP window and one row per growth stage.  Every table behind it (per-kernel timings, secondary workloads, CPU
-per-depth numbers, timing windows) is written to ``bench_detail.json`` next to this file (a short digest goes to stderr).
+devices are visible.  Rank 0 prints ONE JSON line (the last line of stdout), at most 6 KB.  A plain run does only what the headline
+needs: set up, prime, warm up, time the K steps, write the last timed step's outputs (``--dump-outputs DIR``: losses, parameters and
+gradients of G and D as DIR/<name>.npy, fixed samples of the large tensors) and print the contract keys (``cpu_baseline`` null).
+``--full`` adds everything else: ``roofline``, ``cpu_baseline``, the D+GP window and one row per growth stage on the line, and every
+table behind it (per-kernel timings, secondary workloads, CPU per-depth numbers, timing windows) in ``bench_detail.json`` next to this
+file (a short digest goes to stderr).
 
 Fractions (all <= 1 by construction; Winograd F(2x2,3x3) launches are credited 16/36 of the 2*MAC count, peak = the nominal 157.3 TF of
 fp32 MFMA): ``roofline.frac`` = MFMA FLOP the launches of the dominant conv symbol EXECUTE / their HIP-event time (per-launch event
@@ -263,6 +267,14 @@ class KernelTimer(object):
 
 
 
+# Learning rate of the benchmark's Adam steps.  The weight gradients are committed with fp32 atomics, so their last bits depend on the
+# order the workgroups arrive in; training from step to step amplifies that (Adam normalises near-zero gradients, the GAN does the rest):
+# two runs at the reference's 1e-3 share their losses after one step and nothing after 25.  At 0 every step runs the same kernels on the
+# same shapes -- Adam's full update arithmetic included, ``p -= 0 * m / (sqrt(v) + eps)`` -- but on the seeded weights, so each step is
+# a function of the seeded inputs and what it computes is the same on every run up to the rounding of those atomics (--dump-outputs).
+BENCH_LR = 0.0
+
+
 def make_trainer(pg, res, depth, alpha, mb, seed, dp, fmap_base=4096, channels=3, ring=8, host_data=False, lookahead=False):
     torch.manual_seed(1337)                       # same weights on every rank (train.py:21)
     shape = (1, channels, res, res)
@@ -270,8 +282,8 @@ def make_trainer(pg, res, depth, alpha, mb, seed, dp, fmap_base=4096, channels=3
     D = pg.Discriminator(shape, fmap_base=fmap_base).cuda()
     G.depth = D.depth = depth
     G.alpha = D.alpha = alpha
-    opt_g = pg.FusedAdam(G.parameters(), 0.001, betas=(0.0, 0.99))     # 1/world gradient pre-scale: set by Trainer(parallel=...)
-    opt_d = pg.FusedAdam(D.parameters(), 0.001, betas=(0.0, 0.99))
+    opt_g = pg.FusedAdam(G.parameters(), BENCH_LR, betas=(0.0, 0.99))     # 1/world gradient pre-scale: set by Trainer(parallel=...)
+    opt_d = pg.FusedAdam(D.parameters(), BENCH_LR, betas=(0.0, 0.99))
     ds = pg.utils.SyntheticDataset(res, channels, seed=seed, ring=ring, host=host_data)   # pre-generated ring: no RNG kernels in the timed steps
     ds.model_depth = depth
     pg.wgan_gp_loss.manual_seed(seed)
@@ -358,11 +370,84 @@ def d_step_fn(tr):
     z = tr.random_latents_generator()
 
     def one():
-        c = tr.D_loss(tr.D, tr.G, real, z)[0]
-        c.backward()
+        losses = tr.D_loss(tr.D, tr.G, real, z)
+        losses[0].backward()
         tr._exchange(tr.D)
         tr.optimizer_d.step()
+        LAST_LOSSES['values'] = dict(zip(('d_cost', 'd_real_loss', 'd_fake_loss'), losses))
     return one
+
+
+LAST_LOSSES = {'values': None}      # the losses of the latest timed step (--dump-outputs): device tensors, read after the timed loop
+
+
+class _KeepLosses(object):
+    """Trainer plugin (``iteration`` queue, every step): keeps references to the step's losses -- what ``Trainer.call_plugins`` hands
+    its plugins, (G cost, D cost, D real loss, D fake loss) -- without a copy or a synchronisation."""
+    trigger_interval = [(1, 'iteration')]
+
+    def register(self, trainer):
+        pass
+
+    def iteration(self, it, *losses):
+        LAST_LOSSES['values'] = dict(zip(('g_cost', 'd_cost', 'd_real_loss', 'd_fake_loss'), losses))
+
+
+DUMP_SAMPLE = 1 << 16          # elements kept per parameter (and per gradient) tensor: ~14 MB in all at the 1024x1024 stage
+
+
+def _reference_grads(pg, net):
+    """{reference parameter name: gradient in the reference layout (as ``reference_state_dict`` lays out the weights)}."""
+    out = {}
+    for name, m in net.named_modules():
+        if isinstance(m, pg.PGConv2d):
+            gw, gb = m.conv.weight.grad, m.conv.bias.grad
+            if gw is not None:
+                out[name + '.conv.weight'] = (gw.reshape(m.ch_out, m.ch_in, 1, 1) if m.kind in ('fromrgb', 'torgb')
+                                              else gw[..., :m.ch_in].permute(2, 3, 0, 1))
+            if gb is not None:
+                out[name + '.conv.bias'] = gb
+    if hasattr(net, 'linear'):
+        for k in ('weight', 'bias'):
+            g = getattr(net.linear, k).grad
+            if g is not None:
+                out['linear.' + k] = g
+    return out
+
+
+def dump_outputs(pg, tr, path):
+    """What the timed path left its caller after the LAST timed step, as ``path/<name>.npy``: the step's losses (float64, flat: one
+    element per cost, one per image for the D real / fake losses) and the parameters of G and D after the update together with their
+    gradients, in the reference's names and layout (float32).  A tensor of more than DUMP_SAMPLE elements is represented by a fixed
+    sample: the flat indices drawn without replacement by a generator seeded with the tensor's name, ascending, the same on every run.
+    Every step runs on the seeded weights (BENCH_LR), so with the same arguments the inputs and these outputs are the same on every
+    run, up to the rounding of the fp32 atomics that commit the weight gradients."""
+    import zlib
+    import numpy as np
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for key, v in (LAST_LOSSES['values'] or {}).items():
+        arrays[key] = torch.as_tensor(v).detach().reshape(-1).double().cpu().numpy()
+    for tag, net in (('G', tr.G), ('D', tr.D)):
+        params = {k: v for k, v in net.reference_state_dict().items() if torch.is_tensor(v)}
+        grads = _reference_grads(pg, net)
+        for k, v in params.items():
+            idx = None
+            if v.numel() > DUMP_SAMPLE:
+                rng = np.random.default_rng(zlib.crc32(('%s.%s' % (tag, k)).encode()))
+                idx = torch.from_numpy(np.sort(rng.choice(v.numel(), DUMP_SAMPLE, replace=False)))
+            for name, t in (('%s.%s' % (tag, k), v), ('%s.%s.grad' % (tag, k), grads.get(k))):
+                if t is None:
+                    continue
+                flat = t.detach().reshape(-1).float().cpu()
+                arrays[name] = (flat if idx is None else flat[idx]).numpy()
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+        total += a.nbytes
+    return {'dir': path, 'arrays': len(arrays), 'bytes': total}
 
 
 CPU_SAMPLE_MAX_MB = 4
@@ -649,6 +734,12 @@ def main():
                     'trainer.py:92: the Trainer uploads batch k + 1 on a copy stream under iteration k); the device-resident number stays "value"')
     ap.add_argument('--d-step-only', action='store_true', help='the timed loop runs the D step + gradient penalty + Adam(D) only (profiling aid: '
                     'tools/profile_round.sh collects the MFMA-busy counters of that window; the JSON line says so in "metric")')
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline figure (off by default): the D + GP timing, the '
+                    'host-resident input run, the exchange timing of a data-parallel run, per-kernel timing and the roofline, the per-depth '
+                    'table, the secondary workloads, the CPU baseline and bench_detail.json; the --no-* options above trim it')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last of them left its caller (losses, '
+                    'parameters and gradients of G and D; fixed samples of the large tensors) as DIR/<name>.npy (the same on every run up to '
+                    'rounding: see BENCH_LR)')
     args = ap.parse_args()
 
     env_world = os.environ.get('WORLD_SIZE')
@@ -694,6 +785,8 @@ def main():
     seed = pg.parallel.shard_seed(1337, rank)
 
     tr = make_trainer(pg, net_res, depth, args.alpha, mb, seed, dp, fmap_base=args.fmap_base, channels=c['ch'])
+    if args.dump_outputs:
+        tr.register_plugin(_KeepLosses())
     for _ in range(args.prime):           # setup, untimed and reported: code-object loading, allocator growth, clock ramp
         tr.train()
     if dp is not None:
@@ -701,8 +794,11 @@ def main():
     dt = timed_steps(tr, args.steps, args.warmup, dp, fn=d_step_fn(tr) if args.d_step_only else None, markers=args.d_step_only)
     ms_per_step = 1e3 * dt / args.steps
     host_ms, host_free_ms = HOST_ENQUEUE['ms'], HOST_ENQUEUE['free_ms']
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(pg, tr, args.dump_outputs)
+        sys.stderr.write('[bench] outputs of the last timed step: %d arrays, %.1f MB in %s\n' % (dumped['arrays'], dumped['bytes'] / 1e6, dumped['dir']))
     # D step + gradient penalty + Adam(D) of the headline stage (its own timed loop, after the contract's)
-    d_gp_ms = None if (args.no_d_step or args.d_step_only) else robust_ms(tr, dp, fn=d_step_fn(tr), prime=3, window_s=0.25)[0]
+    d_gp_ms = None if (args.no_d_step or args.d_step_only or not args.full) else robust_ms(tr, dp, fn=d_step_fn(tr), prime=3, window_s=0.25)[0]
     if args.d_step_only:
         d_gp_ms = ms_per_step
     value = n_gpus * mb * args.steps / dt
@@ -716,9 +812,9 @@ def main():
         'dtype': 'f32', 'data': 'synthetic (seeded uniform images / normal latents, ring of 8 device-resident batches)' + (
             ' -- PGGAN_DP_SHARE_GPU=1: ALL RANKS ON ONE DEVICE, a collective-matching smoke test, NOT a measurement' if os.environ.get('PGGAN_DP_SHARE_GPU', '') == '1' else ''),
         'config': {'workload': 'BASELINE config %d: PGGAN %dx%d net (fmap_base %d, C=%d, latent %d), stage depth %d = %dx%d, '
-                               'alpha %.2f, minibatch %d/GPU%s, Trainer.train(): WGAN-GP + Adam(0,0.99), fp32'
+                               'alpha %.2f, minibatch %d/GPU%s, Trainer.train(): WGAN-GP + Adam(0,0.99) at lr %g, fp32'
                                % (args.config, net_res, net_res, args.fmap_base, c['ch'], tr.G.latent_size, depth, res, res, args.alpha, mb,
-                                  ' (reference schedule)' if args.config == 5 and not args.minibatch else ''),
+                                  ' (reference schedule)' if args.config == 5 and not args.minibatch else '', BENCH_LR),
                    'resolution': res, 'depth': depth, 'minibatch_per_gpu': mb, 'global_batch': mb * n_gpus,
                    'parallelism': 'dp%d' % n_gpus, 'fmap_base': args.fmap_base},
         'step_algorithmic_gflop_per_image': w / 1e9,
@@ -729,7 +825,7 @@ def main():
         'd_step_gp_ms': d_gp_ms,
     }
     out['config']['hip_graphs'] = bool(pg.wgan_gp_loss._replay_mode(tr.G) == 'graph' and args.alpha >= 1.0)
-    if args.host_data or (args.config == 5 and not args.no_configs):
+    if args.host_data or (args.full and args.config == 5 and not args.no_configs):
         # the same step fed from pinned host memory (37.7 MB per step at 1024x1024): never "value" (inputs resident in HBM is the
         # contract), reported next to it
         th = make_trainer(pg, net_res, depth, args.alpha, mb, seed, dp, fmap_base=args.fmap_base, channels=c['ch'], host_data=True)
@@ -748,6 +844,7 @@ def main():
         steps_counted = args.steps + args.warmup
         out['allreduce_bytes_per_step'] = dp.stats['bytes'] / steps_counted
         out['allreduce_collectives_per_step'] = dp.stats['collectives'] / steps_counted
+    if rccl is not None and args.full:
         # busy time of the exchange per step (HIP events around every collective on the stream it runs on) and the step
         # time with the collectives left out: their difference to ms_per_step is the EXPOSED exchange
         dp.record_events, dp.events = True, []
@@ -764,7 +861,8 @@ def main():
         out['ms_per_step_without_exchange'] = 1e3 * dt0 / args.steps
         out['exposed_exchange_ms'] = ms_per_step - out['ms_per_step_without_exchange']
 
-    if rank == 0 and not args.no_kernel_timing:
+    kernel_timing = args.full and not args.no_kernel_timing
+    if rank == 0 and kernel_timing:
         psteps = 3
         graph_mode = pg.wgan_gp_loss._replay_mode(tr.G) == 'graph'
         if graph_mode or args.serial_kernel_timing:
@@ -862,7 +960,7 @@ def main():
         out['kernels'] = {k: {'tflops': v['tflops'], 'executed_tflops': v['exec_tflops'], 'ms_per_step': v['ms_per_step'],
                               'launches_per_step': v['launches_per_step'], 'avg_launch_us': v['avg_launch_us']}
                           for k, v in fam.items()}
-    elif dp is not None and not args.no_kernel_timing:
+    elif dp is not None and kernel_timing:
         pg.wgan_gp_loss.enable_graphs(False)
         for _ in range(3):                                  # keep collectives matched with rank 0: its instrumented train steps ...
             tr.train()
@@ -874,7 +972,7 @@ def main():
     pg.plans.clear()
     torch.cuda.empty_cache()
 
-    if not args.no_per_depth:
+    if args.full and not args.no_per_depth:
         per = []
         for d in range(0, 9):
             m = REF_MINIBATCH.get(d, 16)
@@ -886,7 +984,7 @@ def main():
             torch.cuda.empty_cache()
         out['per_depth'] = per
 
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         sec = {}
         t = make_trainer(pg, 1024, 8, 0.5, 3, seed, dp)
         sec['depth8_alpha0.5'] = stage_entry(pg, t, dp, n_gpus, 3, 8, 0.5, {'workload': 'config 5 network, 1024x1024 stage in the middle of its fade-in (alpha 0.5)'})
@@ -924,7 +1022,7 @@ def main():
                 h.update(f.read())
         # (keyed by host and by the code that produced it: a stale file of another build or box is never reported as this box's)
         cache = os.path.join(tempfile.gettempdir(), 'pggan_cpu_baseline_%s_%s_d%d_mb%d.json' % (socket.gethostname(), h.hexdigest()[:12], depth, mb))
-        if args.no_cpu or args.config != 5:
+        if args.no_cpu or args.config != 5 or not args.full:
             out['cpu_baseline'] = None
         elif n_gpus == 1:
             out['cpu_baseline'] = cpu_baseline(depth, mb)
@@ -947,7 +1045,7 @@ def main():
     if rank == 0:
         # the JSON line is the LAST thing on stdout: RCCL prints its banner through C stdio, which is still buffered here
         import ctypes
-        detail_path = write_detail(out)
+        detail_path = write_detail(out) if args.full else None
         sys.stdout.flush()
         ctypes.CDLL(None).fflush(None)
         print(compact_line(out, detail_path), flush=True)

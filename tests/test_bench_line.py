@@ -67,3 +67,50 @@ def test_null_traffic_is_kept():
     out = _canned()
     out['roofline']['traffic'] = None
     assert json.loads(bench.compact_line(out))['roofline']['traffic'] is None
+
+
+def test_dump_outputs_is_fixed_and_in_reference_layout(tmp_path, monkeypatch):
+    """``--dump-outputs``: losses as float64, parameters and gradients of G and D in the reference's names and layout as float32; a
+    tensor above DUMP_SAMPLE elements is a sample at the same indices on every run."""
+    import numpy as np
+    import torch
+    import pggan_amd as pg
+    from helpers import reference_grads
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 500)
+    torch.manual_seed(3)
+    shape = (1, 3, 16, 16)
+    G, D = pg.Generator(shape, latent_size=32, fmap_base=128, fmap_max=32), pg.Discriminator(shape, fmap_base=128, fmap_max=32)
+    G.depth = D.depth = 2
+    for p in list(G.parameters()) + list(D.parameters()):
+        p.grad = torch.randn_like(p)
+    monkeypatch.setitem(bench.LAST_LOSSES, 'values', {'g_cost': torch.tensor(0.25), 'd_cost': torch.tensor(-1.5),
+                                                      'd_real_loss': torch.tensor([[0.5], [-0.5], [2.0]])})
+
+    class Tr(object):
+        pass
+    tr = Tr()
+    tr.G, tr.D = G, D
+    a, b = tmp_path / 'a', tmp_path / 'b'
+    info = bench.dump_outputs(pg, tr, str(a))
+    bench.dump_outputs(pg, tr, str(b))
+    names = sorted(os.listdir(str(a)))
+    assert names == sorted(os.listdir(str(b))) and len(names) == info['arrays']
+    assert info['bytes'] <= 64 << 20
+    for n in names:
+        x, y = np.load(str(a / n)), np.load(str(b / n))
+        assert np.array_equal(x, y), n
+        assert x.dtype == (np.float64 if n in ('g_cost.npy', 'd_cost.npy', 'd_real_loss.npy') else np.float32), n
+    assert np.load(str(a / 'd_cost.npy')).tolist() == [-1.5]
+    assert np.load(str(a / 'd_real_loss.npy')).tolist() == [0.5, -0.5, 2.0]
+    sampled = 0
+    for tag, net in (('G', G), ('D', D)):
+        params, grads = net.reference_state_dict(), reference_grads(net)
+        for k, g in grads.items():
+            p, gp = np.load(str(a / ('%s.%s.npy' % (tag, k)))), np.load(str(a / ('%s.%s.grad.npy' % (tag, k))))
+            if g.numel() <= 500:
+                assert np.array_equal(p, params[k].numpy().reshape(-1)) and np.array_equal(gp, g.numpy().reshape(-1)), k
+            else:
+                sampled += 1
+                assert p.shape == gp.shape == (500,), k
+                assert set(gp.tolist()) <= set(g.numpy().reshape(-1).tolist()), k
+    assert sampled > 0

@@ -1,6 +1,6 @@
 """Timeline of ONE train step from a rocprofv3 kernel trace of bench.py (run on the GPU box):
 
-    cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace -d $OUT -o kt --output-format csv -- python bench.py --no-cpu --no-per-depth --no-configs --no-kernel-timing --prime 10 --steps 10 --warmup 3
+    cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace -d $OUT -o kt --output-format csv -- python bench.py --full --no-cpu --no-per-depth --no-configs --no-kernel-timing --prime 10 --steps 10 --warmup 3
     python tools/step_timeline.py "$OUT/**/kt_kernel_trace.csv" [step index from the end, default 3] > timeline.txt
 
 Every kernel of the step in start order: start (us from the step's first kernel), duration, queue (M = the queue with the most kernels,

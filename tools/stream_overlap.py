@@ -1,6 +1,6 @@
 """Occupancy of the two HIP streams from a rocprofv3 kernel trace of bench.py (run on the GPU box):
 
-    cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace -d $OUT -o kt --output-format csv -- python bench.py --no-cpu --no-per-depth --no-kernel-timing --prime 10 --steps 10 --warmup 3
+    cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace -d $OUT -o kt --output-format csv -- python bench.py --full --no-cpu --no-per-depth --no-kernel-timing --prime 10 --steps 10 --warmup 3
     python tools/stream_overlap.py $OUT/**/kt_kernel_trace.csv
 
 Takes the last 10 train steps (delimited by the Adam launches of the generator), and reports per queue: busy time,
