@@ -18,6 +18,7 @@ which is evaluated as (i) a tangent pass pushing u through the same masked linea
 minibatch-stddev Hessian-vector term injected into the ordinary batched backward of the mixed
 samples (SURVEY.md §7 "hard parts"; formulas verified against autograd in tests/).
 """
+import collections as _collections
 import os
 import weakref as _weakref
 
@@ -42,24 +43,20 @@ def _check_dev(t, what):
 # 3x3 layers with a full 16-cout MFMA tile and enough 64-tile workgroups to fill the chip.  With the second-generation kernel
 # (8-channel chunks) that includes the 16-channel layers of the 512^2 stage (1.3-1.55x the direct kernel) and 8->16 at 1024^2
 # (1.16x); 16->8 and 8->8 (half of the cout tile empty) stay on the block-MFMA kernels (0.7-1.0x).
-import os as _os
-USE_WINOGRAD = _os.environ.get('PGGAN_WINOGRAD', '1') != '0'
-WINO_MIN_WORKGROUPS = int(_os.environ.get('PGGAN_WINO_MIN_WG', '32'))     # (K is sliced across workgroups below ~432: ops._stream_with_workspace)
-WINO_MIN_CHANNELS = int(_os.environ.get('PGGAN_WINO_MIN_C', '8'))
-WINO_MIN_COUT = int(_os.environ.get('PGGAN_WINO_MIN_COUT', '16'))
-USE_WINOGRAD_WGRAD = USE_WINOGRAD and _os.environ.get('PGGAN_WINOGRAD_WGRAD', '1') != '0'
-WINO_WGRAD_MIN_CHANNELS = int(_os.environ.get('PGGAN_WINO_WGRAD_MIN_C', '16'))
+USE_WINOGRAD = True            # False in tests/test_winograd.py::test_engine_with_sign_bytes_gpu: every 3x3 layer on the direct kernels
+WINO_MIN_WORKGROUPS = 32       # (K is sliced across workgroups below ~432: ops._stream_with_workspace); 0 in tests/test_winograd.py::_engine_vs_oracle
+_WINO_MIN_CHANNELS = 8         # input channels of the conv
+_WINO_MIN_COUT = 16            # a full 16-cout MFMA tile
+_WINO_WGRAD_MIN_CHANNELS = 16  # channels (either side) of a Winograd weight gradient
 # The c2 output of a DBlock is pooled at once (network.py:229,238); at full resolution only its SIGN is ever used again
 # (LeakyReLU' in the backward / tangent sweeps), so from 64x64 up it is kept as sign bytes (1 byte per 4 channels)
 # instead of fp32: the fp32 write and its re-reads are the largest avoidable HBM traffic of the high-resolution stages.
-import collections as _collections
 FALLBACKS = _collections.Counter()       # launches that answered PG_E_UNSUP to a sign-byte request and were redone in fp32
-USE_SIGN_BYTES = _os.environ.get('PGGAN_SIGN_BYTES', '1') != '0'
-SIGN_BYTES_MIN_H = int(_os.environ.get('PGGAN_SIGN_BYTES_MIN_H', '64'))
+USE_SIGN_BYTES = True          # tests/test_winograd.py::test_engine_with_sign_bytes_host / _gpu set both (sign bytes from 8x8 up)
+SIGN_BYTES_MIN_H = 64
 # With the mask as sign bytes the pool adjoint between two DBlocks can be evaluated in the input gathers of its consumers
 # (backward-data conv and weight gradient of the finer block's c2) instead of being written out at the fine resolution.
-USE_LAZY_UNPOOL = _os.environ.get('PGGAN_LAZY_UNPOOL', '1') != '0'
-USE_LAZY_UNPOOL_FADE = _os.environ.get('PGGAN_LAZY_UNPOOL_FADE', '1') != '0'    # ... also across the fade-in boundary (alpha < 1)
+USE_LAZY_UNPOOL = True         # tests/test_winograd.py::test_engine_with_lazy_pool_adjoint_gpu checks that the path is taken
 
 
 def _live_conv_layers(net):
@@ -86,7 +83,7 @@ def _derived(net):
     live = set(id(m) for m in _live_conv_layers(net))
     # flipped / transposed copies: only for the layers whose backward-data conv has asked for one (_wt marks them) -- the layers that
     # always run Winograd there get their backward-data form straight from the parameter (transposed=True below)
-    todo = [m for m in net._layers() if m.kind == 'conv' and m._wt is not None and id(m) in live and (getattr(m, '_wt_wanted', False) or not WTU_FROM_PARAM)]
+    todo = [m for m in net._layers() if m.kind == 'conv' and m._wt is not None and id(m) in live and getattr(m, '_wt_wanted', False)]
     packs = [((m.conv.weight.data_ptr() - base) // 4, m.ksize, m.conv.weight.shape[2], m.conv.weight.shape[3]) for m in todo]
     # ... and of those only the layers the Winograd path has actually asked for (_wino marks them): the 512-channel layers of the
     # 4x4 stage never reach it, yet are a large part of all Winograd-domain bytes
@@ -97,9 +94,9 @@ def _derived(net):
         if packs:
             ops.pack_dgrad_weights_batched(net._flat_param, net._flat_wt, packs)
         if wl:
-            ops.wino_transform_weights_batched(net._flat_param if WTU_FROM_PARAM else net._flat_wt, net._flat_wtu,
+            ops.wino_transform_weights_batched(net._flat_param, net._flat_wtu,
                                                [(woff, uoff, m.conv.weight.shape[3], m.conv.weight.shape[2]) for m, woff, uoff in wl],
-                                               transposed=WTU_FROM_PARAM)
+                                               transposed=True)
     dev = torch.cuda.current_device() if net._flat_param.is_cuda else None
     cur = torch.cuda.current_stream(torch._C._cuda_getDevice()) if dev is not None else None
     capturing = dev is not None and torch.cuda.is_current_stream_capturing()
@@ -107,8 +104,8 @@ def _derived(net):
     # round 6's early generator pass that wait is exposed, tools/phase_timeline.py) the forward forms go first and close the update for
     # the waiting stream (``_pending`` = the event behind them); the backward-data forms and the flipped copies follow behind that event and
     # are picked up through ``_await_backward_copies`` by their first reader, a forward pass later.
-    split = (SPLIT_DEFERRED_DERIVE and bool(net.__dict__.get('_defer_active')) and dev is not None and cur == _SIDE.get(dev) and not capturing)
-    one_launch = DERIVED_ONE_LAUNCH and WTU_FROM_PARAM and bool(wl) and net.__dict__.get('_bwd_wanted', False) and not split
+    split = bool(net.__dict__.get('_defer_active')) and dev is not None and cur == _SIDE.get(dev) and not capturing
+    one_launch = bool(wl) and net.__dict__.get('_bwd_wanted', False) and not split
     if one_launch:
         # forward AND backward-data Winograd forms in one launch on this stream (the two forms share a buffer, network._flat_wuu): the
         # parameter is read while it is hot, no second launch, no cross-stream hop for it at the iteration boundary
@@ -143,7 +140,7 @@ def _derived(net):
     net._derived_bwd_waited = set()
     if not net.__dict__.get('_bwd_wanted', False):
         pass
-    elif (ASYNC_WGRAD and ASYNC_DERIVED and dev is not None and cur != _SIDE.get(dev) and not capturing):
+    elif ASYNC_WGRAD and dev is not None and cur != _SIDE.get(dev) and not capturing:
         side = _side_stream()
         _wait_stream(side, cur)
         with torch.cuda.stream(side):
@@ -232,7 +229,7 @@ def _wino(layer, N, H, cout, transposed=False):
     if not USE_WINOGRAD or getattr(layer, '_wu', None) is None or H < 8:
         return None
     cin = layer.conv.weight.shape[2] if transposed else layer.conv.weight.shape[3]     # input channels of THIS direction
-    if cin < WINO_MIN_CHANNELS or cout < WINO_MIN_COUT:
+    if cin < _WINO_MIN_CHANNELS or cout < _WINO_MIN_COUT:
         return None
     if -(-(N * (H // 2) * (H // 2)) // 64) * -(-cout // 16) < WINO_MIN_WORKGROUPS:
         return None
@@ -371,13 +368,10 @@ def _dgrad_pnbwd(net, gz, layer, N, H, ysaved, r, slope):
 # Weight gradients are leaves of the backward sweeps (nothing downstream reads them before the optimizer), so
 # they are launched on a second HIP stream and overlap the backward-data chain on the main stream: two
 # half-occupancy MFMA kernels share the CUs instead of running back to back.
-ASYNC_WGRAD = _os.environ.get('PGGAN_ASYNC_WGRAD', '1') != '0'
-ASYNC_DERIVED = _os.environ.get('PGGAN_ASYNC_DERIVED', '1') != '0'
-SPLIT_DEFERRED_DERIVE = _os.environ.get('PGGAN_SPLIT_DERIVE', '1') != '0'      # deferred D update: forward forms first, then release the waiting stream
-DERIVED_EVENT = _os.environ.get('PGGAN_DERIVED_EVENT', '1') != '0'    # 0: the round-5 behaviour (ablation for tests/test_e2e_gpu.py::test_derived_refresh_ordering only)
-DERIVED_ONE_LAUNCH = _os.environ.get('PGGAN_DERIVED_ONE_LAUNCH', '1') != '0'      # forward + backward-data Winograd weights of a network: one launch
-# 0: every live layer gets a flipped / transposed copy and the backward-data Winograd form is derived from that copy (round 2)
-WTU_FROM_PARAM = _os.environ.get('PGGAN_WTU_FROM_PARAM', '1') != '0'
+# PGGAN_ASYNC_WGRAD=0 is the single-stream mode: the first thing to try when a missing cross-stream edge is suspected (bench.py toggles
+# the attribute for its serial kernel timing).
+ASYNC_WGRAD = os.environ.get('PGGAN_ASYNC_WGRAD', '1') != '0'
+DERIVED_EVENT = True           # False: no completion event behind a refresh (ablation half of tests/test_e2e_gpu.py::test_derived_refresh_ordering only)
 _SIDE = {}
 
 
@@ -500,29 +494,24 @@ def _grads_ready(net, layers):
 # The gradient-penalty tangent term and the batched adjoint sweep both add to the weight gradient of every D layer.  For the
 # Winograd layers the first contribution (3 images) is not launched on its own: it waits on the layer and rides in the launch of
 # the second (pg_conv2d_wgrad_wino2_nhwc) -- one commit of dW instead of two, and the commit is a third of a 3-image launch.
-DEFER_TANGENT_WGRAD = _os.environ.get('PGGAN_DEFER_TANGENT_WGRAD', '1') != '0'
+DEFER_TANGENT_WGRAD = True     # False: reference half of tests/test_winograd.py::test_deferred_tangent_wgrad_matches_separate_launches
 
 
 def _wino_wgrad_ok(layer, Hin):
-    return (USE_WINOGRAD_WGRAD and layer.ksize == 3 and layer.pad == 1 and Hin >= 16 and not (Hin & (Hin - 1))
-            and min(layer._gw.shape[2], layer._gw.shape[3]) >= WINO_WGRAD_MIN_CHANNELS)
+    return (USE_WINOGRAD and layer.ksize == 3 and layer.pad == 1 and Hin >= 16 and not (Hin & (Hin - 1))
+            and min(layer._gw.shape[2], layer._gw.shape[3]) >= _WINO_WGRAD_MIN_CHANNELS)
 
 
 # The weight gradients of the entry (finest) block are the last and largest launches of the batched sweep: when the main stream finishes
 # the sweep the second stream still has ~0.4 ms of them queued (tools/phase_timeline.py: D.wgrad_end - D.sweep_end at 1024^2), and with the
 # G step's generator pass already done (EarlyG) the main stream has nothing to run until D's update is through.  The last
-# TAIL_WGRAD_ON_MAIN of them (fromRGB, c1, c2 of the entry block, in that order of preference) are therefore launched on the main stream;
+# one or two of them (fromRGB, then c1 of the entry block) are therefore launched on the main stream;
 # the deferred update is ordered behind both streams (defer_to_side).  Not under a bucketed gradient exchange (its flushes wait for the
 # second stream only).
 # Same-box runs with the early generator pass on, ms per step, 0 | 1 | 2 launches on the main stream: 1024^2 10.182 | 10.135 | 10.134 and
-# 10.185 | 10.118 | 10.076; 512^2 13.322 | 13.288 | 13.384.  Default (-1): 2 at 1024^2, 1 at 512^2, none below (the 16-image stages keep both
+# 10.185 | 10.118 | 10.076; 512^2 13.322 | 13.288 | 13.384.  Hence 2 at 1024^2, 1 at 512^2, none below (the 16-image stages keep both
 # streams busy to the end).
-TAIL_WGRAD_ON_MAIN = int(os.environ.get('PGGAN_TAIL_WGRAD_MAIN', '-1'))
-
-
 def _tail_wgrad_on_main(H):
-    if TAIL_WGRAD_ON_MAIN >= 0:
-        return TAIL_WGRAD_ON_MAIN
     return 2 if H >= 1024 else 1 if H >= 512 else 0
 
 
@@ -637,7 +626,7 @@ def generator_forward(G, z, save=False, out=None, pair_out=None):
         H *= 2
         a1, ra1 = layer(h, blk.c1, H, ups=True)                               # upsample fused into the conv
         img = None
-        if (i == depth - 1 and FUSE_TORGB and alpha >= 1.0 and pair_out is None and blk.c2.pixelnorm and blk.c2.ksize == 3 and a1.is_cuda
+        if (i == depth - 1 and alpha >= 1.0 and pair_out is None and blk.c2.pixelnorm and blk.c2.ksize == 3 and a1.is_cuda
                 and _wino(blk.c2, N, H, blk.c2.conv.weight.shape[2]) is None):
             t = blk.toRGB                          # the last conv writes the image too (toRGB in its epilogue: the 1024^2 stage)
             try:
@@ -776,12 +765,10 @@ def _mbstd_bwd(D, gy, x, stats, cp, apply_mask, mask_slope, tx=None, tstats=None
 # The G step's pass through D is followed by a backward-data sweep only (no weight gradients of D): the fp32 output of the entry block's
 # fromRGB layer is then needed by nobody but the block's first conv, which evaluates it in its gather from the image
 # (ops.conv2d_fromrgb: 12 B of image per pixel instead of 32 B written by one launch and read by the next; the 1024^2 stage).
-FUSE_FROMRGB = _os.environ.get('PGGAN_FUSE_FROMRGB', '1') != '0'
-FUSE_FROMRGB_BWD = _os.environ.get('PGGAN_FUSE_FROMRGB_BWD', '1') != '0'      # fromRGB's backward-data in the epilogue of the entry block's backward-data conv (ops.conv2d_masked_fromrgb_bwd)
-FUSE_FROMRGB_WGRAD = _os.environ.get('PGGAN_FUSE_FROMRGB_WGRAD', '1') != '0'  # ... and fromRGB's weight gradient (the batched adjoint sweep: the 8-channel gradient is then never written)
-FUSE_TORGB = _os.environ.get('PGGAN_FUSE_TORGB', '1') != '0'     # the generator's last conv writes the image in its epilogue (ops.conv2d_pixelnorm_torgb)
-
-
+# In the backward sweeps fromRGB's backward-data, and in the batched adjoint sweep its weight gradient too, ride in the epilogue of the entry
+# block's backward-data conv (ops.conv2d_masked_fromrgb_bwd: the 8-channel gradient is then never written); the generator's last conv
+# writes the image in its epilogue (ops.conv2d_pixelnorm_torgb).  The unfused launches are the path of every other shape, of alpha < 1,
+# of a bucketed gradient exchange, and the fallback when a fused launch answers ``ops.Unsupported``.
 def d_forward(D, x, groups=1, keep_input=True):
     """reference network.py:225-240 on a batch of ``groups`` independent minibatches stacked along
     N (minibatch-stddev is evaluated per group).  Returns (scores [NB], ctx with every activation).
@@ -802,7 +789,7 @@ def d_forward(D, x, groups=1, keep_input=True):
     sb = USE_SIGN_BYTES and not pn                                            # byte copies of the fp32 activations (masks)
     curb = None
     fused = None                                 # (a1, a1b) of the entry block when its c1 ran with fromRGB in the gather
-    if not keep_input and FUSE_FROMRGB and sb and r >= SIGN_BYTES_MIN_H and e < nb - 1 and x.is_cuda:
+    if not keep_input and sb and r >= SIGN_BYTES_MIN_H and e < nb - 1 and x.is_cuda:
         c1 = D.blocks[e].c1
         if c1.ksize == 3 and c1.pad == 1 and _wino(c1, NB, r, c1.conv.weight.shape[2]) is None:
             try:
@@ -865,21 +852,16 @@ def d_forward(D, x, groups=1, keep_input=True):
     return s, ctx
 
 
-# ---- split forward: the real third of a D step's [real | fake | mixed] batch ahead of the other two thirds ------------------------
-# The real images' pass through D needs D's weights only -- final since the D update of the PREVIOUS iteration -- while the fake and mixed
-# thirds need G's update.  Trainer therefore evaluates the real third of iteration i + 1 on the second stream under iteration i's G step
-# (3 images, latency-bound launches: the G step leaves the chip mostly idle), and the D step then runs its forward on the other two thirds
-# only.  Both passes write into ONE set of batched activation tensors (ops.Arena), so the adjoint sweeps stay batched over all 3N images.
-class EarlyReal(object):
-    """State of a real-third pass: the image buffer [3N,C,r,r] (rows [0,N) filled), the arena with the batched activations, the first
-    pass's context, what it was computed with (weights version, stage) and the event that closes it."""
+# ---- three-pass forward of a D step: the real, fake and mixed thirds of the [real | fake | mixed] batch as three passes -----------------
+# All three passes write into ONE set of batched activation tensors (ops.Arena), so the adjoint sweeps stay batched over all 3N images.
+class _DForwardBuffers(object):
+    """Buffers of the three-pass D forward, kept per (network, stage, shape) -- launch plans bake their addresses: the image buffer
+    [3N,C,r,r] and the arena with the batched activations."""
 
     def __init__(self):
         self.arena = ops.Arena()
         self.x3 = None
         self.key = None
-        self.real = None
-        self.ctx = self.scores = self.event = self.stamp = None
         self.owner = None                   # weakref to the _ArenaUse token of the D-loss state whose activations live in these buffers
 
 
@@ -898,60 +880,15 @@ def _arena_free(st):
     return tok is None or tok.consumed
 
 
-EARLY_STATS = {'passes': 0, 'used': 0, 'dropped': 0}
-
-
-def d_forward_real_third(D, real):
-    """First pass (current stream): D on the real images, outputs in rows [0, N) of the batched tensors.  Buffers are kept per (network,
-    stage, shape): launch plans bake their addresses, and every reader of the previous iteration is ordered before this writer (the
-    caller enqueues it behind D's update, which is behind every weight gradient of that iteration)."""
-    ops.require_gpu()
-    given = real
-    real = _check_dev(real, 'real images')
-    N = real.shape[0]
-    key = (int(D.depth), tuple(real.shape))
-    st = D.__dict__.get('_early_buffers')                   # (owned by the network: one stage at a time, a step's worth of activations)
-    if st is None or st.key != key:
-        st = D._early_buffers = EarlyReal()
-        st.key = key
-        st.x3 = torch.empty((3 * N,) + tuple(real.shape[1:]), device=real.device, dtype=torch.float32)
-    ops.axpby_mask(real, a=1.0, out=st.x3[:N])
-    with st.arena.pass_(0):
-        st.scores, st.ctx = d_forward(D, st.x3[:N], groups=1)
-    EARLY_STATS['passes'] += 1
-    st.real = given if given.is_contiguous() else None       # (identity of the caller's tensor: what the D step will be handed)
-    st.stamp = (D._param_version, int(D.depth), float(D.alpha))
-    return st
-
-
-def early_real_on_side(D, real):
-    """Enqueue the real-third pass of the NEXT D step on the second stream, behind everything queued there (D's deferred update) and
-    behind the upload of ``real`` (the current stream has waited for it).  Leaves the state in ``D._early_real``."""
-    main = torch.cuda.current_stream(torch._C._cuda_getDevice())
-    side = _side_stream()
-    _wait_stream(side, main)
-    pend, D._pending = D.__dict__.get('_pending'), None      # (the deferred update's event stays for the MAIN stream: this pass is behind the update in stream order)
-    try:
-        with torch.cuda.stream(side):
-            st = d_forward_real_third(D, real)
-            st.event = torch.cuda.Event()
-            _record_event(st.event, side)
-    finally:
-        D._pending = pend
-    real.record_stream(side)
-    D._early_real = st
-    return st
-
-
-def _merge_ctx(D, first, rest, x3, N, third=None):
-    """The context of the whole batch from the contexts of the two (three) passes: every tensor of a pass is a row range of a batched tensor."""
+def _merge_ctx(D, first, rest, x3, N, third):
+    """The context of the whole batch from the contexts of the three passes: every tensor of a pass is a row range of a batched tensor."""
     def whole(a, *bs):
         base = a._base if a._base is not None else a
         if all(b._base is not None and b._base is base for b in bs) and base.shape[0] == a.shape[0] + sum(b.shape[0] for b in bs):
             return base
         raise RuntimeError('split D forward: the passes did not write into one tensor')
     ctx = dict(NB=3 * N, groups=3, depth=first['depth'], alpha=first['alpha'], x=x3, recs=[])
-    others = [rest['recs']] + ([third['recs']] if third is not None else [])
+    others = [rest['recs'], third['recs']]
     for i, ra in enumerate(first['recs']):
         rec = {}
         for k, v in ra.items():
@@ -1043,7 +980,7 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
                                               mask=rec.get('a1b') if rec.get('a1b') is not None else rec['a1'], mask_slope=c1.slope)
                     if full:
                         _flush_wgrad(c2)           # (this launch does not go through _wgrad: a deferred tangent term rides nowhere)
-                        with (_on_main if rec['first'] and tail >= 3 else _on_side)(rec['a1'], gc, gb):
+                        with _on_side(rec['a1'], gc, gb):
                             ops.conv2d_wgrad_unpooled(rec['a1'], gc, gb, gmul, gsl, c2._gw, c2._gb, NB, H, H, c2.c)
                 except ops.Unsupported:                    # (shape checks are identical for both entry points: nothing was accumulated)
                     FALLBACKS['lazy unpool %dx%d' % (H, H)] += 1
@@ -1073,8 +1010,8 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
                 gin = None
                 # fromRGB's weight gradient rides in the same epilogue when the sweep asks for weight gradients -- not under a bucketed
                 # gradient exchange, whose flushes wait for the weight-gradient stream only (as the tail launches on the main stream)
-                fw = full and FUSE_FROMRGB_WGRAD and getattr(D, '_grad_hook', None) is None
-                if (rec['first'] and (want_gimg or fw) and FUSE_FROMRGB_BWD and rec.get('inpb') is not None and x.is_cuda and c1.ksize == 3 and c1.pad == 1
+                fw = full and getattr(D, '_grad_hook', None) is None
+                if (rec['first'] and (want_gimg or fw) and rec.get('inpb') is not None and x.is_cuda and c1.ksize == 3 and c1.pad == 1
                         and _wino(c1, NB, H, c1.conv.weight.shape[3], transposed=True) is None):
                     # the entry block's backward-data conv hands the IMAGE gradient on as well (fromRGB's backward-data in its epilogue); the
                     # 8-channel gradient itself is written only when somebody reads it afterwards (the tangent term of the gradient penalty)
@@ -1113,7 +1050,7 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
             pc2 = prev['blk'].c2
             if prev['first'] and alpha < 1.0:
                 pc2w = pc2.conv.weight.shape
-                if (USE_LAZY_UNPOOL and USE_LAZY_UNPOOL_FADE and not save_adjoints and prev['a2'].dtype == torch.uint8 and pc2w[3] == 8 and pc2w[2] in (8, 16)
+                if (USE_LAZY_UNPOOL and not save_adjoints and prev['a2'].dtype == torch.uint8 and pc2w[3] == 8 and pc2w[2] in (8, 16)
                         and pc2.ksize == 3 and prev['H'] % 32 == 0):
                     # fade-in at the 1024^2 stage: the same lazy pool adjoint as in the fully grown stage (x alpha); the entry block's c2
                     # consumers evaluate it in their gathers instead of reading a 604 MB fine-resolution gradient (round 4)
@@ -1379,18 +1316,11 @@ def _assign_grads(net, layers, linear=False):
         net.linear.bias.grad = net._lin_gb
 
 
-# With the real third already through D (EarlyReal), the fake third of the D step's forward runs on the second stream next to the mixed
-# third's forward and the first backward of the gradient penalty (3-image launches that leave the chip partly idle); its scores are
-# needed by d_loss only.  Same-box pairs, ms per step off | on: 1024^2 10.52 | 10.47, 512^2 13.82 | 13.74, 256^2 23.42 | 23.39, 128^2 equal,
-# 32^2 10.11 | 10.06.  PGGAN_FAKE_SIDE=0: one [fake | mixed] pass on the main stream.
-FAKE_THIRD_ON_SIDE = os.environ.get('PGGAN_FAKE_SIDE', '1') == '1'
 # The real third on the second stream next to the generator's forward of the SAME step (3-image launches with nothing beside them), the
-# fake third behind it on that stream, the mixed third on the main stream: the step time of the look-ahead form (EarlyReal through
-# Trainer: 10.36 | 10.36 ms at 1024^2, 13.41 | 13.41 at 512^2, 23.1 | 23.1 at 256^2, 14.57 | 14.46 at 64^2) without drawing the next batch
-# early, and for every caller of wgan_gp_D_loss: the D step + gradient penalty alone 7.32 -> 7.21 ms at 1024^2, 9.58 -> 9.34 at 512^2,
-# 16.63 -> 16.32 at 256^2.  Default; PGGAN_REAL_SIDE=0 restores the whole-batch forward (and Trainer(early_real_forward=True) /
-# PGGAN_EARLY_REAL=1 the look-ahead pass, which takes precedence when one is pending).
-REAL_THIRD_IN_STEP = os.environ.get('PGGAN_REAL_SIDE', '1') == '1'
+# fake third behind it on that stream, the mixed third on the main stream.  For every caller of wgan_gp_D_loss: the D step + gradient
+# penalty alone 7.32 -> 7.21 ms at 1024^2, 9.58 -> 9.34 at 512^2, 16.63 -> 16.32 at 256^2.  The whole-batch forward stays the path of
+# alpha < 1, a PixelNorm discriminator, the exact-global minibatch stddev, single-stream mode and the CPU emulation of the host tests.
+REAL_THIRD_IN_STEP = True      # False: reference half of tests/test_e2e_gpu.py::test_three_pass_d_forward_matches_whole_batch_forward
 
 
 def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_target):
@@ -1402,37 +1332,13 @@ def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_
     mix = _check_dev(mix, 'mixing factors').view(-1)
     N = real.shape[0]
     D._sync_version()
-    early = take_early_real(D, real)
     fake_done = None
-    arena_st = early
-    if early is not None:
-        # the real third is already through D (Trainer, under the previous G step): the other two thirds follow into the same tensors
-        x3 = early.x3
-        d_step_generator(D, G, latents, x3[N:2 * N])                        # :51-52  (no graph kept)
-        ops.gp_mix(x3[:N], x3[N:2 * N], mix, out=x3[2 * N:])                  # :19
-        if FAKE_THIRD_ON_SIDE:
-            main = torch.cuda.current_stream(torch._C._cuda_getDevice())
-            side = _side_stream()
-            _wait_stream(side, main)
-            with torch.cuda.stream(side):
-                with early.arena.pass_(2):
-                    s_f, ctx_f = d_forward(D, x3[N:2 * N], groups=1)          # :54
-                fake_done = torch.cuda.Event()
-                _record_event(fake_done, side)
-            _early_g_on_side(D, main, side)
-            with early.arena.pass_(3):
-                s_m, ctx_m = d_forward(D, x3[2 * N:], groups=1)               # :20
-            ctx = _merge_ctx(D, early.ctx, ctx_f, x3, N, third=ctx_m)
-        else:
-            with early.arena.pass_(1):
-                s_rest, ctx_rest = d_forward(D, x3[N:], groups=2)             # :54,20
-            ctx = _merge_ctx(D, early.ctx, ctx_rest, x3, N)
-        s = early.scores._base if early.scores._base is not None else early.scores
-    elif (REAL_THIRD_IN_STEP and float(D.alpha) >= 1.0 and not getattr(D, 'pixelnorm', False) and ASYNC_WGRAD and real.is_cuda
-          and hasattr(ops, 'Arena') and D.__dict__.get('_global_stddev') is None     # (exact-global stddev: its collectives stay on one stream, one pass; host tests run the schedules on a CPU emulation of ops: one pass there)
-          and _three_pass_buffers(D, real) is not None):
+    arena_st = None
+    if (REAL_THIRD_IN_STEP and float(D.alpha) >= 1.0 and not getattr(D, 'pixelnorm', False) and ASYNC_WGRAD and real.is_cuda
+            and hasattr(ops, 'Arena') and D.__dict__.get('_global_stddev') is None     # (exact-global stddev: its collectives stay on one stream, one pass; host tests run the schedules on a CPU emulation of ops: one pass there)
+            and _three_pass_buffers(D, real) is not None):
         # the three thirds as three passes into one set of batched tensors (see REAL_THIRD_IN_STEP)
-        st = arena_st = D._early_buffers
+        st = arena_st = D._d_fwd_buffers
         x3 = st.x3
         main = torch.cuda.current_stream(torch._C._cuda_getDevice())
         side = _side_stream()
@@ -1496,29 +1402,13 @@ def _three_pass_buffers(D, real):
     """The per-(network, stage, shape) arena of the three-pass forward, or None when the activations of an earlier D loss of this
     network still live in it (that loss is alive and has not been back-propagated): the caller then takes the allocating one-pass form."""
     key = (int(D.depth), tuple(real.shape))
-    st = D.__dict__.get('_early_buffers')
+    st = D.__dict__.get('_d_fwd_buffers')
     if st is None or st.key != key:
-        st = D._early_buffers = EarlyReal()
+        st = D._d_fwd_buffers = _DForwardBuffers()
         st.key = key
         st.x3 = torch.empty((3 * real.shape[0],) + tuple(real.shape[1:]), device=real.device, dtype=torch.float32)
         return st
     return st if _arena_free(st) else None
-
-
-def take_early_real(D, real):
-    """The real-third pass Trainer left for THIS real batch, if it is still valid (same tensor, same weights, same stage); the current
-    stream is ordered behind it.  None: the caller runs the whole batch."""
-    st = D.__dict__.pop('_early_real', None)
-    if st is None:
-        return None
-    if (st.real is not real or st.stamp != (D._param_version, int(D.depth), float(D.alpha)) or float(D.alpha) < 1.0
-            or getattr(D, 'pixelnorm', False)):
-        EARLY_STATS['dropped'] += 1
-        return None
-    if st.event is not None:
-        _wait_event(torch.cuda.current_stream(torch._C._cuda_getDevice()), st.event)
-    EARLY_STATS['used'] += 1
-    return st
 
 
 # ---- the G step's generator forward, ahead of time -------------------------------------------------------------------------------------
@@ -1528,19 +1418,19 @@ def take_early_real(D, real):
 # step.  The G step opens with G(z') on fresh latents (trainer.py:103-105) with the SAME generator weights the D step used (G is updated at the
 # end of the G step only), so that pass does not have to wait for anything the D step computes: Trainer hands the latents to the D step
 # (``request_early_g``), the D step enqueues G(z') -- with its activations kept for the backward -- on the second stream behind the fake
-# third, and the G step starts from the finished pass with D's forward.  Same kernels, same inputs, same results; PGGAN_EARLY_G=0 turns it off.
+# third, and the G step starts from the finished pass with D's forward.  Same kernels, same inputs, same results.
 # Same-box pairs, ms per step off | on (round 6): 1024^2 10.344 | 10.263, 10.358 | 10.242, 10.363 | 10.219; 512^2 13.52 | 13.39, 13.53 | 13.37;
 # 256^2 23.04 | 22.83; 64^2 (minibatch 16: the chip is full) 14.54 | 14.66; 16^2 5.25 | 5.34 -- on from 256^2 up (the stages whose minibatch
-# leaves the chip partly idle); PGGAN_EARLY_G=0 off, =2 at every stage.
-EARLY_G_FORWARD = os.environ.get('PGGAN_EARLY_G', '1') != '0'
-EARLY_G_MIN_RES = 4 if os.environ.get('PGGAN_EARLY_G', '1') == '2' else int(os.environ.get('PGGAN_EARLY_G_MIN_RES', '256'))
+# leaves the chip partly idle).
+EARLY_G_FORWARD = True         # False: reference half of tests/test_e2e_gpu.py::test_trainer_early_g_forward_matches_in_step_forward
+EARLY_G_MIN_RES = 256          # 4 in tests/test_e2e_gpu.py::test_early_g_forward_is_the_same_pass (the pass at a small test stage)
 # Two forms: 'side' = on the second stream behind the fake third (the stages whose minibatch leaves the chip partly idle: from 256^2 up);
 # 'batched' = ONE generator pass over [z | z'] in place of the D step's G(z) (the launch-bound 4x4 stage: half the generator launches per
 # iteration, 1.166 -> 0.997 ms per step).  Same-box pairs, ms per step side | batched: 1024^2 10.31 | 10.55, 10.28 | 10.48, 10.33 | 10.46 (a
 # 6-image pass takes 1.50 ms against 1.02 and holds the fake third back); 512^2 13.40 | 13.51; 256^2 23.25 | 23.29; off | batched: 128^2
-# 20.05 | 20.23, 64^2 14.66 | 14.77, 16^2 5.24 | 5.42.  PGGAN_EARLY_G_MODE=side / batched forces one form wherever the pass runs at all.
-EARLY_G_MODE = os.environ.get('PGGAN_EARLY_G_MODE', 'auto')
-EARLY_G_BATCHED_MAX_RES = int(os.environ.get('PGGAN_EARLY_G_BATCHED_MAX_RES', '4'))
+# 20.05 | 20.23, 64^2 14.66 | 14.77, 16^2 5.24 | 5.42.
+EARLY_G_MODE = 'auto'          # 'side' / 'batched' in the two tests above: one form wherever the pass runs at all
+_EARLY_G_BATCHED_MAX_RES = 4
 
 
 def early_g_mode(depth):
@@ -1549,8 +1439,8 @@ def early_g_mode(depth):
         return None
     res = 4 * 2 ** int(depth)
     if EARLY_G_MODE == 'auto':
-        return 'batched' if res <= EARLY_G_BATCHED_MAX_RES else 'side' if res >= EARLY_G_MIN_RES else None
-    return EARLY_G_MODE if (res >= EARLY_G_MIN_RES or res <= EARLY_G_BATCHED_MAX_RES) else None
+        return 'batched' if res <= _EARLY_G_BATCHED_MAX_RES else 'side' if res >= EARLY_G_MIN_RES else None
+    return EARLY_G_MODE if (res >= EARLY_G_MIN_RES or res <= _EARLY_G_BATCHED_MAX_RES) else None
 EARLY_G_STATS = {'passes': 0, 'used': 0, 'dropped': 0}
 
 

@@ -12,14 +12,15 @@ from . import engine
 # wgan_gp_loss.py:4-5 keeps module-global scratch; the only state kept here is the injectable RNG.
 mixing_factors = None
 _seed = None                # [seed, draws so far, torch seed it came from] of the mixing-factor stream; None: seeded from torch's RNG at first use
-_use_graphs = 'auto'        # 'auto': launch plans (hipGraphs at the 4x4 stage only with GRAPH_STAGE0); True: hipGraphs everywhere; False: eager
+_use_graphs = 'auto'        # 'auto': launch plans; True: hipGraphs everywhere; False: eager
 
 
 def enable_graphs(flag=True):
     """How the D-step / G-step schedules are issued whenever alpha == 1:
     ``'auto'`` (default): every stage is replayed from a recorded LAUNCH PLAN (plans.py: the same kernels on the same streams with the
-    same events as the eager path, minus the Python between them; ``enable_plans(False)`` turns that off) -- the 4x4 stage included since
-    round 6 (``GRAPH_STAGE0``: it used to replay captured hipGraphs, graphs.py);
+    same events as the eager path, minus the Python between them; ``enable_plans(False)`` turns that off) -- the 4x4 stage included
+    (minibatch 16, ms per step hipGraph | plan: 1.121 | 0.924; with a one-rank RCCL communicator 4.09 | 1.09 -- a graph replay serialises
+    the streams and cannot carry the bucket collectives);
     ``True``: hipGraph replay everywhere (measured slower from 8x8 on: the replay serialises the weight-gradient stream);
     ``False``: eager launches (per-launch instrumentation, debugging)."""
     global _use_graphs
@@ -31,7 +32,7 @@ def enable_graphs(flag=True):
 
 
 def enable_plans(flag=True):
-    """Launch-plan replay of the stages above 4x4 (see ``enable_graphs``).  Under data parallelism the bucket collectives of the
+    """Launch-plan replay of every stage (see ``enable_graphs``).  Under data parallelism the bucket collectives of the
     sweep are part of the plan (the library's RCCL communicator); Trainer turns plans off only when the reduction goes through
     torch.distributed (CPU hosts)."""
     global _use_plans
@@ -41,19 +42,14 @@ def enable_plans(flag=True):
         plans.clear()
 
 
-_use_plans = __import__('os').environ.get('PGGAN_PLANS', '1') != '0'
-# The 4x4 stage used to replay captured hipGraphs in 'auto' mode (round 3: 1.44x the eager launches).  Since the launch plans exist the plan
-# is the faster form there as well (round 6, 4x4 stage, minibatch 16, ms per step graph | plan: 1.121 | 0.924; with a one-rank RCCL
-# communicator 4.09 | 1.09 -- a graph replay serialises the streams and cannot carry the bucket collectives).  PGGAN_GRAPH_STAGE0=1 restores
-# the graph at that stage; ``enable_graphs(True)`` still captures every stage.
-GRAPH_STAGE0 = __import__('os').environ.get('PGGAN_GRAPH_STAGE0', '0') == '1'
+_use_plans = True           # set through ``enable_plans``; tests/test_e2e_gpu.py and tests/test_collective_gpu.py flip it without dropping the recorded plans
 
 
 def _replay_mode(net):
     """'graph' | 'plan' | None (eager) for a step of ``net`` at its current growth stage (alpha == 1 is checked by the callers)."""
     if _use_graphs is False:
         return None
-    if _use_graphs is True or (int(net.depth) == 0 and GRAPH_STAGE0):
+    if _use_graphs is True:
         return 'graph'
     return 'plan' if _use_plans else None
 
