@@ -19,6 +19,7 @@ minibatch-stddev Hessian-vector term injected into the ordinary batched backward
 samples (SURVEY.md §7 "hard parts"; formulas verified against autograd in tests/).
 """
 import collections as _collections
+import contextlib as _contextlib
 import os
 import weakref as _weakref
 
@@ -76,18 +77,19 @@ def _derived(net):
     at this stage only (at 4x4 that is 2 of the 18 conv layers of a network: re-deriving all 73 MB per update cost ~0.5 ms of
     a 1.6 ms step)."""
     net._ensure_buffers()
+    rt = net._rt
     key = (net._param_version, int(net.depth))
-    if net._derived_ver == key:
+    if rt.derived_ver == key:
         return
     base = net._flat_param.data_ptr()
     live = set(id(m) for m in _live_conv_layers(net))
     # flipped / transposed copies: only for the layers whose backward-data conv has asked for one (_wt marks them) -- the layers that
     # always run Winograd there get their backward-data form straight from the parameter (transposed=True below)
-    todo = [m for m in net._layers() if m.kind == 'conv' and m._wt is not None and id(m) in live and getattr(m, '_wt_wanted', False)]
+    todo = [m for m in net._layers() if m.kind == 'conv' and m._wt is not None and id(m) in live and m._wt_wanted]
     packs = [((m.conv.weight.data_ptr() - base) // 4, m.ksize, m.conv.weight.shape[2], m.conv.weight.shape[3]) for m in todo]
     # ... and of those only the layers the Winograd path has actually asked for (_wino marks them): the 512-channel layers of the
     # 4x4 stage never reach it, yet are a large part of all Winograd-domain bytes
-    wl = [(m, woff, uoff) for m, woff, uoff in (net._wino_layers or []) if id(m) in live and getattr(m, '_wino_wanted', False)]
+    wl = [(m, woff, uoff) for m, woff, uoff in (net._wino_layers or []) if id(m) in live and m._wino_wanted]
     wl = wl if USE_WINOGRAD else []
 
     def backward_copies():                       # what only the backward-data convs read: flipped / transposed weights and the Winograd form of those
@@ -102,10 +104,10 @@ def _derived(net):
     capturing = dev is not None and torch.cuda.is_current_stream_capturing()
     # Inside a deferred update (defer_to_side: Adam + this refresh on the second stream while the main stream waits for D's weights -- since
     # round 6's early generator pass that wait is exposed, tools/phase_timeline.py) the forward forms go first and close the update for
-    # the waiting stream (``_pending`` = the event behind them); the backward-data forms and the flipped copies follow behind that event and
+    # the waiting stream (``_rt.pending`` = the event behind them); the backward-data forms and the flipped copies follow behind that event and
     # are picked up through ``_await_backward_copies`` by their first reader, a forward pass later.
-    split = bool(net.__dict__.get('_defer_active')) and dev is not None and cur == _SIDE.get(dev) and not capturing
-    one_launch = bool(wl) and net.__dict__.get('_bwd_wanted', False) and not split
+    split = rt.defer_active and dev is not None and cur == _SIDE.get(dev) and not capturing
+    one_launch = bool(wl) and rt.bwd_wanted and not split
     if one_launch:
         # forward AND backward-data Winograd forms in one launch on this stream (the two forms share a buffer, network._flat_wuu): the
         # parameter is read while it is hot, no second launch, no cross-stream hop for it at the iteration boundary
@@ -127,18 +129,18 @@ def _derived(net):
     # forward refreshes D's derived weights from inside its real-third pass on the second stream whenever the update did not come through
     # Trainer's deferred update -- the public ``loss.backward(); optimizer.step()`` loop, a foreign optimizer, load_state_dict -- while the
     # mixed third on the main stream was ordered behind the image copy only (docs/experiments_r6.md §1).
-    net._derived_ev = None
-    net._derived_waited = set()
+    rt.derived_ev = None
+    rt.derived_waited = set()
     if dev is not None and DERIVED_EVENT and not capturing:
         ev = torch.cuda.Event()
         _record_event(ev, cur)
-        net._derived_ev = ev
-        net._derived_waited = {cur.cuda_stream}
+        rt.derived_ev = ev
+        rt.derived_waited = {cur.cuda_stream}
         if split:
-            net._pending_ev = ev
-    net._derived_bwd_ev = None
-    net._derived_bwd_waited = set()
-    if not net.__dict__.get('_bwd_wanted', False):
+            rt.pending_ev = ev
+    rt.derived_bwd_ev = None
+    rt.derived_bwd_waited = set()
+    if not rt.bwd_wanted:
         pass
     elif ASYNC_WGRAD and dev is not None and cur != _SIDE.get(dev) and not capturing:
         side = _side_stream()
@@ -150,24 +152,24 @@ def _derived(net):
         for buf in (net._flat_wt, net._flat_wtu):  # written on the side stream: the allocator must not hand the block on before that
             if buf is not None:
                 buf.record_stream(side)
-        net._derived_bwd_ev = ev
+        rt.derived_bwd_ev = ev
     else:
         backward_copies()                        # inline, on ``cur``: readers on other streams are ordered behind this event
         if dev is not None and DERIVED_EVENT and not capturing:
             ev = torch.cuda.Event()
             _record_event(ev, cur)
-            net._derived_bwd_ev = ev
-            net._derived_bwd_waited = {cur.cuda_stream}
-    net._derived_ver = key
-    net._derived_live = live
+            rt.derived_bwd_ev = ev
+            rt.derived_bwd_waited = {cur.cuda_stream}
+    rt.derived_ver = key
+    rt.derived_live = live
 
 
 def _await_derived(net):
     """The current stream waits (once) for the last refresh of the derived weights if that ran on another stream."""
-    ev = net.__dict__.get('_derived_ev')
+    ev = net._rt.derived_ev
     if ev is not None:
         cur = torch.cuda.current_stream(torch._C._cuda_getDevice())
-        waited = net._derived_waited
+        waited = net._rt.derived_waited
         if cur.cuda_stream not in waited and not torch.cuda.is_current_stream_capturing():
             cur.wait_event(ev)
             waited.add(cur.cuda_stream)
@@ -177,18 +179,18 @@ def order_side_behind_derived(net):
     """plans.py, before a replay: the recorded body's per-launch ``_await_derived`` calls are not part of a plan (they are no-ops in
     the orders a plan is entered with), so the one ordering a replay could miss -- the second stream behind a refresh ``_prologue`` just
     issued on the main stream -- is established here, once per step."""
-    ev = net.__dict__.get('_derived_ev')
+    ev = net._rt.derived_ev
     if ev is not None and ASYNC_WGRAD:
         side = _side_stream()
-        if side.cuda_stream not in net._derived_waited:
+        if side.cuda_stream not in net._rt.derived_waited:
             side.wait_event(ev)
-            net._derived_waited.add(side.cuda_stream)
+            net._rt.derived_waited.add(side.cuda_stream)
 
 
 def _assert_live(net, layer):
     """The derived copies are refreshed for the layers that are live at the network's current growth stage only: asking for
     any other layer's would silently compute with the weights of an earlier optimizer step."""
-    if id(layer) not in net._derived_live:
+    if id(layer) not in net._rt.derived_live:
         raise RuntimeError('derived weights requested for a conv layer that is not live at depth %d' % int(net.depth))
 
 
@@ -196,26 +198,26 @@ def _await_backward_copies(net):
     """The current stream waits for the side-stream refresh of the backward-only derived weights.  The event stays until the
     next refresh, so that EVERY stream that consumes (or, for the optimizer, overwrites the source of) the copies is ordered
     behind it, each once."""
-    ev = net.__dict__.get('_derived_bwd_ev')
+    ev = net._rt.derived_bwd_ev
     if ev is not None:
         cur = torch.cuda.current_stream(torch._C._cuda_getDevice())
-        waited = net.__dict__.setdefault('_derived_bwd_waited', set())
+        waited = net._rt.derived_bwd_waited
         if cur.cuda_stream not in waited:
             _wait_event(cur, ev)
             waited.add(cur.cuda_stream)
 
 
 def _want_backward_copies(net):
-    if not net.__dict__.get('_bwd_wanted', False):      # first backward sweep of this network: from now on every refresh includes them
-        net._bwd_wanted = True
-        net._derived_ver = None
+    if not net._rt.bwd_wanted:                          # first backward sweep of this network: from now on every refresh includes them
+        net._rt.bwd_wanted = True
+        net._rt.derived_ver = None
 
 
 def _wt(net, layer):
     """Backward-data (flipped/transposed) copy of a conv layer's weights, refreshed lazily."""
-    if not getattr(layer, '_wt_wanted', False):         # first request: from now on the refresh after every update includes this layer
+    if not layer._wt_wanted:                            # first request: from now on the refresh after every update includes this layer
         layer._wt_wanted = True
-        net._derived_ver = None
+        net._rt.derived_ver = None
     _want_backward_copies(net)
     _derived(net)
     _assert_live(net, layer)
@@ -234,9 +236,9 @@ def _wino(layer, N, H, cout, transposed=False):
     if -(-(N * (H // 2) * (H // 2)) // 64) * -(-cout // 16) < WINO_MIN_WORKGROUPS:
         return None
     net = layer._net()
-    if not getattr(layer, '_wino_wanted', False):       # first request: from now on the refresh after every update includes this layer
+    if not layer._wino_wanted:                          # first request: from now on the refresh after every update includes this layer
         layer._wino_wanted = True
-        net._derived_ver = None
+        net._rt.derived_ver = None
     if transposed:
         _want_backward_copies(net)
     _derived(net)
@@ -455,35 +457,36 @@ def defer_to_side(net, fn):
     main = torch.cuda.current_stream(torch._C._cuda_getDevice())
     side = _side_stream()
     side.wait_stream(main)
-    net._defer_active = True
+    rt = net._rt
+    rt.defer_active = True
     try:
         with torch.cuda.stream(side):
             fn()
-            ev = net.__dict__.pop('_pending_ev', None)      # (_derived: the event behind Adam + the forward forms; the rest of the refresh follows it)
+            ev = rt.take('pending_ev')                      # (_derived: the event behind Adam + the forward forms; the rest of the refresh follows it)
             if ev is None:
                 ev = torch.cuda.Event()
                 ev.record(side)
     finally:
-        net._defer_active = False
-    net._pending = ev
+        rt.defer_active = False
+    rt.pending = ev
 
 
 def wait_pending(net):
     """The current stream waits for a deferred update of ``net`` (no-op when there is none)."""
-    ev = getattr(net, '_pending', None)
+    ev = net._rt.pending
     if ev is not None:
         torch.cuda.current_stream(torch._C._cuda_getDevice()).wait_event(ev)
-        net._pending = None
+        net._rt.pending = None
 
 
 def _grads_ready(net, layers):
-    """Tell the gradient exchange (``parallel.GradExchange``, installed by ``Trainer`` as ``net._grad_hook`` under data
+    """Tell the gradient exchange (``parallel.GradExchange``, installed by ``Trainer`` as ``net._rt.grad_hook`` under data
     parallelism) that every weight-gradient launch of ``layers`` has been enqueued: their spans of the flat gradient
     buffer can start travelling while the sweep goes on."""
-    hook = getattr(net, '_grad_hook', None)
+    hook = net._rt.grad_hook
     if hook is not None:
         for m in layers:                         # "complete" must never precede a deferred contribution that nothing carried
-            if m.__dict__.get('_pending_wgrad') is not None:
+            if m._pending_wgrad is not None:
                 _flush_wgrad(m)
         side = None
         if ASYNC_WGRAD and net._flat_param.is_cuda:
@@ -515,15 +518,8 @@ def _tail_wgrad_on_main(H):
     return 2 if H >= 1024 else 1 if H >= 512 else 0
 
 
-class _on_main(object):
-    def __init__(self, *tensors):
-        pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
+def _on_main(*tensors):
+    return _contextlib.nullcontext()
 
 
 def _wgrad(x, gz, layer, N, Hin, bias=True, ups=False, defer=False, on_main=False):
@@ -535,7 +531,7 @@ def _wgrad(x, gz, layer, N, Hin, bias=True, ups=False, defer=False, on_main=Fals
     if defer and wino and DEFER_TANGENT_WGRAD and not bias and not ups:
         layer._pending_wgrad = (x, gz, N, Hin)
         return
-    pend = layer.__dict__.get('_pending_wgrad')
+    pend = layer._pending_wgrad
     if pend is not None and not (wino and pend[3] == Hin and not ups):
         _flush_wgrad(layer)
         pend = None
@@ -551,7 +547,7 @@ def _wgrad(x, gz, layer, N, Hin, bias=True, ups=False, defer=False, on_main=Fals
 
 def _flush_wgrad(layer):
     """Launch a deferred contribution on its own (nothing came to carry it)."""
-    pend = layer.__dict__.get('_pending_wgrad')
+    pend = layer._pending_wgrad
     if pend is None:
         return
     layer._pending_wgrad = None
@@ -725,25 +721,21 @@ def generator_backward(G, ctx, g_out):
 # the one scalar a group's statistic is (and the three scalars its adjoint / Hessian-vector term need: G_sigma, <v, x - mu>, mean v) are
 # reduced over all ranks, so world x mb equals one process at batch world * mb.  The collectives are a few floats each on the main
 # stream, in the same order on every rank; steps are launched eagerly in this mode (wgan_gp_loss: no hipGraph / launch plan).
-def _mb_dp(D):
-    return D.__dict__.get('_global_stddev')
-
-
 def _mbstd_fwd(D, x, groups, cp):
-    dp = _mb_dp(D)
+    dp = D._rt.global_stddev
     if dp is None:
         return ops.mbstd_fwd(x, groups, cp)
     # the split kernels take the element count of the whole group as local count x ranks (csrc/elementwise.hip mbstd_write_kernel):
     # equal per-rank batches are part of the mode's contract -- checked here, once per batch shape (it was only claimed)
-    if D.__dict__.get('_gs_checked') != (int(x.shape[0]), groups):
+    if D._rt.gs_checked != (int(x.shape[0]), groups):
         dp.assert_same_on_all_ranks(int(x.shape[0]) // groups, 'exact-global minibatch stddev: the per-rank minibatch size')
-        D._gs_checked = (int(x.shape[0]), groups)
+        D._rt.gs_checked = (int(x.shape[0]), groups)
     st = ops.mbstd_stats(x, groups)
     return ops.mbstd_write(x, st, dp.all_gather_rows(st), cp)
 
 
 def _mbstd_tangent(D, x, tx, stats, cp):
-    dp = _mb_dp(D)
+    dp = D._rt.global_stddev
     if dp is None:
         return ops.mbstd_tangent(x, tx, stats, cp)
     ts = ops.mbstd_tangent_stats(x, tx, stats)
@@ -751,12 +743,24 @@ def _mbstd_tangent(D, x, tx, stats, cp):
 
 
 def _mbstd_bwd(D, gy, x, stats, cp, apply_mask, mask_slope, tx=None, tstats=None, gy_first=None, out=None):
-    dp = _mb_dp(D)
+    dp = D._rt.global_stddev
     if dp is None:
         return ops.mbstd_bwd(gy, x, stats, cp, apply_mask, mask_slope, tx=tx, tstats=tstats, gy_first=gy_first, out=out)
     gs = ops.mbstd_gsum(gy, gy_first if tx is not None else None, stats.shape[0], tuple(x.shape), cp)
     dp.all_reduce_flat(gs.view(-1))
     return ops.mbstd_bwd_global(gy, x, stats, cp, apply_mask, gs, dp.world_size, mask_slope, tx=tx, tstats=tstats, gy_first=gy_first, out=out)
+
+
+def _mbstd_bwd_hvp(D, g_head, g_mixed, rec, hvp, fr_slope):
+    """Minibatch-stddev adjoint of the last block ``rec`` under the gradient penalty: the head images take ``g_head``; the mixed images behind
+    them (one extra group) take ``g_mixed`` (None: they have no first-order gradient) plus the Hessian-vector injection of ``hvp``."""
+    nh, tx, tstats, gy_first = hvp[:4]
+    inp, stats, cp = rec['inp'], rec['stats'], rec['blk'].c1.cin_store
+    gin = torch.empty_like(inp)
+    ng = stats.shape[0] - 1
+    _mbstd_bwd(D, g_head, inp[:nh], stats[:ng], cp, rec['first'], fr_slope, out=gin[:nh])
+    _mbstd_bwd(D, g_mixed, inp[nh:], stats[ng:], cp, rec['first'], fr_slope, tx=tx, tstats=tstats, gy_first=gy_first, out=gin[nh:])
+    return gin
 
 
 # ------------------------------------------------------------------------------------------
@@ -915,6 +919,15 @@ def _slice_ctx(ctx, a, b, g0, g1):
     return sub
 
 
+def _lazy_unpool_ok(rec, save_adjoints):
+    """May the pool adjoint behind block ``rec`` stay un-evaluated, for the consumers of the block's c2 gradient to apply in their gathers
+    (ops.conv2d_unpooled / conv2d_wgrad_unpooled)?  Needs c2's output as sign bytes and the 8-channel 3x3 layers those kernels are built for."""
+    c2 = rec['blk'].c2
+    w = c2.conv.weight.shape
+    return (USE_LAZY_UNPOOL and not save_adjoints and rec['a2'].dtype == torch.uint8 and w[3] == 8 and w[2] in (8, 16)
+            and c2.ksize == 3 and rec['H'] % 32 == 0)
+
+
 def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
     """First-order adjoint sweep through D for the batch in ``ctx``.
 
@@ -936,7 +949,7 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
     nh = NB if hvp is None else hvp[0]
     a2 = lastrec['a2']
     lc2 = lastrec['blk'].c2
-    tail = _tail_wgrad_on_main(recs[0]['H']) if (full and ASYNC_WGRAD and getattr(D, '_grad_hook', None) is None and len(recs) > 1) else 0
+    tail = _tail_wgrad_on_main(recs[0]['H']) if (full and ASYNC_WGRAD and D._rt.grad_hook is None and len(recs) > 1) else 0
     if full:
         ops.linear1_wgrad(gscore, a2[:nh], D._lin_gw, D._lin_gb)
     g = ops.linear1_bwd_data(gscore, D.linear.weight.data, a2[:nh], (nh,) + tuple(a2.shape[1:]), lc2.slope)
@@ -962,12 +975,7 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
             if hvp is None:
                 gin = _mbstd_bwd(D, gmb, inp, rec['stats'], cp, rec['first'], fr_slope)
             else:
-                _, tx, tstats, gy_first = hvp
-                gin = torch.empty_like(inp)
-                ng = rec['stats'].shape[0] - 1
-                _mbstd_bwd(D, gmb, inp[:nh], rec['stats'][:ng], cp, rec['first'], fr_slope, out=gin[:nh])
-                _mbstd_bwd(D, None, inp[nh:], rec['stats'][ng:], cp, rec['first'], fr_slope,
-                           tx=tx, tstats=tstats, gy_first=gy_first, out=gin[nh:])
+                gin = _mbstd_bwd_hvp(D, gmb, None, rec, hvp, fr_slope)
             if save_adjoints:
                 adj[idx].update(gz2=gz2, gz1=gz1, gmb=gmb)
         else:
@@ -997,9 +1005,7 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
             g_fused = None
             if not rec['first'] and not (recs[idx - 1]['first'] and alpha < 1.0):
                 pv = recs[idx - 1]
-                pc2w = pv['blk'].c2.conv.weight.shape
-                if (USE_LAZY_UNPOOL and not save_adjoints and pv['a2'].dtype == torch.uint8 and pc2w[3] == 8 and pc2w[2] in (8, 16)
-                        and pv['blk'].c2.ksize == 3 and pv['H'] % 32 == 0):
+                if _lazy_unpool_ok(pv, save_adjoints):
                     # plain coarse gradient; the finer block's c2 consumers apply the pool adjoint in their gathers
                     carry = (_dgrad(D, gz1, c1, NB, H), pv['a2'], 0.25, pv['blk'].c2.slope)
                 else:
@@ -1010,7 +1016,7 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
                 gin = None
                 # fromRGB's weight gradient rides in the same epilogue when the sweep asks for weight gradients -- not under a bucketed
                 # gradient exchange, whose flushes wait for the weight-gradient stream only (as the tail launches on the main stream)
-                fw = full and getattr(D, '_grad_hook', None) is None
+                fw = full and D._rt.grad_hook is None
                 if (rec['first'] and (want_gimg or fw) and rec.get('inpb') is not None and x.is_cuda and c1.ksize == 3 and c1.pad == 1
                         and _wino(c1, NB, H, c1.conv.weight.shape[3], transposed=True) is None):
                     # the entry block's backward-data conv hands the IMAGE gradient on as well (fromRGB's backward-data in its epilogue); the
@@ -1049,9 +1055,7 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
             prev = recs[idx - 1]
             pc2 = prev['blk'].c2
             if prev['first'] and alpha < 1.0:
-                pc2w = pc2.conv.weight.shape
-                if (USE_LAZY_UNPOOL and not save_adjoints and prev['a2'].dtype == torch.uint8 and pc2w[3] == 8 and pc2w[2] in (8, 16)
-                        and pc2.ksize == 3 and prev['H'] % 32 == 0):
+                if _lazy_unpool_ok(prev, save_adjoints):
                     # fade-in at the 1024^2 stage: the same lazy pool adjoint as in the fully grown stage (x alpha); the entry block's c2
                     # consumers evaluate it in their gathers instead of reading a 604 MB fine-resolution gradient (round 4)
                     carry = (gin, prev['a2'], 0.25 * alpha, pc2.slope)
@@ -1153,12 +1157,7 @@ def _d_backward_pn(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=Non
             if hvp is None:
                 gin = _mbstd_bwd(D, gmb, inp, rec['stats'], cp, rec['first'], fr_slope)
             else:
-                _, tx, tstats, gy_first = hvp[:4]
-                gin = torch.empty_like(inp)
-                ng = rec['stats'].shape[0] - 1
-                _mbstd_bwd(D, gmb[:nh], inp[:nh], rec['stats'][:ng], cp, rec['first'], fr_slope, out=gin[:nh])
-                _mbstd_bwd(D, gmb[nh:], inp[nh:], rec['stats'][ng:], cp, rec['first'], fr_slope,
-                           tx=tx, tstats=tstats, gy_first=gy_first, out=gin[nh:])
+                gin = _mbstd_bwd_hvp(D, gmb[:nh], gmb[nh:], rec, hvp, fr_slope)
             if save_adjoints:
                 adj[idx].update(gz2=gz2, gz1=gz1, gmb=gmb)
         else:
@@ -1335,10 +1334,10 @@ def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_
     fake_done = None
     arena_st = None
     if (REAL_THIRD_IN_STEP and float(D.alpha) >= 1.0 and not getattr(D, 'pixelnorm', False) and ASYNC_WGRAD and real.is_cuda
-            and hasattr(ops, 'Arena') and D.__dict__.get('_global_stddev') is None     # (exact-global stddev: its collectives stay on one stream, one pass; host tests run the schedules on a CPU emulation of ops: one pass there)
+            and hasattr(ops, 'Arena') and D._rt.global_stddev is None     # (exact-global stddev: its collectives stay on one stream, one pass; host tests run the schedules on a CPU emulation of ops: one pass there)
             and _three_pass_buffers(D, real) is not None):
         # the three thirds as three passes into one set of batched tensors (see REAL_THIRD_IN_STEP)
-        st = arena_st = D._d_fwd_buffers
+        st = arena_st = D._rt.d_fwd_buffers
         x3 = st.x3
         main = torch.cuda.current_stream(torch._C._cuda_getDevice())
         side = _side_stream()
@@ -1402,9 +1401,9 @@ def _three_pass_buffers(D, real):
     """The per-(network, stage, shape) arena of the three-pass forward, or None when the activations of an earlier D loss of this
     network still live in it (that loss is alive and has not been back-propagated): the caller then takes the allocating one-pass form."""
     key = (int(D.depth), tuple(real.shape))
-    st = D.__dict__.get('_d_fwd_buffers')
+    st = D._rt.d_fwd_buffers
     if st is None or st.key != key:
-        st = D._d_fwd_buffers = _DForwardBuffers()
+        st = D._rt.d_fwd_buffers = _DForwardBuffers()
         st.key = key
         st.x3 = torch.empty((3 * real.shape[0],) + tuple(real.shape[1:]), device=real.device, dtype=torch.float32)
         return st
@@ -1472,10 +1471,10 @@ def d_step_generator(D, G, latents, out):
     announced the G step's latents z' (``request_early_g``) the two passes run as ONE pass over [z | z'] -- the same weights, twice the
     images per launch, and the <= 64x64 layers of a 3-image pass are latency-bound launches that take 6 images in nearly the same time --
     and the second half (with its activations) is left for the G step as an ``EarlyG``."""
-    req = D.__dict__.get('_early_g_request') if early_g_mode(G.depth) == 'batched' else None
+    req = D._rt.early_g_request if early_g_mode(G.depth) == 'batched' else None
     if req is None or req[0] is not G or tuple(req[1].shape) != tuple(latents.shape):
         return generator_forward(G, latents, out=out)
-    D.__dict__.pop('_early_g_request', None)
+    D._rt.early_g_request = None
     zg = _check_dev(req[1], 'latents')
     N = latents.shape[0]
     z2 = torch.empty((2 * N,) + tuple(latents.shape[1:]), device=latents.device, dtype=torch.float32)
@@ -1489,19 +1488,19 @@ def d_step_generator(D, G, latents, out):
     _record_event(eg.event, torch.cuda.current_stream(torch._C._cuda_getDevice()))
     eg.latents = zg
     eg.stamp = (G._param_version, int(G.depth), float(G.alpha))
-    G._early_fwd = eg
+    G._rt.early_fwd = eg
     EARLY_G_STATS['passes'] += 1
     return img
 
 
 def request_early_g(D, G, latents):
     """Trainer, before the D loss: the next G loss of this iteration will be ``wgan_gp_G_loss(G, D, latents)``."""
-    D._early_g_request = (G, latents)
+    D._rt.early_g_request = (G, latents)
 
 
 def _early_g_on_side(D, main, side):
     """Inside ``d_loss_forward``, right after the fake third was queued on the second stream: the requested generator pass behind it."""
-    req = D.__dict__.pop('_early_g_request', None)
+    req = D._rt.take('early_g_request')
     if req is None or early_g_mode(req[0].depth) != 'side':
         return
     G, z = req
@@ -1520,14 +1519,14 @@ def _early_g_on_side(D, main, side):
             t.record_stream(main)
     eg.latents = z
     eg.stamp = (G._param_version, int(G.depth), float(G.alpha))
-    G._early_fwd = eg
+    G._rt.early_fwd = eg
     EARLY_G_STATS['passes'] += 1
 
 
 def take_early_g(G, latents):
     """The generator pass the D step left for exactly these latents, if it is still valid (same tensor, same weights, same stage); the
     current stream is ordered behind it.  None: the caller runs the pass itself."""
-    eg = G.__dict__.pop('_early_fwd', None)
+    eg = G._rt.take('early_fwd')
     if eg is None:
         return None
     if eg.latents is not latents or eg.stamp != (G._param_version, int(G.depth), float(G.alpha)):
@@ -1549,7 +1548,7 @@ def d_loss_backward(state, scale=1.0):
         tok.consumed = True
     ops.zero_(D._flat_grad)
     if scale != 1.0:
-        D._grad_hook = None                      # the gradients are rescaled after the sweep: nothing may travel early
+        D._rt.grad_hook = None                   # the gradients are rescaled after the sweep: nothing may travel early
     for lay in _live_conv_layers(D):             # (nothing of an aborted earlier step may ride along)
         lay._pending_wgrad = None
     hvp = d_tangent_wgrad(D, state['sub'], state['adj'], state['u'])
@@ -1562,9 +1561,9 @@ def d_loss_backward(state, scale=1.0):
     if PROBES is not None and ASYNC_WGRAD and D._flat_param.is_cuda:
         with torch.cuda.stream(_side_stream()):
             probe('D.wgrad_end')
-    if not (getattr(D, '_skip_join', False) and scale == 1.0):
+    if not (D._rt.skip_join and scale == 1.0):
         _join_side()         # default: the gradients are complete for whatever the caller does next on this stream
-    # (Trainer sets _skip_join when the whole D update follows on the second stream, in order behind the weight
+    # (Trainer sets skip_join when the whole D update follows on the second stream, in order behind the weight
     #  gradients: the main stream then goes straight on to the G step instead of idling under the last, largest
     #  weight-gradient launches of the 1024^2 layers)
     if scale != 1.0:
@@ -1598,7 +1597,7 @@ def g_loss_backward(state, scale=1.0):
     G._ensure_buffers()
     ops.zero_(G._flat_grad)
     if scale != 1.0:
-        G._grad_hook = None
+        G._rt.grad_hook = None
     gimg, _ = d_backward(D, state['dctx'], state['gscore'], full=False, want_gimg=True)
     probe('G.d_bwd_end')
     active = generator_backward(G, state['gctx'], gimg)

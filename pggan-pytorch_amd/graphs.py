@@ -33,23 +33,6 @@ def clear():
     ops.release_capture_workspaces()          # the capture streams are gone with the graphs
 
 
-def _force_repack(net, layers):
-    """The derived backward-data weights must be re-packed on EVERY replay: make them stale so that the
-    pack kernels are part of the captured sequence."""
-    net._derived_ver = None
-
-
-def _d_active_conv(D, depth):
-    return [m for m in engine.d_active_params(D, depth, 1.0) if m.kind == 'conv']
-
-
-def _g_active_conv(G, depth):
-    ls = [G.block0.c1, G.block0.c2]
-    for i in range(depth):
-        ls += [G.blocks[i].c1, G.blocks[i].c2]
-    return ls
-
-
 def d_step(D, G, real, latents, mix, lam, eps, target):
     """Graphed ``d_loss_forward`` + ``d_loss_backward``.  Returns (d_cost, d_real_loss, d_fake_loss)."""
     key = ('D', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(D.depth), tuple(real.shape), tuple(latents.shape), float(lam), float(eps), float(target))
@@ -68,16 +51,17 @@ def d_step(D, G, real, latents, mix, lam, eps, target):
             g.warm += 1
             return body()
         torch.cuda.synchronize()
-        _force_repack(D, _d_active_conv(D, int(D.depth)))
-        _force_repack(G, _g_active_conv(G, int(G.depth)))     # the captured body runs G(z) on G's derived (Winograd) weights
+        # the derived weights must be re-packed on EVERY replay: stale now, so that the pack kernels are part of the captured sequence
+        D._rt.reset_derived()
+        G._rt.reset_derived()                    # (the captured body runs G(z) on G's derived (Winograd) weights)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             g.static_out = body()
         g.graph = graph
         # the three-pass forward's activations live in the network's single-slot arena (engine._three_pass_buffers), allocated during the
         # eager warm-up, i.e. OUTSIDE the graph's private pool: the graph bakes their addresses, so it keeps them alive -- a D step of
-        # another batch shape at this depth replaces D._d_fwd_buffers, and a replay of this graph must not touch freed memory
-        g.keep = D.__dict__.get('_d_fwd_buffers')
+        # another batch shape at this depth replaces D._rt.d_fwd_buffers, and a replay of this graph must not touch freed memory
+        g.keep = D._rt.d_fwd_buffers
     g.graph.replay()
     engine._assign_grads(D, engine.d_active_params(D, int(D.depth), 1.0), linear=True)
     # the static outputs are overwritten by the next replay: hand out copies (a plugin may keep loss tensors)
@@ -101,8 +85,8 @@ def g_step(G, D, latents):
             g.warm += 1
             return body()[0]
         torch.cuda.synchronize()
-        _force_repack(D, _d_active_conv(D, int(D.depth)))
-        _force_repack(G, _g_active_conv(G, int(G.depth)))
+        D._rt.reset_derived()                    # (as in d_step)
+        G._rt.reset_derived()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             g.static_out = body()

@@ -21,6 +21,8 @@ from torch import nn
 
 import weakref
 
+from .runtime import LEGACY_KEYS, NetRuntime
+
 MBSTD_PAD = 16        # the 513-channel input of DLastBlock.c1 is stored with 512+16 channels
 _FLAT_REGISTRY = {}   # flat parameter buffer base pointer -> weakref(network)  (lets FusedAdam find its net)
 
@@ -72,6 +74,8 @@ class PGConv2d(nn.Module):
             raise ValueError('channel counts must be multiples of 4 for the MFMA conv kernels '
                              '(got %d -> %d)' % (ch_in, ch_out))
         self._gw = self._gb = self._wt = None
+        self._wt_wanted = self._wino_wanted = False      # engine._wt / _wino: the refresh of the derived weights includes this layer
+        self._pending_wgrad = None                       # engine._wgrad: a deferred tangent contribution waiting for its carrier
 
     # ---- layout conversion (host-side utilities, not on the hot path) ----
     def _pack(self, w_ref):
@@ -106,11 +110,16 @@ class PGConv2d(nn.Module):
     def __getstate__(self):
         d = self.__dict__.copy()
         d['_gw'] = d['_gb'] = d['_wt'] = None
-        d['_wt_ver'] = None
         d['_wu'] = d['_wtu'] = None
         d['_net'] = None
+        d['_wt_wanted'] = d['_wino_wanted'] = False      # (the first request after a reload sets them again, as on a fresh network)
         d['_pending_wgrad'] = None
         return d
+
+    def __setstate__(self, state):
+        super(PGConv2d, self).__setstate__(state)
+        self.__dict__.pop('_wt_ver', None)               # (snapshots of earlier versions: a dead key; the flags were set on demand, or saved set)
+        self._wt_wanted = self._wino_wanted = False
 
 
 class GFirstBlock(nn.Module):
@@ -169,6 +178,7 @@ class _GradViews(object):
 
     def __init__(self, gw, gb):
         self._gw, self._gb = gw, gb
+        self._pending_wgrad = None               # (never has one: engine._grads_ready asks every layer)
 
 
 class _FlatParamsMixin(object):
@@ -212,10 +222,10 @@ class _FlatParamsMixin(object):
             m._gw = m._gb = m._wt = None
             m._wu = m._wtu = None
         self._flat_wu = self._flat_wtu = self._flat_wuu = None
-        self._derived_ver = None
+        if '_rt' not in self.__dict__:
+            self._rt = NetRuntime()                        # (schedule state of engine / plans / trainer: runtime.py)
+        self._rt.reset_derived()
         self._param_version = getattr(self, '_param_version', 0) + 1
-        for m in self._layers():
-            m._wt_ver = None
         _FLAT_REGISTRY[flat.data_ptr()] = weakref.ref(self)
 
     def _apply(self, fn, recurse=True):
@@ -263,7 +273,7 @@ class _FlatParamsMixin(object):
             m._wtu = self._flat_wtu[off:off + n].view(16, ci, co)
             self._wino_layers.append((m, byptr[id(m.conv.weight)], off))
             off += n
-        self._derived_ver = None
+        self._rt.reset_derived()
         if hasattr(self, 'linear'):
             ow, ob = byptr[id(self.linear.weight)], byptr[id(self.linear.bias)]
             self._lin_gw = self._flat_grad[ow:ow + self.linear.weight.numel()].view(self.linear.weight.shape)
@@ -295,32 +305,17 @@ class _FlatParamsMixin(object):
 
     def __getstate__(self):
         d = self.__dict__.copy()
-        d['_flat_grad'] = None
-        d['_flat_wt'] = None
+        d['_flat_grad'] = d['_flat_wt'] = None
         d['_flat_wu'] = d['_flat_wtu'] = d['_flat_wuu'] = None
         d['_wino_layers'] = None
-        d['_derived_ver'] = None
-        d['_pending'] = None
-        d['_skip_join'] = False
         d['_lin_gw'] = d['_lin_gb'] = d['_lin_layer'] = None
-        d['_grad_hook'] = d['_grad_exchange'] = None
-        d['_global_stddev'] = None               # (a process-group handle: a reloaded network starts in the local-shard mode)
-        d['_gs_checked'] = None
-        d['_plan_unjoined'] = False
-        d['_d_fwd_buffers'] = None               # (device buffers of the three-pass D forward: rebuilt on demand)
-        d['_early_fwd'] = d['_early_g_request'] = None     # (a generator pass left for the G step / the request for one: engine.EarlyG)
-        d['_plist'] = None
-        d['_layer_list'] = None
-        d['_derived_bwd_ev'] = None
-        d['_derived_bwd_waited'] = set()
-        d['_derived_ev'] = d['_pending_ev'] = None
-        d['_defer_active'] = False
-        d['_derived_waited'] = set()
-        d['_bwd_wanted'] = False
+        d['_plist'] = d['_layer_list'] = None
+        d.pop('_rt', None)                       # (events, process-group handles, device buffers: a reloaded network starts with a fresh one)
         return d
 
     def __setstate__(self, state):
-        super(_FlatParamsMixin, self).__setstate__(state)
+        super(_FlatParamsMixin, self).__setstate__({k: v for k, v in state.items() if k not in LEGACY_KEYS})
+        self._rt = NetRuntime()
         if getattr(self, '_flat_param', None) is not None:
             _FLAT_REGISTRY[self._flat_param.data_ptr()] = weakref.ref(self)
 

@@ -12,7 +12,7 @@ only: rendezvous, the broadcast of the communicator id and of the initial weight
 world-size-2 gloo tests — the reduction itself goes through ``torch.distributed`` as well.)
 
 Overlap: the backward sweeps of ``engine`` report every block whose weight gradients have been enqueued
-(``net._grad_hook``); ``GradExchange`` collects them into buckets of ~``BUCKET_BYTES`` and issues each bucket's
+(``net._rt.grad_hook``); ``GradExchange`` collects them into buckets of ~``BUCKET_BYTES`` and issues each bucket's
 all-reduce on the exchange stream behind an event of the weight-gradient stream, so the 512-channel blocks of D (85 % of
 the bytes, finished in the first quarter of the sweep) travel under the rest of the backward pass and only the last
 bucket is exposed.  xGMI is point-to-point (7 links per GPU): a few multi-MB messages keep the links busy, hence
@@ -194,7 +194,7 @@ class DataParallel(object):
         if net._flat_grad is None:
             raise RuntimeError('all_reduce_grads called before any backward pass')
         flat = net._flat_grad
-        ex = getattr(net, '_grad_exchange', None)
+        ex = net._rt.grad_exchange
         if ex is not None and ex.started:
             ex.finish()
         else:

@@ -140,10 +140,10 @@ def _replay(plan):
         elif kind == WAIT:
             e[2].wait_event(e[1])
         elif kind == PENDING:
-            ev = getattr(e[1], '_pending', None)
+            ev = e[1]._rt.pending
             if ev is not None:
                 e[2].wait_event(ev)
-                e[1]._pending = None
+                e[1]._rt.pending = None
         else:
             with torch.cuda.stream(e[2]):             # (no-op when e[2] is the current stream, which is the usual case)
                 engine._await_backward_copies(e[1])
@@ -167,7 +167,7 @@ def _prologue(*nets):
     for net in nets:
         net._sync_version()
         net._ensure_buffers()
-        if net._derived_ver != (net._param_version, int(net.depth)):
+        if net._rt.derived_ver != (net._param_version, int(net.depth)):
             engine._derived(net)
         engine.order_side_behind_derived(net)
 
@@ -175,7 +175,7 @@ def _prologue(*nets):
 def _dp_tag(net):
     """What a plan recorded under data parallelism depends on: the bucketed exchange the sweep feeds (``Trainer._open_exchange`` installs it
     BEFORE the loss call in plan mode) and whether its collectives are being left out (bench.py's exposed-exchange estimate)."""
-    ex = net.__dict__.get('_grad_exchange') if net.__dict__.get('_grad_hook') is not None else None
+    ex = net._rt.grad_exchange if net._rt.grad_hook is not None else None
     return (0, None) if ex is None else ((id(ex), bool(ex.dp.skip_exchange)), ex)
 
 
@@ -201,11 +201,9 @@ def d_step(D, G, real, latents, mix, lam, eps, target):
     _prologue(D, G)
     dp_tag, ex = _dp_tag(D)
     # the G step's generator pass rides in this step on the second stream (engine.request_early_g): its latents are a fourth static input
-    req = D.__dict__.get('_early_g_request')
+    req = D._rt.early_g_request
     if req is not None and engine.early_g_mode(req[0].depth) is None:
-        req = None
-    if req is None:
-        D.__dict__.pop('_early_g_request', None)
+        req = D._rt.early_g_request = None
     zg = engine._check_dev(req[1], 'latents') if req is not None else None
     key = ('D', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(D.depth), tuple(real.shape), tuple(latents.shape), float(lam), float(eps), float(target), dp_tag,
            (req[0]._flat_param.data_ptr(), tuple(zg.shape)) if req is not None else 0)
@@ -217,44 +215,44 @@ def d_step(D, G, real, latents, mix, lam, eps, target):
         _CACHE.move_to_end(key)
     if req is not None:
         g.static_in[3].copy_(zg)
-        D._early_g_request = (req[0], g.static_in[3])
+        D._rt.early_g_request = (req[0], g.static_in[3])
     for dst, src in zip(g.static_in, (real, latents, mix)):
         dst.copy_(src)
 
     def body():
         # The plan itself never joins the weight-gradient stream: whether the caller's next launch needs the join is not known
         # here.  ``backward()`` of the returned loss does it (wgan_gp_loss._replayed_backward) unless the caller has set
-        # ``D._skip_join`` by then (Trainer: the whole update follows on the weight-gradient stream, in order behind them).
-        caller = getattr(D, '_skip_join', False)
-        D._skip_join = True
+        # ``D._rt.skip_join`` by then (Trainer: the whole update follows on the weight-gradient stream, in order behind them).
+        caller = D._rt.skip_join
+        D._rt.skip_join = True
         try:
             c, rl, fl, state = engine.d_loss_forward(D, G, g.static_in[0], g.static_in[1], g.static_in[2], lam, eps, target)
             engine.d_loss_backward(state)
         finally:
-            D._skip_join = caller
+            D._rt.skip_join = caller
         return c, rl, fl
-    if D.__dict__.get('_plan_unjoined', False):     # a step whose loss never had backward() called: its weight gradients may still be in flight
+    if D._rt.plan_unjoined:                         # a step whose loss never had backward() called: its weight gradients may still be in flight
         engine._join_side()
-    D._plan_unjoined = True
+    D._rt.plan_unjoined = True
 
     def early_g_handover(eg):
         # what the body (or the replay) left for the G step is keyed to the CALLER's latents tensor, not to the static copy
-        D.__dict__.pop('_early_g_request', None)         # (a body without a second-stream pass does not take the request)
+        D._rt.early_g_request = None                     # (a body without a second-stream pass does not take the request)
         if req is not None and eg is not None:
             eg.latents = zg
             eg.stamp = (req[0]._param_version, int(req[0].depth), float(req[0].alpha))
-            req[0]._early_fwd = eg
+            req[0]._rt.early_fwd = eg
     if g.entries is None:
         if g.warm < 2:                       # eager warm-up (kernel attributes, first-request derived copies, allocator pools)
             g.warm += 1
             out = body()
-            early_g_handover(req[0].__dict__.get('_early_fwd') if req is not None else None)
+            early_g_handover(req[0]._rt.early_fwd if req is not None else None)
             return out
         before = _dp_begin(ex)
         with _Recorder(g):
             g.static_out = body()
         _dp_recorded(g, ex, before)
-        g.early_g = req[0].__dict__.get('_early_fwd') if req is not None else None
+        g.early_g = req[0]._rt.early_fwd if req is not None else None
     else:
         _replay(g)
         _dp_replayed(g, ex)
@@ -276,9 +274,9 @@ def g_step(G, D, latents):
     dp_tag, ex = _dp_tag(G)
     # the generator pass may already be through (engine.EarlyG, left by the D step for exactly these latents): a plan of its own, whose
     # body starts from that pass's tensors -- stable addresses: the D step's plan rewrites them at every replay
-    eg = G.__dict__.get('_early_fwd')
+    eg = G._rt.early_fwd
     if eg is not None and not (eg.latents is latents and eg.stamp == (G._param_version, int(G.depth), float(G.alpha))):
-        eg = G.__dict__.pop('_early_fwd') and None
+        eg = G._rt.early_fwd = None
         engine.EARLY_G_STATS['dropped'] += 1
     key = ('G', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(G.depth), tuple(latents.shape), dp_tag, eg is not None)
     g = _CACHE.get(key)
@@ -294,9 +292,9 @@ def g_step(G, D, latents):
     if eg is not None:
         eg.latents = g.static_in[0]          # (what the body hands to g_loss_forward; identity is all take_early_g compares)
         if g.entries is not None:            # replay: the wait on the pass's event is one of the recorded entries
-            G.__dict__.pop('_early_fwd', None)
+            G._rt.early_fwd = None
             engine.EARLY_G_STATS['used'] += 1
-    if getattr(D, '_pending', None) is None:  # (a deferred D update refreshes D's derived weights itself, on the second stream)
+    if D._rt.pending is None:                 # (a deferred D update refreshes D's derived weights itself, on the second stream)
         _prologue(D)
     _prologue(G)
 

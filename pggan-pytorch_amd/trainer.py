@@ -19,7 +19,7 @@ MI355X data-parallel additions (optional, default off):
 import heapq
 import os
 
-from . import engine
+from . import engine, runtime
 
 PLUGIN_UNITS = ('iteration', 'epoch', 's', 'end')
 
@@ -169,7 +169,7 @@ class Trainer(object):
             raise ValueError('global_stddev=True needs parallel= (the exact-global minibatch stddev is a data-parallel mode)')
         if parallel is not None and hasattr(D, '_flat_param'):
             # minibatch stddev under data parallelism: local-shard statistics by default, exact-global on request
-            D._global_stddev = parallel if global_stddev else None
+            D._rt.global_stddev = parallel if global_stddev else None
         if parallel is not None:
             from . import wgan_gp_loss
             if getattr(parallel, 'comm', None) is None:
@@ -234,7 +234,7 @@ class Trainer(object):
         if ex is None:
             ex = self._exchanges[id(net)] = par.GradExchange(self.parallel, net)
         ex.begin(layers_fn(net, int(net.depth), float(net.alpha)))
-        net._grad_exchange, net._grad_hook = ex, ex.ready
+        net._rt.grad_exchange, net._rt.grad_hook = ex, ex.ready
 
     def _exchange(self, net):
         if self.parallel is not None:
@@ -279,6 +279,7 @@ class Trainer(object):
 
     def _train_iteration(self):
         world = 1 if self.parallel is None else self.parallel.world_size
+        d_rt, g_rt = runtime.of(self.D), runtime.of(self.G)      # (None for a foreign network: it takes no part in the schedules' state)
         latents = _to_device(self.random_latents_generator())                     # :86
         d_losses = (0, 0, 0)
         for rep in range(self.D_training_repeats):                                # :90
@@ -302,19 +303,18 @@ class Trainer(object):
                 if getattr(z_g, 'is_cuda', False):
                     engine.request_early_g(self.D, self.G, z_g)
             try:
-                d_losses = _as_tuple(self.D_loss(self.D, self.G, reals, latents)) # :95
-            except BaseException:
-                self.D._grad_hook = None
-                raise
-            finally:
-                self.D.__dict__.pop('_early_g_request', None)                     # (a D loss that never reached the engine's second-stream pass)
-            defer = last and self._can_overlap_d_update()
-            self.D._skip_join = defer                # the update runs on the second stream, behind the weight gradients
-            try:
+                try:
+                    d_losses = _as_tuple(self.D_loss(self.D, self.G, reals, latents))     # :95
+                finally:
+                    if d_rt is not None:
+                        d_rt.early_g_request = None  # (a D loss that never reached the engine's second-stream pass)
+                defer = last and self._can_overlap_d_update()
+                if d_rt is not None:
+                    d_rt.skip_join = defer           # the update runs on the second stream, behind the weight gradients
                 d_losses[0].backward()                                            # :98
-            finally:
-                self.D._skip_join = False
-                self.D._grad_hook = None
+            finally:                                 # (also when the loss or its backward raised)
+                if d_rt is not None:
+                    d_rt.skip_join, d_rt.grad_hook = False, None
             if defer:
                 # the tail of the last D update (all-reduce, Adam, derived weights) runs on the second stream under the
                 # generator forward that opens the G step; the main stream re-joins at its first use of D (engine.wait_pending)
@@ -328,14 +328,16 @@ class Trainer(object):
             g_losses = _as_tuple(self.G_loss(self.G, self.D, latents))            # :105-110
             g_losses[0].backward()                                                # :111
         finally:
-            self.G._grad_hook = None
+            if g_rt is not None:
+                g_rt.grad_hook = None
         self._exchange(self.G)
         self.optimizer_g.step()                                                   # :112
         if getattr(self.G, '_flat_param', None) is not None and self.G._flat_param.is_cuda:
             engine._derived(self.G)                  # (the next generator pass needs them first thing; never part of a replayed plan)
             engine.probe('G.update_end')
-        engine.wait_pending(self.D)                  # (a G_loss that never ran D: nothing may outlive the iteration)
-        if getattr(self.G, '__dict__', {}).pop('_early_fwd', None) is not None:   # (... nor a generator pass nobody took)
+        if d_rt is not None:
+            engine.wait_pending(self.D)              # (a G_loss that never ran D: nothing may outlive the iteration)
+        if g_rt is not None and g_rt.take('early_fwd') is not None:               # (... nor a generator pass nobody took)
             engine.EARLY_G_STATS['dropped'] += 1
         self.iterations += 1
         self.call_plugins('iteration', self.iterations, *(g_losses + d_losses))   # :115

@@ -56,7 +56,7 @@ def _replay_mode(net):
 
 def _exchange_instrumented(net):
     """bench.py times every collective with a fresh HIP event pair (``DataParallel.record_events``): those steps are issued eagerly."""
-    ex = net.__dict__.get('_grad_exchange') if net.__dict__.get('_grad_hook') is not None else None
+    ex = net._rt.grad_exchange if net._rt.grad_hook is not None else None
     return ex is not None and ex.dp.record_events
 
 
@@ -125,12 +125,12 @@ def _replayed_backward(net):
     """``backward()`` of a loss whose step was replayed (hipGraph or launch plan): the gradient launches are already enqueued.  A
     replayed plan leaves the weight-gradient stream un-joined; the join happens HERE, so that ``loss.backward(); optimizer.step()``
     keeps the contract of the eager path (engine.d_loss_backward: gradients complete for whatever the caller does next on this
-    stream) -- unless the caller has set ``net._skip_join`` (Trainer: the update follows on the weight-gradient stream itself).
+    stream) -- unless the caller has set ``net._rt.skip_join`` (Trainer: the update follows on the weight-gradient stream itself).
     A ``gradient`` other than 1 rescales the flat gradient buffer afterwards, as the eager path does."""
     def fn(scale):
-        if not (getattr(net, '_skip_join', False) and scale == 1.0):
+        if not (net._rt.skip_join and scale == 1.0):
             engine._join_side()
-        net._plan_unjoined = False           # joined, or the caller took over (its update is ordered behind the weight-gradient stream)
+        net._rt.plan_unjoined = False        # joined, or the caller took over (its update is ordered behind the weight-gradient stream)
         if scale != 1.0:
             from . import ops
             ops.axpby_mask(net._flat_grad, a=scale, out=net._flat_grad)
@@ -153,7 +153,7 @@ def wgan_gp_D_loss(D, G, real_images_in, fake_latents_in,
     else:                                                                # :15-17 (device RNG)
         mix = _draw_mixing_factors(n, real_images_in.device)
     mode = _replay_mode(D) if (float(D.alpha) >= 1.0 and real_images_in.is_cuda and hasattr(D, '_flat_param')
-                               and D.__dict__.get('_global_stddev') is None) else None      # (exact-global stddev: collectives inside the step -> eager)
+                               and D._rt.global_stddev is None) else None      # (exact-global stddev: collectives inside the step -> eager)
     if mode == 'plan' and _exchange_instrumented(D):
         mode = None
     if mode is not None:
@@ -178,7 +178,7 @@ def wgan_gp_G_loss(G, D, fake_latents_in):
     """reference wgan_gp_loss.py:68-74."""
     G.zero_grad()                                                        # :69
     mode = _replay_mode(G) if (float(G.alpha) >= 1.0 and fake_latents_in.is_cuda and hasattr(G, '_flat_param')
-                               and D.__dict__.get('_global_stddev') is None) else None
+                               and D._rt.global_stddev is None) else None
     if mode == 'plan' and _exchange_instrumented(G):
         mode = None
     if mode is not None:

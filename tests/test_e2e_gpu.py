@@ -758,7 +758,7 @@ def test_early_g_forward_is_the_same_pass(mode, deterministic_forward, monkeypat
         assert miss[2] == base[2] and _l2(miss[3], base[3].cpu()) < 2e-5
     else:
         assert abs(miss[2] - base[2]) <= 2e-4 * max(1.0, abs(base[2])) and _l2(miss[3], base[3].cpu()) < 5e-3
-    assert G.__dict__.get('_early_fwd') is None and D.__dict__.get('_early_g_request') is None
+    assert G._rt.early_fwd is None and D._rt.early_g_request is None
 
 
 @pytest.mark.parametrize('plans_on,mode', [(False, 'side'), (True, 'side'), (False, 'batched'), (True, 'batched')])
@@ -853,6 +853,46 @@ def test_whole_module_pickle_roundtrip(tmp_path):
     assert not torch.equal(before, D2._flat_param)
     assert torch.isfinite(D2._flat_param).all()
     assert D2.blocks[-1].c2.conv.weight.data_ptr() >= D2._flat_param.data_ptr()      # still views of the flat buffer
+
+
+def test_trainer_iterations_stick_no_attribute_onto_a_module(monkeypatch):
+    """The schedule state lives in ``net._rt`` (runtime.NetRuntime) and in attributes every layer is built with: real ``Trainer``
+    iterations with launch plans -- deferred D update, early generator pass, three-pass D forward, eager warm-up, plan record and replay --
+    leave no new attribute on a layer and none but the host caches on a network."""
+    wl, eng = pg.wgan_gp_loss, pg.engine
+    monkeypatch.setattr(eng, 'EARLY_G_MIN_RES', 4)                # (the second-stream generator pass at a small test stage)
+    monkeypatch.setattr(eng, 'EARLY_G_MODE', 'side')
+    torch.manual_seed(21)
+    shape = (1, 3, 32, 32)
+    kw = dict(fmap_base=512, fmap_max=64)
+    G = pg.Generator(shape, latent_size=64, **kw).cuda()
+    D = pg.Discriminator(shape, **kw).cuda()
+    G.depth = D.depth = 3
+    opt_g, opt_d = pg.FusedAdam(G.parameters(), 0.001, betas=(0.0, 0.99)), pg.FusedAdam(D.parameters(), 0.001, betas=(0.0, 0.99))
+    ds = pg.utils.SyntheticDataset(32, 3, seed=5)
+    ds.model_depth = 3
+    tr = pg.Trainer(D, G, pg.wgan_gp_D_loss, pg.wgan_gp_G_loss, opt_d, opt_g, ds, ds.loader(8), pg.utils.device_latents(8, 64, seed=3))
+    for net in (G, D):
+        net._ensure_buffers()
+    keys = {id(m): set(vars(m)) for net in (G, D) for m in [net] + net._layers()}
+    wl.enable_graphs('auto')
+    pg.plans.clear()
+    pg.plans.STATS.update(recorded=0, replayed=0)
+    s0 = dict(eng.EARLY_G_STATS)
+    try:
+        for it in range(4):                                       # two eager warm-up iterations, one recorded, one replayed
+            tr.train()
+        torch.cuda.synchronize()
+        assert pg.plans.STATS['recorded'] >= 2 and pg.plans.STATS['replayed'] >= 2, pg.plans.STATS
+        assert eng.EARLY_G_STATS['used'] - s0['used'] == 4 and D._rt.d_fwd_buffers is not None and D._rt.pending is None
+        for net in (G, D):
+            new = set(vars(net)) - keys[id(net)]
+            assert new <= {'_plist', '_layer_list', '_torch_versions_seen'}, sorted(new)
+            for m in net._layers():
+                assert set(vars(m)) == keys[id(m)], sorted(set(vars(m)) - keys[id(m)])
+    finally:
+        wl.enable_graphs(False)
+        pg.plans.clear()
 
 
 def test_non_default_flags_fixture_gpu():
@@ -1084,7 +1124,7 @@ def test_deferred_d_update_matches_inline(monkeypatch, deterministic_forward):
         trb.train()
         assert n_def == it + 1 and len(taken) == n_def          # deferred in A, inline in B
         torch.cuda.synchronize()
-        assert getattr(tra.D, '_pending', None) is None
+        assert tra.D._rt.pending is None
         # D's gradients: computed at identical weights -> equal up to the order of the atomic weight-gradient commits, tensor by
         # tensor (a dropped or re-ordered contribution of ONE small layer shows here).  G's are computed through D AFTER its
         # update, where a sign-like Adam has already turned that noise into +-lr differences of near-zero elements: looser.

@@ -311,9 +311,81 @@ def test_process_group_handle_is_not_pickled():
         def __reduce__(self):
             raise RuntimeError('the process-group handle must not be pickled')
     D = pg.Discriminator((1, 3, 16, 16), fmap_base=64, fmap_max=16)
-    D._global_stddev = Handle()
+    D._rt.global_stddev = Handle()
     buf = io.BytesIO()
     torch.save(D, buf)
     buf.seek(0)
     D2 = torch.load(buf, weights_only=False)
-    assert D2.__dict__.get('_global_stddev') is None and isinstance(D._global_stddev, Handle)
+    assert D2._rt.global_stddev is None and '_global_stddev' not in vars(D2) and isinstance(D._rt.global_stddev, Handle)
+
+
+SCHEDULE_KEYS = ('_derived_ver', '_derived_live', '_derived_ev', '_derived_waited', '_derived_bwd_ev', '_derived_bwd_waited', '_bwd_wanted',
+                 '_defer_active', '_pending_ev', '_pending', '_skip_join', '_plan_unjoined', '_grad_hook', '_grad_exchange',
+                 '_global_stddev', '_gs_checked', '_early_g_request', '_early_fwd', '_d_fwd_buffers')       # where the schedule state lived before runtime.NetRuntime
+HOST_CACHES = {'_plist', '_layer_list', '_torch_versions_seen'}      # the only attributes a network may gain while it runs
+
+
+def _tiny32_after_steps():
+    meta, data = load_fixture('tiny32')
+    G, D = build_nets(meta)
+    cfg = meta['cfg']
+    for net in (G, D):
+        net._ensure_buffers()
+    keys = {id(m): set(vars(m)) for net in (G, D) for m in [net] + net._layers()}
+    for alpha in (1.0, 0.5):
+        G.depth = D.depth = 2
+        G.alpha = D.alpha = alpha
+        real, z_d, z_g, mix = synthetic(3, 4, cfg['num_channels'], 16, cfg['latent_size'])
+        pg.wgan_gp_loss.set_mixing_factors(mix)
+        pg.wgan_gp_D_loss(D, G, real, z_d)[0].backward()
+        pg.wgan_gp_G_loss(G, D, z_g).backward()
+    return G, D, keys
+
+
+def test_no_attribute_is_stuck_onto_a_module_at_run_time(emu):
+    """The step schedules keep their state in ``net._rt`` (runtime.NetRuntime) and in three attributes every PGConv2d is built with: a D
+    step and a G step (fully grown and fading in) leave no new attribute on a layer, and none but the host caches on a network."""
+    G, D, keys = _tiny32_after_steps()
+    for net in (G, D):
+        assert set(vars(net)) - keys[id(net)] <= HOST_CACHES, sorted(set(vars(net)) - keys[id(net)])
+        for m in net._layers():
+            assert set(vars(m)) == keys[id(m)], sorted(set(vars(m)) - keys[id(m)])
+
+
+def test_runtime_object_is_closed_and_not_pickled(emu):
+    import io
+    G, D, _ = _tiny32_after_steps()
+    fresh = pg.runtime.NetRuntime()
+    for net in (G, D):
+        with pytest.raises(AttributeError):
+            net._rt.derived_version = None                 # (an undeclared field)
+        assert net._rt.derived_ver is not None and net._rt.bwd_wanted          # the steps did leave state behind
+        buf = io.BytesIO()
+        torch.save(net, buf)
+        buf.seek(0)
+        net2 = torch.load(buf, weights_only=False)
+        for f in fresh.__slots__:
+            assert getattr(net2._rt, f) == getattr(fresh, f), f
+        assert net._rt.derived_ver is not None             # (the original keeps its own)
+        for m in net2._layers():
+            assert m._wt_wanted is False and m._wino_wanted is False and m._pending_wgrad is None
+    assert any(m._wt_wanted for m in D._layers())
+
+
+def test_snapshot_with_loose_schedule_attributes_loads():
+    """A whole-module snapshot of an earlier version carries the schedule state as loose attributes (reset to None / False / empty when it
+    was written): they are dropped on load."""
+    D = pg.Discriminator((1, 3, 16, 16), fmap_base=64, fmap_max=16)
+    state = D.__getstate__()
+    assert '_rt' not in state and not set(SCHEDULE_KEYS) & set(state)
+    for k in SCHEDULE_KEYS:
+        state[k] = set() if k.endswith('_waited') else False if k in ('_skip_join', '_plan_unjoined', '_defer_active', '_bwd_wanted') else None
+    D2 = pg.Discriminator.__new__(pg.Discriminator)
+    D2.__setstate__(state)
+    assert not set(SCHEDULE_KEYS) & set(vars(D2)) and isinstance(D2._rt, pg.runtime.NetRuntime)
+    lay = D.blocks[0].c1
+    lstate = dict(lay.__getstate__(), _wt_ver=None)
+    del lstate['_wt_wanted']                               # (set on the first request only; '_wt_ver' was written and never read)
+    lay2 = type(lay).__new__(type(lay))
+    lay2.__setstate__(lstate)
+    assert '_wt_ver' not in vars(lay2) and lay2._wt_wanted is False and lay2._wino_wanted is False and lay2._pending_wgrad is None

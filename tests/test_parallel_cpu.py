@@ -77,7 +77,7 @@ def _worker(rank, world, port, out_path, res, bucket_bytes):
     orig_all_reduce = dp.all_reduce_grads
 
     def recording_all_reduce(net, average=False):
-        ex = getattr(net, '_grad_exchange', None)
+        ex = net._rt.grad_exchange
         assert ex is not None and ex.started               # the Trainer opened a bucketed exchange for this sweep
         before = dp.stats['bytes']
         r = orig_all_reduce(net, average=average)
@@ -323,7 +323,7 @@ def _global_stddev_worker(rank, world, port, out_path, depth, alpha):
         return pg.wgan_gp_D_loss(Dm, Gm, r_, z_)
     tr = pg.Trainer(D, G, d_loss, pg.wgan_gp_G_loss, opt_d, opt_g, DS(), loader(), lambda: state['z'].pop(0) if state['z'] else z_g[sl],
                     parallel=dp, global_stddev=True)
-    assert D._global_stddev is dp
+    assert D._rt.global_stddev is dp
     got = {}
     orig = dp.all_reduce_grads
 
