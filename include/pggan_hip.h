@@ -11,7 +11,9 @@
  *     with pg_workspace_bytes and it is handed over per (device, stream) with pg_set_workspace;
  *   - process-wide state, all of it: (1) the immutable table of RCCL entry points resolved on first use of the pg_comm_* /
  *     pg_allreduce_* calls; (2) the mutex-guarded registry of caller-owned scratch buffers that pg_set_workspace fills -- the one
- *     piece of MUTABLE global state: a launch on a stream reads its entry, nothing else ever writes it.  Everything else is
+ *     piece of MUTABLE global state: a launch on a stream reads its entry, nothing else ever writes it; (3) the number of resident
+ *     workgroups of each row-streaming Winograd kernel per device (csrc/conv_wino_strip.hip, launch_ws), queried on the first launch of
+ *     that kernel on that device and constant afterwards.  The library reads no environment variable.  Everything else is
  *     re-entrant and callable from any thread (the thread-local tuning / attribution aids used by bench.py and tools/ are
  *     declared separately in pggan_hip_debug.h);
  *   - "feature" tensors are NHWC  [N][H][W][C]  with C % 4 == 0 and 16-byte aligned bases;
@@ -135,15 +137,7 @@ int pg_conv2d_wgrad_unpooled_nhwc(const float* x, const float* g, const unsigned
                                   float* dw, float* db, int N, int Hin, int Win, int Cin, int Cout,
                                   float scale, pg_stream_t stream);
 
-/* A DBlock's first conv with the block's fromRGB layer evaluated in its input gather (fromRGB = PGConv2d 1x1 + LeakyReLU,
- * /root/reference/network.py:145, in front of the block's c1, network.py:33-36 / :151; the call order D.forward network.py:227-228):
- *   x0[n][h][w][co] = lrelu(rgb_scale * sum_c rgb_w[co][c] * img[n][c][h][w] + rgb_b[co], rgb_slope)      (never materialised)
- *   y = lrelu(scale * conv3x3(x0, w, pad 1) + bias, slope)
- * img [N][C][H][W] fp32, rgb_w [Cmid][C], w [3][3][Cout][Cmid], y [N][H][W][Cout]; x_signs / y_signs (optional): the sign bytes
- * [N][H][W][C/4] of x0 / y (what the masked backward-data forms and pg_fromrgb_bwd_* read).  For forward passes that are not
- * followed by this conv's weight gradient (which needs x0 in fp32): the G step's pass through D.  Bit-identical to pg_fromrgb_fwd
- * followed by pg_conv2d_nhwc.  Implemented for Cmid = Cout = 8, C <= 3, W % 64 == 0, H % 16 == 0 (the 1024^2 stage); PG_E_UNSUP otherwise. */
-/* The generator's last conv with the block's toRGB layer in its epilogue (PGConv2d + PixelNorm /root/reference/network.py:33-41,
+/* The generator's last conv with the block's toRGB layer in its epilogue (PGConv2d + PixelNorm network.py:33-41,
  * toRGB network.py:49, applied at network.py:138 with alpha = 1):
  *   y = pixelnorm(lrelu(scale * conv3x3(x, w, pad 1) + bias, slope)), r[pixel] = the normalisation factor        (as pg_conv2d_pixelnorm_nhwc)
  *   img[n][c][h][w] = t_scale * sum_co t_w[c][co] * y[n][h][w][co] + t_b[c]                                     (as pg_torgb_fwd)
@@ -153,7 +147,7 @@ int pg_conv2d_pixelnorm_torgb_nhwc(const float* x, const float* w, const float* 
                                    int N, int C, int H, int W, int Cin, int Cout, float scale, float slope, float eps,
                                    pg_stream_t stream);
 
-/* The entry block's backward-data conv with fromRGB's backward-data in its epilogue (the adjoint of /root/reference/network.py:228
+/* The entry block's backward-data conv with fromRGB's backward-data in its epilogue (the adjoint of network.py:228
  * `h = self.blocks[...](self.blocks[...].fromRGB(x))` down to the image, autograd in the reference: wgan_gp_loss.py:25-28, trainer.py:111):
  *   gf[n][h][w][ci] = scale * conv3x3(gz, wt, pad 1) * (bit ci of mask_bytes[n][h][w] ? 1 : mask_slope)     (wt: the flipped / transposed weights of
  *   pg_pack_dgrad_weights; written to y unless y == NULL)
@@ -166,6 +160,14 @@ int pg_conv2d_masked_fromrgb_bwd_nhwc(const float* gz, const float* wt, const un
                                       const float* img, float* rgb_dw, float* rgb_db,
                                       int N, int C, int H, int W, int Cin, int Cout, float scale, pg_stream_t stream);
 
+/* A DBlock's first conv with the block's fromRGB layer evaluated in its input gather (fromRGB = PGConv2d 1x1 + LeakyReLU,
+ * network.py:145, in front of the block's c1, network.py:33-36 / :151; the call order D.forward network.py:227-228):
+ *   x0[n][h][w][co] = lrelu(rgb_scale * sum_c rgb_w[co][c] * img[n][c][h][w] + rgb_b[co], rgb_slope)      (never materialised)
+ *   y = lrelu(scale * conv3x3(x0, w, pad 1) + bias, slope)
+ * img [N][C][H][W] fp32, rgb_w [Cmid][C], w [3][3][Cout][Cmid], y [N][H][W][Cout]; x_signs / y_signs (optional): the sign bytes
+ * [N][H][W][C/4] of x0 / y (what the masked backward-data forms and pg_fromrgb_bwd_* read).  For forward passes that are not
+ * followed by this conv's weight gradient (which needs x0 in fp32): the G step's pass through D.  Bit-identical to pg_fromrgb_fwd
+ * followed by pg_conv2d_nhwc.  Implemented for Cmid = Cout = 8, C <= 3, W % 64 == 0, H % 16 == 0 (the 1024^2 stage); PG_E_UNSUP otherwise. */
 int pg_conv2d_fromrgb_nhwc(const float* img, const float* rgb_w, const float* rgb_b, float rgb_scale, float rgb_slope,
                            unsigned char* x_signs, const float* w, const float* bias, float* y, unsigned char* y_signs,
                            int N, int C, int H, int W, int Cmid, int Cout, float scale, float slope, pg_stream_t stream);

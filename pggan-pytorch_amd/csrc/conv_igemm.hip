@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pggan_hip.h"
+#include "pggan_hip_debug.h"
 #include "bufload.h"
 #include "convp.h"
 
@@ -30,7 +31,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 thread_local char g_last_kernel[96] = "";     // symbol of the last conv kernel launched by this thread
-thread_local int g_tune[4] = {-1, -1, -1, -1}; // tuning overrides (pg_debug_set_tuning): [0] conv tile, [1] wgrad config, [2] conv split-K, [3] 1: generic path for the 4x4 boundary layers, 2: generic path for the 8/16-cout layers, 3: unfused pooling, 10: unfused unpooling, 11 / 12: unfused PixelNorm forward / adjoint, 20: tile kernels instead of the row-streaming ones, 21: 4x4 -> 1x1 layer on one workgroup per cout block
+thread_local int g_tune[4] = {-1, -1, -1, -1}; // pg_debug_set_tuning overrides, indexed by pg_tune_key (keys and values: pggan_hip_debug.h)
 
 template <typename K>
 inline int set_smem(K kern, size_t smem)
@@ -1109,7 +1110,7 @@ int launch_thin(ConvP& p, hipStream_t s)
 
 int dispatch_thin(ConvP& p, hipStream_t s)
 {
-    if (g_tune[3] != 20) {                        // row-streaming kernel (conv_strip.hip) where the shape allows; 20: tile kernel (A/B)
+    if (g_tune[PG_TUNE_PATH] != PG_PATH_TILE_NOT_STRIP) {        // row-streaming kernel (conv_strip.hip) where the shape allows
         const int rc = pgk::launch_conv_strip(p, s, g_last_kernel, sizeof(g_last_kernel));
         if (rc != PG_E_UNSUP) return rc;
     }
@@ -1119,7 +1120,13 @@ int dispatch_thin(ConvP& p, hipStream_t s)
     return PG_E_UNSUP;
 }
 
-inline bool k4_dense_ok(int Cin, int Cout) { return (Cin & 15) == 0 && (Cout & 15) == 0; }
+// the two 4x4 boundary layers with their own kernels: 1x1 -> 4x4 (pad 3) and 4x4 -> 1x1 (pad 0), whole 16-channel blocks
+template <typename P>
+inline bool k4_layer(const P& p, int KS)
+{
+    return KS == 4 && !p.ups && (p.Cin & 15) == 0 && (p.Cout & 15) == 0 &&
+           ((p.pad == 3 && p.Hin == 1 && p.Win == 1) || (p.pad == 0 && p.Hin == 4 && p.Win == 4));
+}
 
 int launch_k4_conv(ConvP& p, hipStream_t s)
 {
@@ -1136,7 +1143,7 @@ int launch_k4_conv(ConvP& p, hipStream_t s)
         dim3 grid(p.Cout >> 4, (p.N + 16 * nt - 1) / (16 * nt));
         pgk::Workspace ws{};
         const size_t nblk = (size_t)grid.x * grid.y;
-        if (g_tune[3] != 21 && nblk <= 256 && nblk <= pgk::WS_TICKETS && pgk::find_workspace(s, ws) &&
+        if (g_tune[PG_TUNE_PATH] != PG_PATH_K4_ONE_WORKGROUP && nblk <= 256 && nblk <= pgk::WS_TICKETS && pgk::find_workspace(s, ws) &&
             pgk::WS_HEAD + nblk * 16 * nt * 1024 <= ws.bytes) {          // few cout blocks: one workgroup per (block, input pixel)
             dim3 sgrid(grid.x * 16, grid.y);
             snprintf(g_last_kernel, sizeof(g_last_kernel), "conv_k4_reduce_split_kernel<%d>", nt);
@@ -1223,8 +1230,7 @@ __global__ void pack_dgrad_batched_kernel(const float* __restrict__ wbase, float
     }
 }
 
-inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+using pgk::ilog2; using pgk::is_pow2;
 
 struct TileGeom { int lgTW, lgTH, TN, tilesW, tilesH, ntiles; };
 
@@ -1264,8 +1270,8 @@ int launch_conv(ConvP& p, hipStream_t s)
     const int nblocks = g.ntiles * ncob;
     const int nchunks = p.Cin / (4 * VEC);
     int ksplit = 1;
-    if (g_tune[2] > 0) {
-        ksplit = g_tune[2] > nchunks ? nchunks : g_tune[2];
+    if (g_tune[PG_TUNE_SPLITK] > 0) {
+        ksplit = g_tune[PG_TUNE_SPLITK] > nchunks ? nchunks : g_tune[PG_TUNE_SPLITK];
         const int cper = (nchunks + ksplit - 1) / ksplit;
         ksplit = (nchunks + cper - 1) / cper;
     } else if (nblocks < 192 && nchunks >= 4) {           // too few workgroups for 256 CUs: slice K
@@ -1500,8 +1506,8 @@ int dispatch_conv(ConvP& p, hipStream_t s)
     } else {
         if constexpr (VEC == 4) {
             const long long Mpx = (long long)p.N * p.Hout * p.Wout;
-            if (!p.ups && !p.ypool && !p.yup && !p.pn_r && !p.pnb_y && p.Cin >= 128 && g_tune[0] < 0 && g_tune[3] != 8 &&
-                ((g_tune[3] == 9 && Mpx <= 2304) || (g_tune[3] != 9 && Mpx <= 576))) {
+            if (!p.ups && !p.ypool && !p.yup && !p.pn_r && !p.pnb_y && p.Cin >= 128 && g_tune[PG_TUNE_CONV_TILE] < 0 &&
+                g_tune[PG_TUNE_PATH] != PG_PATH_NO_SMALLMAP_SPLIT && Mpx <= (g_tune[PG_TUNE_PATH] == PG_PATH_SMALLMAP_SPLIT_2304 ? 2304 : 576)) {
                 const int rc = Mpx <= 256 ? launch_ksplit<1>(p, s) : launch_ksplit<2>(p, s);
                 if (rc != PG_E_UNSUP) return rc;
             }
@@ -1550,7 +1556,7 @@ int dispatch_conv(ConvP& p, hipStream_t s)
             if (ks > 1) cost += 8000.0;
             if (cost < best) { best = cost; bi = i; }
         }
-        if (g_tune[0] >= 0) bi = g_tune[0];
+        if (g_tune[PG_TUNE_CONV_TILE] >= 0) bi = g_tune[PG_TUNE_CONV_TILE];
         switch (bi) {
             case 0: return launch_conv<KS, VEC, 1, 1, 4>(p, s);
             case 1: return launch_conv<KS, VEC, 2, 2, 4>(p, s);
@@ -1594,7 +1600,7 @@ int launch_wgrad(WgP& p, hipStream_t s)
     if (red > smem) smem = red;
     const int gy = (p.Cout + BCO - 1) / BCO, gz_ = (p.Cin + BCI - 1) / BCI;
     int chunks = (512 + gy * gz_ - 1) / (gy * gz_);        // ~512 workgroups: fills 256 CUs twice over while
-    if (g_tune[2] > 0) chunks = g_tune[2];                 // (tuning sweep)
+    if (g_tune[PG_TUNE_SPLITK] > 0) chunks = g_tune[PG_TUNE_SPLITK];                 // (tuning sweep)
     if (chunks > g.ntiles) chunks = g.ntiles;              // keeping the commit traffic (chunks x |dW|) small
     if (chunks < 1) chunks = 1;
     p.tiles_per_block = (g.ntiles + chunks - 1) / chunks;
@@ -1864,7 +1870,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_thin_kernel(WgP p)
 template <int BPX>
 int launch_wgrad_thin(WgP& p, hipStream_t s)
 {
-    if (g_tune[1] != 20) {                        // row-streaming kernel (conv_strip.hip) where the shape allows; 20: tile kernel (A/B)
+    if (g_tune[PG_TUNE_WGRAD] != PG_WGRAD_TILE_NOT_STRIP) {      // row-streaming kernel (conv_strip.hip) where the shape allows
         const int rc = pgk::launch_wgrad_strip(p, s, g_last_kernel, sizeof(g_last_kernel));
         if (rc != PG_E_UNSUP) return rc;
     }
@@ -1887,8 +1893,7 @@ int launch_wgrad_thin(WgP& p, hipStream_t s)
 #ifdef PG_WINO_TRACE
     p.trace = g_wgrad_trace;
 #endif
-    static const int fix_env = getenv("PG_WGRAD_THIN_FIX") ? atoi(getenv("PG_WGRAD_THIN_FIX")) : 1;
-    const bool fix = BPX == 64 && g.lgTW == 4 && g.lgTH == 2 && g.TN == 1 && fix_env;
+    const bool fix = BPX == 64 && g.lgTW == 4 && g.lgTH == 2 && g.TN == 1;
 #define THIN(CO_, CI_) { if (fix) { auto kern = conv_wgrad_thin_kernel<CO_, CI_, BPX, BPX == 64>; if (int rc = set_smem(kern, smem)) return rc; \
                              hipLaunchKernelGGL(kern, dim3(chunks), dim3(256), smem, s, p); } \
                          else { auto kern = conv_wgrad_thin_kernel<CO_, CI_, BPX, false>; if (int rc = set_smem(kern, smem)) return rc; \
@@ -1913,21 +1918,21 @@ int dispatch_wgrad(WgP& p, hipStream_t s)
         if (M <= 32) return launch_wgrad<KS, 1, 1, 2, 2, 16>(p, s);
         if constexpr (KS == 3) {
             // measured (tools/sweeps/sweep_wgrad_thin.py): block-MFMA wins on 32 -> 16 always, on 16 -> 32 below ~1.5 M pixels
-            if (g_tune[1] != 8 && ((p.Cout == 16 && p.Cin == 32) || (p.Cout == 32 && p.Cin == 16 && M < 1500000)))
+            if ((p.Cout == 16 && p.Cin == 32) || (p.Cout == 32 && p.Cin == 16 && M < 1500000))
                 return launch_wgrad_thin<64>(p, s);
         }
         if (p.Cout <= 16 && p.Cin <= 16) {
             if constexpr (KS == 3) {
                 // 8-channel sides: the 16x16x4 tile would be 50-75 % padding -> 4x4x1 block MFMA kernel
-                if (g_tune[1] != 8 && (p.Cout == 8 || p.Cin == 8) && (p.Cout == 8 || p.Cout == 16) && (p.Cin == 8 || p.Cin == 16))
+                if ((p.Cout == 8 || p.Cin == 8) && (p.Cout == 8 || p.Cout == 16) && (p.Cin == 8 || p.Cin == 16))
                     return launch_wgrad_thin<64>(p, s);
             }
             return launch_wgrad<KS, 1, 1, 1, 1, 128>(p, s);     // 16x16 block
         }
         if constexpr (KS == 3) {
-            switch (g_tune[1]) {                                                               // tuning sweep only
-                case 1: return launch_wgrad<KS, 2, 1, 1, 1, 128>(p, s);
-                case 3: return launch_wgrad<KS, 2, 1, 2, 1, 64>(p, s);
+            switch (g_tune[PG_TUNE_WGRAD]) {                                                   // tuning sweep only
+                case PG_WGRAD_32x16_128PX: return launch_wgrad<KS, 2, 1, 1, 1, 128>(p, s);
+                case PG_WGRAD_64x16_64PX: return launch_wgrad<KS, 2, 1, 2, 1, 64>(p, s);
                 default: break;
             }
         }
@@ -1935,7 +1940,7 @@ int dispatch_wgrad(WgP& p, hipStream_t s)
             // measured (tools/sweeps/sweep_wgrad.py): with >= ~4e8 MACs per tap the 64-cout block (two K-waves) wins on
             // >= 64 input channels and 128-pixel tiles win on the narrow layers; small launches keep 32x16 / 64 px
             const double macs = (double)M * p.Cout * p.Cin;
-            if (g_tune[1] < 0 && macs >= 4e8) {
+            if (g_tune[PG_TUNE_WGRAD] < 0 && macs >= 4e8) {
                 if (p.Cin >= 64) return launch_wgrad<KS, 2, 1, 2, 1, 64>(p, s);
                 return launch_wgrad<KS, 2, 1, 1, 1, 128>(p, s);
             }
@@ -1946,106 +1951,97 @@ int dispatch_wgrad(WgP& p, hipStream_t s)
 
 }  // namespace
 
-extern "C" int pg_avgpool2_fwd(const float* x, const float* other, float* y, int N, int H, int W, int C,
-                               float a, float b, pg_stream_t stream);
-
-extern "C" int pg_avgpool2_bwd(const float* gy, const float* mask, float* gx, int N, int H, int W, int C,
-                               float mul, float mask_slope, pg_stream_t stream);
-extern "C" int pg_pixelnorm_fwd(const float* x, float* y, float* r, int64_t P, int C, float eps, pg_stream_t stream);
-extern "C" int pg_pixelnorm_lrelu_bwd(const float* gy, const float* y, const float* r, float* gz,
-                                      int64_t P, int C, float slope, pg_stream_t stream);
-
-static int conv2d_impl(const float* x, const float* w, const float* bias, const float* mask, float* y,
-                       float* ypool, const float* pool_other, float pool_a, float pool_b, int pool_only,
-                       int N, int Hin, int Win, int Cin, int Cout, int KS, int pad, int ups,
-                       float scale, float slope, float mask_slope, pg_stream_t stream,
-                       float* yup = nullptr, const float* upmask = nullptr, float up_mul = 1.f,
-                       float* pn_r = nullptr, float pn_eps = 0.f, const float* pnb_y = nullptr, const float* pnb_r = nullptr)
+// Whatever the launch of a request could not fuse into its epilogue runs as a second pass over y (``pooled``: the launch pooled)
+static int second_pass(const ConvP& want, bool pooled, pg_stream_t stream)
 {
-    if (!x || !w || !y || N <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0) return PG_E_ARG;
-    if ((Cin & 3) || (Cout & 3)) return PG_E_ALIGN;
-    const int flags = ups;                                  // PG_FLAG_*: bit 0 = nearest x2 upsample of x
-    ups = flags & PG_FLAG_UPSAMPLE;
+    const int64_t P = (int64_t)want.N * want.Hout * want.Wout;
+    if (want.ypool && !pooled)
+        return pg_avgpool2_fwd(want.y, want.pool_other, want.ypool, want.N, want.Hout >> 1, want.Wout >> 1, want.Cout, want.pool_a, want.pool_b, stream);
+    if (want.yup) return pg_avgpool2_bwd(want.y, want.upmask, want.yup, want.N, want.Hout, want.Wout, want.Cout, want.up_mul, want.mask_slope, stream);
+    if (want.pn_r) return pg_pixelnorm_fwd(want.y, want.y, want.pn_r, P, want.Cout, want.pn_eps, stream);
+    if (want.pnb_y) return pg_pixelnorm_lrelu_bwd(want.y, want.pnb_y, want.pnb_r, want.y, P, want.Cout, want.mask_slope, stream);
+    return 0;
+}
+
+// 3x3 pad-1 layers on maps of whole 32 x 8 pixel tiles, for the block-MFMA kernels of the 8/16-cout layers (dispatch_thin);
+// ``channels``: the caller's condition on the channel counts
+static bool thin_shape(const ConvP& p, bool channels)
+{
+    return channels && p.KS == 3 && p.pad == 1 && (p.Wout & 31) == 0 && (p.Hout & 7) == 0 && g_tune[PG_TUNE_PATH] != PG_PATH_NO_THIN;
+}
+
+// The fields every conv entry point takes; the optional outputs are set by the entry point that has them
+static ConvP conv_request(const float* x, const float* w, const float* bias, const float* mask, float* y,
+                          int N, int Hin, int Win, int Cin, int Cout, int KS, int pad, float scale, float slope, float mask_slope)
+{
     ConvP p;
-    p.mask_bytes = (flags & PG_FLAG_MASK_BYTES) ? 1 : 0; p.y_bytes = (flags & PG_FLAG_Y_BYTES) ? 1 : 0;
-    p.ysigns = nullptr;
-    p.gbytes = nullptr; p.gmul = 1.f; p.gslope = 1.f;
-    if (flags & PG_FLAG_SIGNS_OUT) {                        // forward mode: the (otherwise unused) mask argument is the byte output
-        if (!mask || p.mask_bytes) return PG_E_ARG;
-        p.ysigns = reinterpret_cast<unsigned char*>(const_cast<float*>(mask));
-        mask = nullptr;
-    }
     p.x = x; p.w = w; p.bias = bias; p.mask = mask; p.y = y;
-    p.N = N; p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.Cout = Cout; p.KS = KS; p.pad = pad; p.ups = ups;
-    p.Hout = Hin + 2 * pad - KS + 1; p.Wout = Win + 2 * pad - KS + 1;
-    if (p.Hout <= 0 || p.Wout <= 0 || !is_pow2(p.Hout) || !is_pow2(p.Wout)) return PG_E_UNSUP;
-    if (ups && ((Hin | Win) & 1)) return PG_E_ARG;
-    if (ypool && ((p.Hout | p.Wout) & 1)) return PG_E_ARG;
-    // 32-bit element offsets inside the kernels
-    if ((long long)N * Hin * Win * Cin >= (1ll << 31) || (long long)N * p.Hout * p.Wout * Cout >= (1ll << 31) ||
-        (long long)KS * KS * Cout * Cin >= (1ll << 31)) return PG_E_UNSUP;
+    p.N = N; p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.Cout = Cout; p.KS = KS; p.pad = pad;
     p.scale = scale; p.slope = slope; p.mask_slope = mask_slope;
-    p.ksplit = 1;
-    const bool fuse_pool = ypool != nullptr && KS == 3 && g_tune[3] != 3;
-    p.ypool = fuse_pool ? ypool : nullptr; p.pool_other = pool_other; p.pool_a = pool_a; p.pool_b = pool_b;
-    p.pool_only = pool_only;
-    // the unpool epilogue exists in the generic tile kernel only (no split-K): everything else unpools in a second pass
-    const bool fuse_up = yup != nullptr && KS == 3 && g_tune[3] != 10;
-    p.yup = nullptr; p.upmask = upmask; p.up_mul = up_mul;
-    p.pn_r = nullptr; p.pn_eps = pn_eps; p.pnb_y = nullptr; p.pnb_r = pnb_r;
+    return p;
+}
+
+// ``p``: the request of an entry point (every optional output it wants is set); ``flags``: PG_FLAG_*
+static int conv2d_impl(ConvP& p, int flags, pg_stream_t stream)
+{
+    if (!p.x || !p.w || !p.y || p.N <= 0 || p.Hin <= 0 || p.Win <= 0 || p.Cin <= 0 || p.Cout <= 0) return PG_E_ARG;
+    if ((p.Cin & 3) || (p.Cout & 3)) return PG_E_ALIGN;
+    const int KS = p.KS, Cin = p.Cin, Cout = p.Cout;
+    p.ups = flags & PG_FLAG_UPSAMPLE;
+    p.mask_bytes = (flags & PG_FLAG_MASK_BYTES) ? 1 : 0; p.y_bytes = (flags & PG_FLAG_Y_BYTES) ? 1 : 0;
+    if (flags & PG_FLAG_SIGNS_OUT) {                        // forward mode: the (otherwise unused) mask argument is the byte output
+        if (!p.mask || p.mask_bytes) return PG_E_ARG;
+        p.ysigns = reinterpret_cast<unsigned char*>(const_cast<float*>(p.mask));
+        p.mask = nullptr;
+    }
+    p.Hout = p.Hin + 2 * p.pad - KS + 1; p.Wout = p.Win + 2 * p.pad - KS + 1;
+    if (p.Hout <= 0 || p.Wout <= 0 || !is_pow2(p.Hout) || !is_pow2(p.Wout)) return PG_E_UNSUP;
+    if (p.ups && ((p.Hin | p.Win) & 1)) return PG_E_ARG;
+    if (p.ypool && ((p.Hout | p.Wout) & 1)) return PG_E_ARG;
+    // 32-bit element offsets inside the kernels
+    if ((long long)p.N * p.Hin * p.Win * Cin >= (1ll << 31) || (long long)p.N * p.Hout * p.Wout * Cout >= (1ll << 31) ||
+        (long long)KS * KS * Cout * Cin >= (1ll << 31)) return PG_E_UNSUP;
+    // ``want`` keeps the request; in p an optional output is set only while the launch at hand fuses it.  The pool is fused by every
+    // 3x3 launch that does not split K, the others by the launches below that name them.
+    const ConvP want = p;
+    if (KS != 3) p.ypool = nullptr;
+    p.yup = nullptr; p.pn_r = nullptr; p.pnb_y = nullptr;
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if (p.mask_bytes || p.y_bytes || p.ysigns) {
         // sign-byte activations exist in the epilogues of the generic tile kernel (no split-K, no second pass) and of the
         // 8-cout block-MFMA kernel only: PG_E_UNSUP tells the caller to redo the layer with fp32 masks
-        if (KS != 3 || (p.y_bytes && !ypool) || pn_r || pnb_y) return PG_E_UNSUP;
-        p.ypool = ypool;
-        p.yup = yup;
-        const bool thin_plain = !p.y_bytes && !yup && !ypool && ((Cout == 8 && (Cin == 8 || Cin == 16)) || (Cout == 16 && Cin == 8 && mask));
-        const bool thin_pool = g_tune[3] != 17 && !yup && ypool && Cout == 16 && Cin == 8;      // 8->16 + pool (forward: sign bytes out; tangent: masked): +8..14 % over the generic tile kernel (tools/sweeps/bench_thin16pool.py)
-        const bool thin_b = pad == 1 && (thin_plain || thin_pool) && (p.Wout & 31) == 0 && (p.Hout & 7) == 0 && g_tune[3] != 2;
-        if (thin_b) return dispatch_thin(p, s);
-        return dispatch_conv_generic_nosplit(p, s);
+        if (KS != 3 || (p.y_bytes && !p.ypool) || want.pn_r || want.pnb_y) return PG_E_UNSUP;
+        p.yup = want.yup;
+        const bool thin_plain = !p.y_bytes && !p.yup && !p.ypool && ((Cout == 8 && (Cin == 8 || Cin == 16)) || (Cout == 16 && Cin == 8 && p.mask));
+        // 8->16 + pool (forward: sign bytes out; tangent: masked): +8..14 % over the generic tile kernel (tools/sweeps/bench_thin16pool.py)
+        const bool thin_pool = g_tune[PG_TUNE_PATH] != PG_PATH_NO_THIN_POOL16 && !p.yup && p.ypool && Cout == 16 && Cin == 8;
+        return thin_shape(p, thin_plain || thin_pool) ? dispatch_thin(p, s) : dispatch_conv_generic_nosplit(p, s);
     }
-    if (pnb_y && pnb_r && KS == 3 && Cout <= 32 && g_tune[3] != 12) {
-        p.pnb_y = pnb_y;
-        const bool thin_pn = pad == 1 && Cout == 8 && (Cin == 8 || Cin == 16) && (p.Wout & 31) == 0 && (p.Hout & 7) == 0 && g_tune[3] != 2;
+    const bool thin_pn = thin_shape(p, Cout == 8 && (Cin == 8 || Cin == 16));
+    if (want.pnb_y && want.pnb_r && KS == 3 && Cout <= 32) {             // fused PixelNorm adjoint: thin kernel (8 couts) or one-row generic tiles
+        p.pnb_y = want.pnb_y;
         rc = thin_pn ? dispatch_thin(p, s) : dispatch_conv_generic_nosplit(p, s);
-        if (rc == 0) return 0;
         if (rc != PG_E_UNSUP) return rc;
         p.pnb_y = nullptr;
     }
-    if (pn_r && KS == 3 && Cout <= 32 && !mask && g_tune[3] != 11) {   // fused PixelNorm: thin kernel (8 couts) or one-row generic tiles
-        p.pn_r = pn_r;
-        const bool thin_pn = pad == 1 && Cout == 8 && (Cin == 8 || Cin == 16) && (p.Wout & 31) == 0 && (p.Hout & 7) == 0 && g_tune[3] != 2;
+    if (want.pn_r && KS == 3 && Cout <= 32 && !p.mask && g_tune[PG_TUNE_PATH] != PG_PATH_UNFUSED_PIXELNORM) {   // fused PixelNorm, likewise
+        p.pn_r = want.pn_r;
         rc = thin_pn ? dispatch_thin(p, s) : dispatch_conv_generic_nosplit(p, s);
-        if (rc == 0) return 0;
         if (rc != PG_E_UNSUP) return rc;
         p.pn_r = nullptr;
     }
-    if (fuse_up) {
-        p.yup = yup;
+    if (want.yup && KS == 3) {             // the unpool epilogue exists in the generic tile kernel only (no split-K): everything else unpools in a second pass
+        p.yup = want.yup;
         rc = dispatch_conv_generic_nosplit(p, s);
-        if (rc == 0) return 0;
         if (rc != PG_E_UNSUP) return rc;
         p.yup = nullptr;
     }
     // measured (tools/sweeps/sweep_thin8.py): 1.5-1.7x on 8 couts; on 16 couts only the masked 8->16 launch gains (the
     // 16x16x4 tile has no padding there), 32 input channels lose -> those stay on the generic kernel
-    const bool thin_ok = KS == 3 && pad == 1 && ((Cout == 8 && (Cin == 8 || Cin == 16)) || (Cout == 16 && Cin == 8 && mask && !ypool)) &&
-                         (p.Wout & 31) == 0 && (p.Hout & 7) == 0 && g_tune[3] != 2;
-    if (thin_ok) {
+    if (thin_shape(p, (Cout == 8 && (Cin == 8 || Cin == 16)) || (Cout == 16 && Cin == 8 && p.mask && !want.ypool)))
         rc = dispatch_thin(p, s);                       // pools in its own epilogue when p.ypool is set
-        if (rc) return rc;
-        if (ypool && !p.ypool)
-            return pg_avgpool2_fwd(y, pool_other, ypool, N, p.Hout >> 1, p.Wout >> 1, Cout, pool_a, pool_b, stream);
-        if (yup) return pg_avgpool2_bwd(y, upmask, yup, N, p.Hout, p.Wout, Cout, up_mul, mask_slope, stream);
-        if (pn_r) return pg_pixelnorm_fwd(y, y, pn_r, (int64_t)N * p.Hout * p.Wout, Cout, pn_eps, stream);
-        if (pnb_y) return pg_pixelnorm_lrelu_bwd(y, pnb_y, pnb_r, y, (int64_t)N * p.Hout * p.Wout, Cout, mask_slope, stream);
-        return 0;
-    }
-    if (KS == 4 && !ups && k4_dense_ok(Cin, Cout) && g_tune[3] != 1 &&
-        ((pad == 3 && Hin == 1 && Win == 1) || (pad == 0 && Hin == 4 && Win == 4)))
+    else if (k4_layer(p, KS))
         rc = launch_k4_conv(p, s);
     else switch (KS) {
         case 1: rc = dispatch_conv_vec<1>(p, s); break;
@@ -2054,20 +2050,15 @@ static int conv2d_impl(const float* x, const float* w, const float* bias, const 
         default: return PG_E_UNSUP;
     }
     if (rc) return rc;
-    if (ypool && !(fuse_pool && p.ksplit == 1))          // split-K / non-3x3 launches pool in a second pass over y
-        return pg_avgpool2_fwd(y, pool_other, ypool, N, p.Hout >> 1, p.Wout >> 1, Cout, pool_a, pool_b, stream);
-    if (yup) return pg_avgpool2_bwd(y, upmask, yup, N, p.Hout, p.Wout, Cout, up_mul, mask_slope, stream);
-    if (pn_r) return pg_pixelnorm_fwd(y, y, pn_r, (int64_t)N * p.Hout * p.Wout, Cout, pn_eps, stream);
-    if (pnb_y) return pg_pixelnorm_lrelu_bwd(y, pnb_y, pnb_r, y, (int64_t)N * p.Hout * p.Wout, Cout, mask_slope, stream);
-    return 0;
+    return second_pass(want, p.ypool && p.ksplit == 1, stream);      // (split-K launches defer their epilogue: no pool)
 }
 
 extern "C" int pg_conv2d_nhwc(const float* x, const float* w, const float* bias, const float* mask, float* y,
                               int N, int Hin, int Win, int Cin, int Cout, int KS, int pad, int ups,
                               float scale, float slope, float mask_slope, pg_stream_t stream)
 {
-    return conv2d_impl(x, w, bias, mask, y, nullptr, nullptr, 1.f, 0.f, 0, N, Hin, Win, Cin, Cout, KS, pad, ups,
-                       scale, slope, mask_slope, stream);
+    ConvP p = conv_request(x, w, bias, mask, y, N, Hin, Win, Cin, Cout, KS, pad, scale, slope, mask_slope);
+    return conv2d_impl(p, ups, stream);
 }
 
 extern "C" int pg_conv2d_pixelnorm_nhwc(const float* x, const float* w, const float* bias, float* y, float* r,
@@ -2075,8 +2066,9 @@ extern "C" int pg_conv2d_pixelnorm_nhwc(const float* x, const float* w, const fl
                                         float scale, float slope, float eps, pg_stream_t stream)
 {
     if (!r) return PG_E_ARG;
-    return conv2d_impl(x, w, bias, nullptr, y, nullptr, nullptr, 1.f, 0.f, 0, N, Hin, Win, Cin, Cout, KS, pad, ups,
-                       scale, slope, 0.2f, stream, nullptr, nullptr, 1.f, r, eps);
+    ConvP p = conv_request(x, w, bias, nullptr, y, N, Hin, Win, Cin, Cout, KS, pad, scale, slope, 0.2f);
+    p.pn_r = r; p.pn_eps = eps;
+    return conv2d_impl(p, ups, stream);
 }
 
 extern "C" int pg_conv2d_pnbwd_nhwc(const float* x, const float* w, const float* ysaved, const float* r, float* y,
@@ -2084,8 +2076,9 @@ extern "C" int pg_conv2d_pnbwd_nhwc(const float* x, const float* w, const float*
                                     float scale, float slope, pg_stream_t stream)
 {
     if (!ysaved) return PG_E_ARG;
-    return conv2d_impl(x, w, nullptr, nullptr, y, nullptr, nullptr, 1.f, 0.f, 0, N, Hin, Win, Cin, Cout, KS, pad, 0,
-                       scale, 1.0f, slope, stream, nullptr, nullptr, 1.f, nullptr, 0.f, ysaved, r);
+    ConvP p = conv_request(x, w, nullptr, nullptr, y, N, Hin, Win, Cin, Cout, KS, pad, scale, 1.0f, slope);
+    p.pnb_y = ysaved; p.pnb_r = r;
+    return conv2d_impl(p, 0, stream);
 }
 
 extern "C" int pg_conv2d_unpool_nhwc(const float* x, const float* w, const float* upmask, float* y, float* yup,
@@ -2093,8 +2086,9 @@ extern "C" int pg_conv2d_unpool_nhwc(const float* x, const float* w, const float
                                      float scale, float up_mul, float mask_slope, pg_stream_t stream)
 {
     if (!yup) return PG_E_ARG;
-    return conv2d_impl(x, w, nullptr, nullptr, y, nullptr, nullptr, 1.f, 0.f, 0, N, Hin, Win, Cin, Cout, KS, pad, flags & PG_FLAG_MASK_BYTES,
-                       scale, 1.0f, mask_slope, stream, yup, upmask, up_mul);
+    ConvP p = conv_request(x, w, nullptr, nullptr, y, N, Hin, Win, Cin, Cout, KS, pad, scale, 1.0f, mask_slope);
+    p.yup = yup; p.upmask = upmask; p.up_mul = up_mul;
+    return conv2d_impl(p, flags & PG_FLAG_MASK_BYTES, stream);
 }
 
 extern "C" int pg_conv2d_pool_nhwc(const float* x, const float* w, const float* bias, const float* mask, float* y,
@@ -2103,8 +2097,9 @@ extern "C" int pg_conv2d_pool_nhwc(const float* x, const float* w, const float* 
                                    float scale, float slope, float mask_slope, pg_stream_t stream)
 {
     if (!ypool) return PG_E_ARG;
-    return conv2d_impl(x, w, bias, mask, y, ypool, pool_other, pool_a, pool_b, pool_only, N, Hin, Win, Cin, Cout, KS, pad, ups,
-                       scale, slope, mask_slope, stream);
+    ConvP p = conv_request(x, w, bias, mask, y, N, Hin, Win, Cin, Cout, KS, pad, scale, slope, mask_slope);
+    p.ypool = ypool; p.pool_other = pool_other; p.pool_a = pool_a; p.pool_b = pool_b; p.pool_only = pool_only;
+    return conv2d_impl(p, ups, stream);
 }
 
 extern "C" int pg_conv2d_wgrad_nhwc(const float* x, const float* gz, float* dw, float* db,
@@ -2120,11 +2115,8 @@ extern "C" int pg_conv2d_wgrad_nhwc(const float* x, const float* gz, float* dw, 
     if (p.Hout <= 0 || p.Wout <= 0 || !is_pow2(p.Hout) || !is_pow2(p.Wout)) return PG_E_UNSUP;
     if (ups && ((Hin | Win) & 1)) return PG_E_ARG;
     p.scale = scale;
-    p.gbytes = nullptr; p.gmul = 1.f; p.gslope = 1.f;
     hipStream_t s = (hipStream_t)stream;
-    if (KS == 4 && !ups && k4_dense_ok(Cin, Cout) && g_tune[3] != 1 &&
-        ((pad == 3 && Hin == 1 && Win == 1) || (pad == 0 && Hin == 4 && Win == 4)))
-        return launch_k4_wgrad(p, s);
+    if (k4_layer(p, KS)) return launch_k4_wgrad(p, s);
     switch (KS) {
         case 1: return dispatch_wgrad<1>(p, s);
         case 3: return dispatch_wgrad<3>(p, s);
@@ -2146,14 +2138,11 @@ extern "C" int pg_conv2d_unpooled_nhwc(const float* g, const float* w, const uns
     if (!(Cout == 8 && (Cin == 8 || Cin == 16)) || (Win & 31) || (Hin & 7) || !is_pow2(Hin) || !is_pow2(Win)) return PG_E_UNSUP;
     if ((long long)N * Hin * Win * Cin >= (1ll << 31)) return PG_E_UNSUP;
     ConvP p;
-    p.x = g; p.w = w; p.bias = nullptr; p.mask = mask; p.y = y;
+    p.x = g; p.w = w; p.mask = mask; p.y = y;
     p.N = N; p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.Cout = Cout; p.KS = 3; p.pad = 1; p.ups = 1;
     p.Hout = Hin; p.Wout = Win;
-    p.scale = scale; p.slope = 1.f; p.mask_slope = mask_slope; p.ksplit = 1;
-    p.ypool = nullptr; p.pool_other = nullptr; p.pool_a = 1.f; p.pool_b = 0.f; p.pool_only = 0;
-    p.yup = nullptr; p.upmask = nullptr; p.up_mul = 1.f;
-    p.pn_r = nullptr; p.pn_eps = 0.f; p.pnb_y = nullptr; p.pnb_r = nullptr;
-    p.mask_bytes = (flags & PG_FLAG_MASK_BYTES) ? 1 : 0; p.y_bytes = 0; p.ysigns = nullptr;
+    p.scale = scale; p.mask_slope = mask_slope;
+    p.mask_bytes = (flags & PG_FLAG_MASK_BYTES) ? 1 : 0;
     p.gbytes = gbytes; p.gmul = gmul; p.gslope = gslope;
     return dispatch_thin(p, (hipStream_t)stream);
 }
@@ -2226,7 +2215,7 @@ extern "C" int pg_debug_wgrad_trace(void* buf) { g_wgrad_trace = (unsigned long 
 extern "C" int pg_debug_set_tuning(int key, int value)
 {
     if (key < 0 || key >= 4) return PG_E_ARG;
-    g_tune[key] = value;
+    g_tune[key] = value;                                    // (values nothing interprets select nothing: see the enums)
     return 0;
 }
 

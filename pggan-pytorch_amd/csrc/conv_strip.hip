@@ -30,7 +30,6 @@
 // upsample fused into the row gather (the DMA source address).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <cstdio>
 #include <type_traits>
 #include "pggan_hip.h"
@@ -880,23 +879,30 @@ int launch_wgrad_strip_t(const WArgs& a, int N, hipStream_t s, char* name, size_
     return (int)hipGetLastError();
 }
 
+// Rows per workgroup of the conv kernels: long enough to amortise the two-block prologue, short enough for >= 3 workgroups per CU.
+// 0: no legal segment length for this map.
+int strip_seg_rows(int N, int H, int W)
+{
+    int seg = 64;
+    while (seg > 16 && ((long long)N * (W / SW) * (H / seg) < 768 || (H % seg))) seg >>= 1;
+    return (seg < 16 || (seg % RB) || (H % seg)) ? 0 : seg;
+}
+
+// 8 -> 8 layers keep the weights of a lane's cout row in registers (72 VGPRs, three waves per SIMD) instead of LDS: 0.5-3 % slower alone
+// on the device in round 3, but faster INSIDE the two-stream step, where the LDS pipe is shared with the weight-gradient kernels -- round 4,
+// same box, three pairs: 10.71 / 10.68 / 10.68 vs 10.81 / 10.82 / 10.72 ms per step.  Exceptions are noted where they are launched.
+constexpr bool STRIP_WREG = true;
+
 }  // namespace
 
 int pgk::launch_conv_strip(ConvP& p, hipStream_t s, char* name, size_t name_len)
 {
-    static const int seg_env = getenv("PG_STRIP_SEG") ? atoi(getenv("PG_STRIP_SEG")) : 0;
-    // (8 -> 8 weights in registers: 0.5-3 % slower alone on the device in round 3, but faster INSIDE the two-stream step, where the LDS pipe is
-    //  shared with the weight-gradient kernels -- round 4, same box, three pairs: 10.71 / 10.68 / 10.68 vs 10.81 / 10.82 / 10.72 ms per step)
-    static const int wreg_env = getenv("PG_STRIP_WREG") ? atoi(getenv("PG_STRIP_WREG")) : 1;
-    static const int epi_env = getenv("PG_STRIP_EPI") ? atoi(getenv("PG_STRIP_EPI")) : -1;      // 0: always the generic epilogue (A/B)
     if (p.KS != 3 || p.pad != 1 || p.yup || p.ksplit != 1) return PG_E_UNSUP;
     if ((p.Wout % SW) || (p.Hout % 16) || p.Hout != p.Hin || p.Wout != p.Win) return PG_E_UNSUP;
     if (!(p.Cout == 8 && (p.Cin == 8 || p.Cin == 16))) return PG_E_UNSUP;       // (16 couts: the tile / Winograd kernels keep those layers)
     if ((long long)p.Hin * p.Win * 16 * 4 >= (1ll << 31)) return PG_E_UNSUP;     // 32-bit byte offsets inside an image
-    // rows per workgroup: long enough to amortise the two-block prologue, short enough for >= 3 workgroups per CU
-    int seg = seg_env > 0 ? seg_env : 64;
-    while (seg > 16 && ((long long)p.N * (p.Wout / SW) * (p.Hout / seg) < 768 || (p.Hout % seg))) seg >>= 1;
-    if (seg < 16 || (seg % RB) || (p.Hout % seg)) return PG_E_UNSUP;
+    const int seg = strip_seg_rows(p.N, p.Hout, p.Wout);
+    if (!seg) return PG_E_UNSUP;
     SArgs a{};                                   // (the fields this entry does not use -- fromRGB gather, toRGB epilogue -- must read as "off")
     a.x = p.x; a.w = p.w; a.bias = p.bias; a.mask = p.mask; a.y = p.y;
     a.ysigns = p.ysigns; a.pn_r = p.pn_r; a.pnb_y = p.pnb_y; a.pnb_r = p.pnb_r; a.ypool = p.ypool; a.pool_other = p.pool_other;
@@ -918,10 +924,7 @@ int pgk::launch_conv_strip(ConvP& p, hipStream_t s, char* name, size_t name_len)
         else if (p.mask && !p.pnb_y && !p.pn_r) epi = EPI_MASK;
         else if (!p.mask && !p.pnb_y && !p.pn_r) epi = EPI_FWD;
     }
-    if (epi_env == 0) epi = EPI_GENERIC;
-    // 8 -> 8: the weights of a lane's cout row fit in registers (72 VGPRs, three waves per SIMD) or stay in LDS (four+ waves per SIMD)
-    if (p.Cin == 8) return wreg_env ? launch_strip_epi<8, 8, true>(a, epi, p.N, s, name, name_len)
-                                    : launch_strip_epi<8, 8, false>(a, epi, p.N, s, name, name_len);
+    if (p.Cin == 8) return launch_strip_epi<8, 8, STRIP_WREG>(a, epi, p.N, s, name, name_len);
     return launch_strip_epi<8, 16, false>(a, epi, p.N, s, name, name_len);
 }
 
@@ -932,9 +935,8 @@ int pgk::launch_conv_strip_fromrgb(const float* img, const float* rgb_w, const f
 {
     if (C > RGB_MAXC || Cmid != 8 || Cout != 8 || (W % SW) || (H % 16)) return PG_E_UNSUP;
     if ((long long)H * W * 16 * 4 >= (1ll << 31)) return PG_E_UNSUP;            // 32-bit byte offsets inside an image
-    int seg = 64;                                                                // (as launch_conv_strip)
-    while (seg > 16 && ((long long)N * (W / SW) * (H / seg) < 768 || (H % seg))) seg >>= 1;
-    if (seg < 16 || (seg % RB) || (H % seg)) return PG_E_UNSUP;
+    const int seg = strip_seg_rows(N, H, W);
+    if (!seg) return PG_E_UNSUP;
     SArgs a{};
     a.x = img; a.w = w; a.bias = bias; a.y = y; a.ysigns = y_signs;
     a.scale = scale; a.slope = slope; a.mask_slope = 1.f; a.pool_a = 1.f;
@@ -953,18 +955,16 @@ int pgk::launch_conv_strip_pn_torgb(const float* x, const float* w, const float*
                                     int N, int C, int H, int W, int Cin, int Cout, float scale, float slope, float eps,
                                     hipStream_t s, char* name, size_t name_len)
 {
-    static const int wreg_env = getenv("PG_STRIP_WREG") ? atoi(getenv("PG_STRIP_WREG")) : 1;
     if (C < 1 || C > RGB_MAXC || Cin != 8 || Cout != 8 || (W % SW) || (H % 16)) return PG_E_UNSUP;
     if ((long long)H * W * 16 * 4 >= (1ll << 31)) return PG_E_UNSUP;
-    int seg = 64;                                                                // (as launch_conv_strip)
-    while (seg > 16 && ((long long)N * (W / SW) * (H / seg) < 768 || (H % seg))) seg >>= 1;
-    if (seg < 16 || (seg % RB) || (H % seg)) return PG_E_UNSUP;
+    const int seg = strip_seg_rows(N, H, W);
+    if (!seg) return PG_E_UNSUP;
     SArgs a{};
     a.x = x; a.w = w; a.bias = bias; a.y = y; a.pn_r = r; a.pn_eps = eps;
     a.scale = scale; a.slope = slope; a.mask_slope = 1.f; a.pool_a = 1.f;
     a.H = H; a.W = W; a.strips = W / SW; a.segs = H / seg; a.seg_rows = seg;
     a.t_out = img; a.t_w = t_w; a.t_b = t_b; a.t_scale = t_scale; a.tC = C; a.t_sc = Cout; a.t_sco = 1;
-    return wreg_env ? launch_strip_x<EPI_PN, true, 1>(a, N, s, name, name_len) : launch_strip_x<EPI_PN, false, 1>(a, N, s, name, name_len);
+    return launch_strip_x<EPI_PN, STRIP_WREG, 1>(a, N, s, name, name_len);
 }
 
 int pgk::launch_conv_strip_masked_rgb_bwd(const float* gz, const float* wt, const unsigned char* mask_bytes, float mask_slope, float* y,
@@ -973,35 +973,31 @@ int pgk::launch_conv_strip_masked_rgb_bwd(const float* gz, const float* wt, cons
                                           int N, int C, int H, int W, int Cin, int Cout, float scale,
                                           hipStream_t s, char* name, size_t name_len)
 {
-    // (with the weight gradient's 16 accumulators the register-weights form would drop to two waves per SIMD: weights in LDS then)
-    static const int wreg_env0 = getenv("PG_STRIP_WREG") ? atoi(getenv("PG_STRIP_WREG")) : 1;
-    const int wreg_env = rgb_dw ? 0 : wreg_env0;
     if (C < 1 || C > RGB_MAXC || Cin != 8 || Cout != 8 || (W % SW) || (H % 16)) return PG_E_UNSUP;
     if ((long long)H * W * 16 * 4 >= (1ll << 31)) return PG_E_UNSUP;
-    int seg = 64;                                                                // (as launch_conv_strip)
-    while (seg > 16 && ((long long)N * (W / SW) * (H / seg) < 768 || (H % seg))) seg >>= 1;
-    if (seg < 16 || (seg % RB) || (H % seg)) return PG_E_UNSUP;
+    const int seg = strip_seg_rows(N, H, W);
+    if (!seg) return PG_E_UNSUP;
     SArgs a{};
     a.x = gz; a.w = wt; a.mask = mask_bytes; a.mask_bytes = 1; a.y = y;
     a.scale = scale; a.slope = 1.f; a.mask_slope = mask_slope; a.pool_a = 1.f;
     a.H = H; a.W = W; a.strips = W / SW; a.segs = H / seg; a.seg_rows = seg;
     a.t_out = gimg; a.t_w = rgb_w; a.t_b = nullptr; a.t_scale = rgb_scale; a.tC = C; a.t_sc = 1; a.t_sco = C; a.t_only = y ? 0 : 1;
     a.fw_img = img; a.fw_dw = rgb_dw; a.fw_db = rgb_db; a.fw_scale = rgb_scale;
+    // weights in LDS, both forms: with the weight gradient's 16 accumulators the register-weights form would drop to two waves per SIMD,
+    // and without them it sits at the 168-VGPR cap of three waves per SIMD and spills
     if (rgb_dw) return launch_strip_x<EPI_MASK, false, 3>(a, N, s, name, name_len);
-    (void)wreg_env;                              // (the register-weights form of this one sits at the 168-VGPR cap of three waves per SIMD and spills)
     return launch_strip_x<EPI_MASK, false, 1>(a, N, s, name, name_len);
 }
 
 int pgk::launch_wgrad_strip(WgP& p, hipStream_t s, char* name, size_t name_len)
 {
-    static const int seg_env = getenv("PG_WSTRIP_SEG") ? atoi(getenv("PG_WSTRIP_SEG")) : 0;
     if (p.pad != 1 || p.Hout != p.Hin || p.Wout != p.Win || (p.gbytes && p.ups)) return PG_E_UNSUP;
     if ((p.Wout % SW) || (p.Hout % 16)) return PG_E_UNSUP;
     if (!((p.Cout == 8 && p.Cin == 8) || (p.Cout == 16 && p.Cin == 8) || (p.Cout == 8 && p.Cin == 16))) return PG_E_UNSUP;
     if ((long long)p.Hin * p.Win * 16 * 4 >= (1ll << 31)) return PG_E_UNSUP;     // 32-bit byte offsets inside an image
     // one commit of |dW| atomics per workgroup: few, long-lived workgroups -- ~1000 of them while the segments stay >= 64 rows
     // (measured at 1024^2: 9 images 128 rows = 1152 workgroups 143 us, 256 rows 160 us, 64 rows 147 us), >= 512 below that
-    int seg = seg_env > 0 ? seg_env : 256;
+    int seg = 256;
     auto tasks = [&](int sg) { return (long long)p.N * (p.Wout / SW) * (p.Hout / sg); };
     while (seg > 64 && (seg > p.Hout || (p.Hout % seg) || tasks(seg) < 1024)) seg >>= 1;
     while (seg > 16 && (seg > p.Hout || (p.Hout % seg) || tasks(seg) < 512)) seg >>= 1;

@@ -24,7 +24,6 @@
 #include <type_traits>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include "pggan_hip.h"
 #include "bufload.h"
 #include "convp.h"
@@ -437,12 +436,11 @@ __global__ __launch_bounds__(256, 2) void conv_wino_strip_kernel(WinoP p, WinoSt
 template <int CIN, int NCB, int EPI>
 int launch_ws(const WinoP& p, WinoStripGeo g, hipStream_t s, char* name, size_t name_len)
 {
-    static const int rounds_env = getenv("PG_WSTRIP_ROUNDS") ? atoi(getenv("PG_WSTRIP_ROUNDS")) : 1;
-    static const int minspw_env = getenv("PG_WSTRIP_MINSPW") ? atoi(getenv("PG_WSTRIP_MINSPW")) : 4;
-    static const int stagger_env = getenv("PG_WSTRIP_STAGGER") ? atoi(getenv("PG_WSTRIP_STAGGER")) : -1;
+    constexpr int MIN_SPW = 4;                   // steps per workgroup, at least
     const size_t smem = (size_t)Ring<CIN>::BYTES + (size_t)(CIN / 4) * 16 * 16 * NCB * 16;
     auto kern = conv_wino_strip_kernel<CIN, NCB, EPI>;
-    // resident workgroups of this kernel on this device (queried once per device): the grid is sized to ONE round of them
+    // resident workgroups of this kernel on this device (queried once per device; process-wide state (3) of pggan_hip.h): the grid is
+    // sized to ONE round of them
     static int slots[16] = {0};
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return (int)e;
@@ -458,16 +456,15 @@ int launch_ws(const WinoP& p, WinoStripGeo g, hipStream_t s, char* name, size_t 
         if (nb < 1 || cus < 1) return PG_E_UNSUP;
         slots[dev] = nb * cus;
     }
-    const int rounds = rounds_env > 0 ? rounds_env : 1;
-    long long target = (long long)slots[dev] * rounds / g.ncog;
+    long long target = (long long)slots[dev] / g.ncog;
     if (target < 1) target = 1;
     int spw = (int)((g.total + target - 1) / target);
-    if (spw < minspw_env) spw = minspw_env;
+    if (spw < MIN_SPW) spw = MIN_SPW;
     g.spw = spw;
     g.nrun = (g.total + spw - 1) / spw;
     // start offset between the waves that share a SIMD, in units of 512 cycles: one wave's MFMA time per step (1024 cycles per
     // 8-channel chunk and cout block)
-    g.stagger = stagger_env >= 0 ? stagger_env : 2 * (CIN / 8) * NCB;
+    g.stagger = 2 * (CIN / 8) * NCB;
     snprintf(name, name_len, "conv_wino_strip_kernel<%d, %d, %d>", CIN, NCB, EPI);
     hipLaunchKernelGGL(kern, dim3((unsigned)(g.nrun * g.ncog)), dim3(256), smem, s, p, g);
     return (int)hipGetLastError();
@@ -488,8 +485,6 @@ int launch_ws_epi(const WinoP& p, const WinoStripGeo& g, int epi, hipStream_t s,
     return launch_ws<CIN, NCB, SE_GENERIC>(p, g, s, name, name_len);
 }
 
-inline int ilog2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
 }  // namespace
 
 // Called by wino_conv (conv_wino.hip) with the epilogue fields of ``p`` filled in.  PG_E_UNSUP = "not this shape": the caller keeps
@@ -498,7 +493,6 @@ inline int ilog2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 // faster there (tools/sweeps/bench_wino_strip.py: the general epilogue costs the strip kernel half of its resident waves).
 int pgw::launch_wino_strip(WinoP& p, int mode, hipStream_t s, char* name, size_t name_len)
 {
-    static const int ncb_env = getenv("PG_WSTRIP_WINO_NCB") ? atoi(getenv("PG_WSTRIP_WINO_NCB")) : 0;
     if (p.Cin != 8 && p.Cin != 16 && p.Cin != 32) return PG_E_UNSUP;
     if ((p.Cout & 15) || (p.W % SW) || (p.H & 15) || (p.H & (p.H - 1)) || (p.W & (p.W - 1))) return PG_E_UNSUP;
     if ((long long)p.H * p.W * 32 * 4 >= (1ll << 31)) return PG_E_UNSUP;          // 32-bit byte offsets inside an image
@@ -521,7 +515,6 @@ int pgw::launch_wino_strip(WinoP& p, int mode, hipStream_t s, char* name, size_t
     // couts per workgroup: every cout of a pixel for the PixelNorm epilogues (<= 32), else 32 when the layer has them and the
     // 64 KB of U still leave room (Cin <= 16), 16 otherwise
     int ncb = (p.pn_r || p.pnb_y) ? (p.Cout > 16 ? 2 : 1) : ((p.Cout % 32 == 0 && p.Cin <= 16) ? 2 : 1);
-    if (ncb_env == 1 || ncb_env == 2) { if (!(p.pn_r || p.pnb_y)) ncb = ncb_env; }
     if (se == SE_PLAIN_SIGNS || se == SE_UNPOOL) ncb = 1;       // (these two exist for 16 couts per workgroup only: never fall through to the general epilogue)
     if ((p.pn_r || p.pnb_y) && p.Cout > 32) return PG_E_UNSUP;
     if (p.Cout % (16 * ncb)) return PG_E_UNSUP;
@@ -530,7 +523,7 @@ int pgw::launch_wino_strip(WinoP& p, int mode, hipStream_t s, char* name, size_t
     if (g.ncog & (g.ncog - 1)) return PG_E_UNSUP;
     g.strips = p.W / SW; g.stepsH = p.H >> 2;
     g.total = p.N * g.strips * g.stepsH;
-    g.lgCog = ilog2i(g.ncog); g.lgStrips = ilog2i(g.strips); g.lgStepsH = ilog2i(g.stepsH);
+    g.lgCog = pgk::ilog2(g.ncog); g.lgStrips = pgk::ilog2(g.strips); g.lgStepsH = pgk::ilog2(g.stepsH);
     g.spw = g.nrun = g.stagger = 0;                          // (launch_ws: they depend on the kernel variant's occupancy)
     switch (p.Cin) {
         case 8: return ncb == 2 ? launch_ws_epi<8, 2>(p, g, se, s, name, name_len) : launch_ws_epi<8, 1>(p, g, se, s, name, name_len);

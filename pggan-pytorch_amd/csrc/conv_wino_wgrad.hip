@@ -14,9 +14,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include "pggan_hip.h"
 #include "bufload.h"
+#include "convp.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -467,7 +467,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino_wgrad_pair_kernel(WWP p)
 
 
 thread_local char g_ww_last[64] = "";
-inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 }  // namespace
 
@@ -486,7 +485,7 @@ extern "C" int pg_conv2d_wgrad_wino2_nhwc(const float* x, const float* gz, int N
     if (!db) db_batches = 0;
     if (N2 > 0 && ((long long)N2 * H * W * Cin >= (1ll << 31) || (long long)N2 * H * W * Cout >= (1ll << 31))) return PG_E_UNSUP;
     if ((Cin & 3) || (Cout & 3)) return PG_E_ALIGN;
-    if (!pow2(H) || !pow2(W) || H < PH || W < PW) return PG_E_UNSUP;
+    if (!pgk::is_pow2(H) || !pgk::is_pow2(W) || H < PH || W < PW) return PG_E_UNSUP;
     if (ups && ((H | W) & 1)) return PG_E_ARG;
     if ((long long)N * H * W * Cin >= (1ll << 31) || (long long)N * H * W * Cout >= (1ll << 31)) return PG_E_UNSUP;
     if ((long long)H * W * Cin * 4 >= (1ll << 31) || (long long)H * W * Cout * 4 >= (1ll << 31)) return PG_E_UNSUP;      // 32-bit buffer offsets per image
@@ -496,8 +495,7 @@ extern "C" int pg_conv2d_wgrad_wino2_nhwc(const float* x, const float* gz, int N
     p.x2 = N2 > 0 ? x2 : x; p.gz2 = N2 > 0 ? gz2 : gz; p.db_batches = db_batches;
     p.N = N + N2; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.ups = ups; p.scale = scale;
     p.blocksW = W / PW; p.blocksH = H / PH;
-    p.lgBW = 0; while ((1 << p.lgBW) < p.blocksW) ++p.lgBW;
-    p.lgBH = 0; while ((1 << p.lgBH) < p.blocksH) ++p.lgBH;
+    p.lgBW = pgk::ilog2(p.blocksW); p.lgBH = pgk::ilog2(p.blocksH);
     p.nregions1 = N * p.blocksW * p.blocksH;
     p.nregions = (N + N2) * p.blocksW * p.blocksH;
 #ifdef PG_WINO_TRACE
@@ -514,9 +512,7 @@ extern "C" int pg_conv2d_wgrad_wino2_nhwc(const float* x, const float* gz, int N
     // (round 4, inside the train step where the kernel shares the CUs with the main stream's convs; ms per step, 384 | 512: 1024^2 stage (launches
     //  of 3 + 9 images) 10.573 / 10.573 | 10.607 / 10.617; 512^2 and 256^2 stages equal; 128^2 stage (16 + 48 images) 21.17 / 21.16 | 20.97 / 21.01;
     //  256 and 768 lose at 1024^2: 10.66 / 10.75.  Alone on the device 512 is 1-2 % faster than 384.)
-    static const int target_env = [] { const char* t = getenv("PG_WW_TARGET"); return t ? atoi(t) : 0; }();
-    static const int target3_env = [] { const char* t = getenv("PG_WW_TARGET3"); return t ? atoi(t) : 0; }();        // launches of <= 4 images (the G step's): sweeps
-    const int target = (target3_env > 0 && N + N2 <= 4) ? target3_env : target_env > 0 ? target_env : (N + N2 <= 12 ? 320 : N + N2 <= 24 ? 384 : 512);
+    const int target = N + N2 <= 12 ? 320 : N + N2 <= 24 ? 384 : 512;
     // (round 5, after the k-step got faster; same-box pairs: 1024^2 stage 320 | 384: 10.286 | 10.308 ms over five pairs, 288 equal, 256 +0.08;
     //  512^2 stage (launches of 6 and 24 images) 384 | 512: 13.44 | 13.54; 256^2 stage (14 and 56 images) 512 | 384 | 768: 23.0 | 23.1 | 23.1)
     int chunks = (target + gy * gz_ - 1) / (gy * gz_);
@@ -526,10 +522,10 @@ extern "C" int pg_conv2d_wgrad_wino2_nhwc(const float* x, const float* gz, int N
     chunks = (p.nregions + p.regions_per_block - 1) / p.regions_per_block;
     snprintf(g_ww_last, sizeof(g_ww_last), "conv_wino_wgrad_kernel<%d, %d>", nco, nci);
     const dim3 grid(chunks, gy, gz_);
-    // measured (tools/sweeps/sweep_wino_wgrad.py, PG_WW_PAIR=0/1/2): the pair mapping wins 8-9 % from ~9 regions per workgroup on
-    // (n9 @64 128->256: 137 -> 126 us) and loses up to 15 % at 3 (its extra fold through LDS); 1: built-in choice, 0 / 2: never / always
-    static const int pair_env = getenv("PG_WW_PAIR") ? atoi(getenv("PG_WW_PAIR")) : 1;
-    if (nco == 2 && nci == 2 && (pair_env == 2 || (pair_env == 1 && p.regions_per_block >= 6))) {
+    // measured (never / built-in / always, variant builds): the pair mapping wins 8-9 % from ~9 regions per workgroup on
+    // (n9 @64 128->256: 137 -> 126 us) and loses up to 15 % at 3 (its extra fold through LDS)
+    constexpr int PAIR_MIN_REGIONS = 6;
+    if (nco == 2 && nci == 2 && p.regions_per_block >= PAIR_MIN_REGIONS) {
         snprintf(g_ww_last, sizeof(g_ww_last), "conv_wino_wgrad_pair_kernel");
         hipLaunchKernelGGL(conv_wino_wgrad_pair_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
     }

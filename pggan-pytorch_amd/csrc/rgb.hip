@@ -3,7 +3,6 @@
 // traffic on the NHWC feature side, row-contiguous traffic on the NCHW image side, the
 // fade-in blend / 2x2 pooling of the image fused so the image is touched exactly once.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <stdint.h>
 #include "pggan_hip.h"
 
@@ -606,8 +605,6 @@ __global__ __launch_bounds__(256) void fromrgb_bwd_data_wide_kernel(
 // former flat cap of 1024 workgroups, n3 @256 32 features: 83 -> 44 us, n3 @1024 8 features: 42 -> 36 us, n9 unchanged).
 inline int small_wgrad_grid(size_t total, int features)
 {
-    static const int forced = getenv("PG_RGB_WGRAD_GRID") ? atoi(getenv("PG_RGB_WGRAD_GRID")) : 0;       // sweeps
-    if (forced > 0) return (int)((total + 255) / 256 < (size_t)forced ? (total + 255) / 256 : (size_t)forced);
     const size_t per_thread = (size_t)(192 / features < 1 ? 1 : 192 / features);
     size_t g = (total + 256 * per_thread - 1) / (256 * per_thread);
     if (g < 128) g = 128;

@@ -255,6 +255,58 @@ def test_library_exports_every_declared_symbol():
     assert lib.pg_abi_version() == pg._lib.ABI_VERSION
 
 
+def _library_sources():
+    import glob
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    paths = glob.glob(os.path.join(root, 'pggan-pytorch_amd', 'csrc', '*')) + glob.glob(os.path.join(root, 'include', '*'))
+    assert len(paths) > 10
+    return root, {p: open(p).read() for p in paths}
+
+
+def test_library_reads_no_environment_variable():
+    """pggan_hip.h lists the library's process-wide state "all of it": no source or header may call getenv."""
+    _, srcs = _library_sources()
+    assert [p for p, text in srcs.items() if 'getenv' in text] == []
+
+
+def test_tuning_values_are_named():
+    """Every PG_TUNE_* key / PG_PATH_* value that pggan_hip_debug.h declares is interpreted somewhere in csrc/, and csrc/ compares
+    g_tune[...] against those names: no bare integer other than 0 and -1 (the "built-in choice" tests)."""
+    import os
+    import re
+    root, srcs = _library_sources()
+    dbg = srcs[os.path.join(root, 'include', 'pggan_hip_debug.h')]
+    names = re.findall(r'\b(PG_(?:TUNE|PATH)_\w+)\s*=\s*\d+', dbg)
+    assert len(names) >= 4 + 7, names
+    csrc = '\n'.join(text for p, text in srcs.items() if os.sep + 'csrc' + os.sep in p)
+    for name in names:
+        assert re.search(r'\b%s\b' % name, csrc), name
+    cmp_ops = r'(?:==|!=|<=|>=|<|>)'
+    bare = re.findall(r'g_tune\[[^\]]*\]\s*%s\s*(-?\d+)\b' % cmp_ops, csrc) + \
+        re.findall(r'(-?\b\d+)\s*%s\s*g_tune\[' % cmp_ops, csrc)
+    assert len(bare) >= 3                                    # (the pattern still finds the comparisons)
+    assert [v for v in bare if v not in ('0', '-1')] == []
+    assert not re.search(r'switch\s*\(g_tune\[[^)]*\)\s*\{[^}]*\bcase\s+-?\d', csrc)
+
+
+def test_debug_set_wino_accepts_only_existing_variants():
+    """pg_debug_set_wino (host-only, thread-local): the first-generation kernel's values 2 and 4 are argument errors."""
+    import ctypes
+    import os
+    if not os.path.exists(pg.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    lib = ctypes.CDLL(pg.LIB_PATH)
+    PG_E_ARG = -1
+    try:
+        assert lib.pg_debug_set_wino(4) == PG_E_ARG and lib.pg_debug_set_wino(2) == PG_E_ARG
+        for v in (0, 11, 12, 20, 21):
+            assert lib.pg_debug_set_wino(v) == 0, v
+    finally:
+        lib.pg_debug_set_wino(0)
+
+
 def test_no_cpu_fallback():
     meta, data = load_fixture('tiny32')
     G, D = build_nets(meta)

@@ -83,19 +83,16 @@ def test_engine_with_winograd_gpu(monkeypatch, depth, alpha, n):
 @pytest.mark.parametrize('case', [(2, 32, 64, 64, 0), (3, 16, 128, 96, 0), (1, 8, 32, 48, 0), (9, 8, 512, 512, 0), (2, 64, 32, 64, 1),
                                   (3, 16, 528, 512, 0), (5, 8, 64, 36, 0), (1, 128, 32, 32, 1), (2, 8, 16, 32, 0),
                                   (2, 32, 8, 16, 0), (3, 16, 16, 16, 0), (1, 64, 24, 32, 1), (2, 16, 8, 40, 1), (1, 128, 16, 32, 0)])
-@pytest.mark.parametrize('gen', [0, 11, 12, 4])
+@pytest.mark.parametrize('gen', [0, 11, 12])
 def test_conv2d_wino_kernel(case, gen):
-    """Every Winograd conv kernel against the torch restatement of the conv contract: gen 0 = the built-in choice (second
-    generation), 11 / 12 = second generation with 16 / 32 couts per workgroup, 4 = the round-1 kernel (pg_debug_set_wino)."""
+    """Every Winograd conv kernel against the torch restatement of the conv contract: gen 0 = the built-in choice,
+    11 / 12 = the tile kernel with 16 / 32 couts per workgroup (pg_debug_set_wino)."""
     lib = pg._lib.load()
-    if gen == 4 and case[2] % 16:
-        pytest.skip('the first-generation kernel stages 16-channel chunks (8-channel layers: second generation only)')
     assert lib.pg_debug_set_wino(gen) == 0
     try:
         _wino_kernel_case(case)
-        want = 'conv_wino_kernel<4>' if gen == 4 else 'conv_wino2_kernel<'
         name = lib.pg_debug_last_wino_kernel().decode()
-        assert name.startswith(want) or (gen == 0 and name.startswith('conv_wino_strip_kernel<')), name
+        assert name.startswith('conv_wino2_kernel<') or (gen == 0 and name.startswith('conv_wino_strip_kernel<')), name
     finally:
         lib.pg_debug_set_wino(0)
 

@@ -124,7 +124,7 @@ def make_table(list_json, counters_csv, out_csv):
     with open(counters_csv) as f:
         for row in csv.DictReader(f):
             name = row['Kernel_Name']
-            if 'conv_wino2_kernel' not in name and 'conv_wino_strip_kernel' not in name and 'conv_wino_kernel' not in name:
+            if 'conv_wino2_kernel' not in name and 'conv_wino_strip_kernel' not in name:
                 continue
             d = per.setdefault(int(row['Dispatch_Id']), dict(name=name, ns=int(row['End_Timestamp']) - int(row['Start_Timestamp'])))
             d[row['Counter_Name']] = d.get(row['Counter_Name'], 0.0) + float(row['Counter_Value'])

@@ -1,6 +1,6 @@
 """Row-streaming conv (csrc/conv_strip.hip) vs the tile kernel it replaces, on the 1024^2 layer shapes of the schedule.
-Interleaved A/B in one process (pg_debug_set_tuning(3, 20) = tile kernel); PG_STRIP_SEG / PG_STRIP_WREG select the
-strip variants (read once per process: run the script once per setting)."""
+Interleaved A/B in one process (pg_debug_set_tuning(3, 20) = tile kernel); other strip variants (segment length, weights in
+LDS) are variant builds: tools/exp/build_variant.sh + PGGAN_HIP_LIB."""
 import os
 import sys
 
@@ -58,7 +58,6 @@ def case(n, ci, co, kind):
         kind, n, ci, co, H, a, fl / a / 1e6, byt / a / 1e6, t, t / a, ka), flush=True)
 
 
-print('PG_STRIP_SEG=%s PG_STRIP_WREG=%s' % (os.environ.get('PG_STRIP_SEG'), os.environ.get('PG_STRIP_WREG')))
 for n in (3, 9):
     for ci, co, kind in ((8, 8, 'fwd'), (8, 8, 'masked'), (8, 8, 'fwd+signs'), (8, 8, 'pn'), (16, 8, 'masked'), (16, 8, 'ups+pn')):
         if kind == 'ups+pn' and n == 9:

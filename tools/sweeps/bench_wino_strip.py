@@ -96,7 +96,6 @@ CASES = [
     # 256^2 stage
     (256, 32, 32, 'fwd+signs'), (256, 32, 32, 'maskb'), (256, 32, 64, 'pool+bytes'), (256, 32, 32, 'pn'), (256, 32, 64, 'maskb+pool'), (256, 32, 32, 'unpool'),
 ]
-print('PG_WSTRIP_WINO_SEG=%s PG_WSTRIP_WINO_NCB=%s' % (os.environ.get('PG_WSTRIP_WINO_SEG'), os.environ.get('PG_WSTRIP_WINO_NCB')))
 for n in (9, 3):
     for H, ci, co, kind in CASES:
         if ONLY and ONLY not in ('%d:%d:%d:%s' % (H, ci, co, kind)):

@@ -24,7 +24,6 @@ def timeit(fn, reps=20):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
-print('PG_WSTRIP_SEG=%s' % os.environ.get('PG_WSTRIP_SEG'))
 for n in (3, 9):
     for ci, co, ups in ((8, 8, 0), (8, 16, 0), (16, 8, 1)):
         if n == 9 and (ci, co) != (8, 8):

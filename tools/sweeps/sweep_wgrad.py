@@ -6,7 +6,7 @@ sys.path.insert(0, ROOT)
 import torch
 import pggan_amd as pg
 ops, lib = pg.ops, pg._lib.load()
-cfgs = [int(v) for v in sys.argv[1:]] or [-1, 1, 2, 3, 4, 5, 6, 7]
+cfgs = [int(v) for v in sys.argv[1:]] or [-1, 1, 3]
 SHAPES = [(9, 16, 512, 512), (3, 16, 512, 512), (9, 32, 256, 512), (3, 32, 256, 256), (9, 64, 128, 256), (3, 64, 128, 128),
           (9, 128, 64, 128), (9, 256, 32, 64), (3, 256, 32, 32), (9, 512, 16, 32), (3, 512, 16, 16), (9, 8, 512, 512), (3, 8, 512, 512),
           (9, 4, 512, 512)]
