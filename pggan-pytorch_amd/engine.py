@@ -26,6 +26,7 @@ import weakref as _weakref
 import torch
 
 from . import ops
+from . import saved
 
 
 # ------------------------------------------------------------------------------------------
@@ -583,12 +584,12 @@ def generator_forward(G, z, save=False, out=None, pair_out=None):
     C = G.num_channels
     b0 = G.block0
     G._ensure_buffers()
-    ctx = dict(N=N, depth=depth, alpha=alpha, recs=[])
+    ctx = saved.GContext(N=N, depth=depth, alpha=alpha, recs=[])
     if G.normalize_latents:
         zn, _ = ops.pixelnorm_fwd(z, G.eps)                                   # :120-123
     else:
         zn = z
-    ctx['zn'] = zn
+    ctx.zn = zn
 
     def layer(x, lay, H, ups=False):
         if lay.pixelnorm:
@@ -605,7 +606,7 @@ def generator_forward(G, z, save=False, out=None, pair_out=None):
 
     y1, r1 = layer(zn.view(N, 1, 1, L), b0.c1, 1)                            # 4x4 conv pad 3 on 1x1
     y2, r2 = layer(y1, b0.c2, 4)
-    ctx.update(y1=y1, r1=r1, y2=y2, r2=r2)
+    ctx.y1, ctx.r1, ctx.y2, ctx.r2 = y1, r1, y2, r2
     def to_rgb(h, t, H, out_mul=1.0, prev=None, prev_mul=0.0):
         if pair_out is None:
             return ops.torgb_fwd(h, t.conv.weight.data, t.conv.bias.data, N, C, H, H, t.c, out_mul=out_mul, prev=prev, prev_mul=prev_mul, out=out)
@@ -633,7 +634,7 @@ def generator_forward(G, z, save=False, out=None, pair_out=None):
                 img = None
         if img is None:
             a2, ra2 = layer(a1, blk.c2, H)
-        ctx['recs'].append(dict(blk=blk, inp=h, a1=a1, r1=ra1, a2=a2, r2=ra2, H=H))
+        ctx.recs.append(saved.GBlock(blk=blk, inp=h, a1=a1, r1=ra1, a2=a2, r2=ra2, H=H))
         hprev, h = h, a2
     if img is not None:
         return (img, ctx) if save else img
@@ -650,7 +651,7 @@ def generator_backward(G, ctx, g_out):
     """Adjoint sweep of generator_forward: accumulates into G's flat gradient buffer."""
     wait_pending(G)
     G._ensure_buffers()
-    N, depth, alpha = ctx['N'], ctx['depth'], ctx['alpha']
+    N, depth, alpha = ctx.N, ctx.depth, ctx.alpha
     C = G.num_channels
     b0 = G.block0
     active = [b0.c1, b0.c2]
@@ -658,57 +659,57 @@ def generator_backward(G, ctx, g_out):
     top_done = False
     if depth == 0:
         t = b0.toRGB
-        with _on_side(g_out, ctx['y2']):
-            ops.torgb_wgrad(g_out, ctx['y2'], t._gw, t._gb, N, C, 4, 4, t.c, 1.0)
+        with _on_side(g_out, ctx.y2):
+            ops.torgb_wgrad(g_out, ctx.y2, t._gw, t._gb, N, C, 4, 4, t.c, 1.0)
         g = ops.torgb_bwd_data(g_out, t.conv.weight.data, N, C, 4, 4, t.c)
         active.append(t)
     else:
-        rec = ctx['recs'][-1]
-        H = rec['H']
-        t = rec['blk'].toRGB
-        with _on_side(g_out, rec['a2']):
-            ops.torgb_wgrad(g_out, rec['a2'], t._gw, t._gb, N, C, H, H, alpha * t.c, alpha)
+        rec = ctx.recs[-1]
+        H = rec.H
+        t = rec.blk.toRGB
+        with _on_side(g_out, rec.a2):
+            ops.torgb_wgrad(g_out, rec.a2, t._gw, t._gb, N, C, H, H, alpha * t.c, alpha)
         # toRGB's adjoint + the adjoint of the top block's last (LeakyReLU -> PixelNorm) in one launch (network.py:138, :44-52)
-        if rec['r2'] is not None:
-            g = ops.torgb_bwd_data_pnbwd(g_out, t.conv.weight.data, rec['a2'], rec['r2'], N, C, H, H, alpha * t.c, rec['blk'].c2.slope)
+        if rec.r2 is not None:
+            g = ops.torgb_bwd_data_pnbwd(g_out, t.conv.weight.data, rec.a2, rec.r2, N, C, H, H, alpha * t.c, rec.blk.c2.slope)
             top_done = True
         else:                                         # (a generator built without PixelNorm: the adjoint is LeakyReLU' alone)
             g = ops.torgb_bwd_data(g_out, t.conv.weight.data, N, C, H, H, alpha * t.c)
         active.append(t)
         if alpha < 1.0:
             pt = G.blocks[depth - 2].toRGB if depth > 1 else b0.toRGB
-            with _on_side(g_out, rec['inp']):
-                ops.torgb_wgrad(g_out, rec['inp'], pt._gw, pt._gb, N, C, H // 2, H // 2, (1 - alpha) * pt.c,
+            with _on_side(g_out, rec.inp):
+                ops.torgb_wgrad(g_out, rec.inp, pt._gw, pt._gb, N, C, H // 2, H // 2, (1 - alpha) * pt.c,
                                 1 - alpha, down=True)
             g_extra = ops.torgb_bwd_data(g_out, pt.conv.weight.data, N, C, H // 2, H // 2, (1 - alpha) * pt.c, down=True)
             active.append(pt)
     _grads_ready(G, active[2:])
-    recs = ctx['recs']
+    recs = ctx.recs
     for k in range(len(recs) - 1, -1, -1):
         rec = recs[k]
-        blk, H = rec['blk'], rec['H']
+        blk, H = rec.blk, rec.H
         c1, c2 = blk.c1, blk.c2
         if top_done:                                  # (the top block's adjoint came with toRGB's)
             gz2, top_done = g, False
         else:
-            gz2 = ops.pixelnorm_lrelu_bwd(g, rec['a2'], rec['r2'], c2.slope, inplace=True)
-        _wgrad(rec['a1'], gz2, c2, N, H)
+            gz2 = ops.pixelnorm_lrelu_bwd(g, rec.a2, rec.r2, c2.slope, inplace=True)
+        _wgrad(rec.a1, gz2, c2, N, H)
         # backward-data conv of c2 + adjoint of c1's (LeakyReLU -> PixelNorm) in one launch
-        gz1 = _dgrad_pnbwd(G, gz2, c2, N, H, rec['a1'], rec['r1'], c1.slope)
-        _wgrad(rec['inp'], gz1, c1, N, H, ups=True)
+        gz1 = _dgrad_pnbwd(G, gz2, c2, N, H, rec.a1, rec.r1, c1.slope)
+        _wgrad(rec.inp, gz1, c1, N, H, ups=True)
         # backward-data conv of c1 + adjoint of the nearest x2 upsample (sum over 2x2 = 4 * average pool, exact in fp32)
         # + the fade-in branch's gradient, all in the conv epilogue
         # ... and, where it fits, the adjoint of the coarser block's last (LeakyReLU -> PixelNorm) as well
-        prev = (recs[k - 1]['a2'], recs[k - 1]['r2'], recs[k - 1]['blk'].c2.slope) if k > 0 else (ctx['y2'], ctx['r2'], b0.c2.slope)
+        prev = (recs[k - 1].a2, recs[k - 1].r2, recs[k - 1].blk.c2.slope) if k > 0 else (ctx.y2, ctx.r2, b0.c2.slope)
         g, top_done = _dgrad_pool(G, gz1, c1, N, H, other=g_extra, a=4.0, b=1.0, pnb=prev)
         g_extra = None
         active += [c1, c2]
         _grads_ready(G, [c1, c2])
-    gz2 = g if top_done else ops.pixelnorm_lrelu_bwd(g, ctx['y2'], ctx['r2'], b0.c2.slope, inplace=True)
-    _wgrad(ctx['y1'], gz2, b0.c2, N, 4)
+    gz2 = g if top_done else ops.pixelnorm_lrelu_bwd(g, ctx.y2, ctx.r2, b0.c2.slope, inplace=True)
+    _wgrad(ctx.y1, gz2, b0.c2, N, 4)
     g1 = _dgrad(G, gz2, b0.c2, N, 4)
-    gz1 = ops.pixelnorm_lrelu_bwd(g1, ctx['y1'], ctx['r1'], b0.c1.slope, inplace=True)
-    _wgrad(ctx['zn'].view(N, 1, 1, -1), gz1, b0.c1, N, 1)
+    gz1 = ops.pixelnorm_lrelu_bwd(g1, ctx.y1, ctx.r1, b0.c1.slope, inplace=True)
+    _wgrad(ctx.zn.view(N, 1, 1, -1), gz1, b0.c1, N, 1)
     _grads_ready(G, [b0.c1, b0.c2])
     return active
 
@@ -754,12 +755,11 @@ def _mbstd_bwd(D, gy, x, stats, cp, apply_mask, mask_slope, tx=None, tstats=None
 def _mbstd_bwd_hvp(D, g_head, g_mixed, rec, hvp, fr_slope):
     """Minibatch-stddev adjoint of the last block ``rec`` under the gradient penalty: the head images take ``g_head``; the mixed images behind
     them (one extra group) take ``g_mixed`` (None: they have no first-order gradient) plus the Hessian-vector injection of ``hvp``."""
-    nh, tx, tstats, gy_first = hvp[:4]
-    inp, stats, cp = rec['inp'], rec['stats'], rec['blk'].c1.cin_store
+    nh, inp, stats, cp = hvp.n_head, rec.inp, rec.stats, rec.blk.c1.cin_store
     gin = torch.empty_like(inp)
     ng = stats.shape[0] - 1
-    _mbstd_bwd(D, g_head, inp[:nh], stats[:ng], cp, rec['first'], fr_slope, out=gin[:nh])
-    _mbstd_bwd(D, g_mixed, inp[nh:], stats[ng:], cp, rec['first'], fr_slope, tx=tx, tstats=tstats, gy_first=gy_first, out=gin[nh:])
+    _mbstd_bwd(D, g_head, inp[:nh], stats[:ng], cp, rec.first, fr_slope, out=gin[:nh])
+    _mbstd_bwd(D, g_mixed, inp[nh:], stats[ng:], cp, rec.first, fr_slope, tx=hvp.tx, tstats=hvp.tstats, gy_first=hvp.gy_first, out=gin[nh:])
     return gin
 
 
@@ -777,7 +777,7 @@ def d_forward(D, x, groups=1, keep_input=True):
     """reference network.py:225-240 on a batch of ``groups`` independent minibatches stacked along
     N (minibatch-stddev is evaluated per group).  Returns (scores [NB], ctx with every activation).
     ``keep_input=False``: the caller will not ask for D's weight gradients (``d_backward(full=False)``) -- the entry block's fromRGB
-    output may stay unmaterialised (``rec['inp']`` is None then; its sign bytes ``rec['inpb']`` are always there)."""
+    output may stay unmaterialised (``rec.inp`` is None then; its sign bytes ``rec.inpb`` are always there)."""
     wait_pending(D)
     D._sync_version()
     NB, C, r, _ = x.shape
@@ -787,7 +787,7 @@ def d_forward(D, x, groups=1, keep_input=True):
     nb = len(D.blocks)
     e = nb - 1 - depth                                                        # blocks[-(depth+1)]  (:227)
     D._ensure_buffers()
-    ctx = dict(NB=NB, groups=groups, depth=depth, alpha=alpha, x=x, recs=[])
+    ctx = saved.DContext(NB=NB, groups=groups, depth=depth, alpha=alpha, x=x, recs=[])
     pn = bool(getattr(D, 'pixelnorm', False))
     fr = D.blocks[e].fromRGB
     sb = USE_SIGN_BYTES and not pn                                            # byte copies of the fp32 activations (masks)
@@ -813,45 +813,40 @@ def d_forward(D, x, groups=1, keep_input=True):
     for k, j in enumerate(range(e, nb)):
         blk = D.blocks[j]
         last = (j == nb - 1)
-        rec = dict(blk=blk, inp=cur, H=H, first=(k == 0), last=last)
-        if k == 0 and curb is not None:
-            rec['inpb'] = curb
+        rec = saved.DBlock(blk=blk, inp=cur, H=H, first=(k == 0), last=last, inpb=curb if k == 0 else None)
         if last:
             mb, stats = _mbstd_fwd(D, cur, groups, blk.c1.cin_store)          # :168
             a1 = _conv(mb, blk.c1, NB, H)
             if pn:
-                a1, rec['r1'] = ops.pixelnorm_fwd(a1, inplace=True)
+                a1, rec.r1 = ops.pixelnorm_fwd(a1, inplace=True)
             a2 = _conv(a1, blk.c2, NB, H)                                     # 4x4 pad 0 -> 1x1
             if pn:
-                a2, rec['r2'] = ops.pixelnorm_fwd(a2, inplace=True)
-            rec.update(mb=mb, stats=stats, a1=a1, a2=a2)
+                a2, rec.r2 = ops.pixelnorm_fwd(a2, inplace=True)
+            rec.mb, rec.stats, rec.a1, rec.a2 = mb, stats, a1, a2
         else:
             if k == 0 and fused is not None:
-                a1, rec['a1b'] = fused
+                a1, rec.a1b = fused
             elif sb and H >= SIGN_BYTES_MIN_H:
-                a1, a1b = _conv(cur, blk.c1, NB, H, signs_out=True)
-                if a1b is not None:
-                    rec['a1b'] = a1b
+                a1, rec.a1b = _conv(cur, blk.c1, NB, H, signs_out=True)
             else:
                 a1 = _conv(cur, blk.c1, NB, H)
             if pn:                                                            # a1/a2 hold the NORMALISED outputs
-                a1, rec['r1'] = ops.pixelnorm_fwd(a1, inplace=True)
+                a1, rec.r1 = ops.pixelnorm_fwd(a1, inplace=True)
             pf = None
             if k == 0 and alpha < 1.0:                                        # :230-233
                 nfr = D.blocks[j + 1].fromRGB
-                pf = ops.fromrgb_fwd(x, nfr.conv.weight.data, nfr.conv.bias.data, NB, C, H // 2, H // 2,
-                                     nfr.c, nfr.slope, pool=True)
-                rec['pf'] = pf
+                pf = rec.pf = ops.fromrgb_fwd(x, nfr.conv.weight.data, nfr.conv.bias.data, NB, C, H // 2, H // 2,
+                                              nfr.c, nfr.slope, pool=True)
             pa, pb = (alpha, 1.0 - alpha) if pf is not None else (1.0, 0.0)
             if pn:
                 a2 = _conv(a1, blk.c2, NB, H)
-                a2, rec['r2'] = ops.pixelnorm_fwd(a2, inplace=True)
+                a2, rec.r2 = ops.pixelnorm_fwd(a2, inplace=True)
                 cur = ops.avgpool2_fwd(a2, pf, pa, pb)                        # :229,238
             else:                                                             # pool (+ fade-in blend) in the conv epilogue
                 a2, cur = _conv_pool(a1, blk.c2, NB, H, other=pf, a=pa, b=pb, y_bytes=USE_SIGN_BYTES and H >= SIGN_BYTES_MIN_H)
-            rec.update(a1=a1, a2=a2)
+            rec.a1, rec.a2 = a1, a2
             H //= 2
-        ctx['recs'].append(rec)
+        ctx.recs.append(rec)
     s = ops.linear1_fwd(a2, D.linear.weight.data, D.linear.bias.data)         # :239
     return s, ctx
 
@@ -884,48 +879,13 @@ def _arena_free(st):
     return tok is None or tok.consumed
 
 
-def _merge_ctx(D, first, rest, x3, N, third):
-    """The context of the whole batch from the contexts of the three passes: every tensor of a pass is a row range of a batched tensor."""
-    def whole(a, *bs):
-        base = a._base if a._base is not None else a
-        if all(b._base is not None and b._base is base for b in bs) and base.shape[0] == a.shape[0] + sum(b.shape[0] for b in bs):
-            return base
-        raise RuntimeError('split D forward: the passes did not write into one tensor')
-    ctx = dict(NB=3 * N, groups=3, depth=first['depth'], alpha=first['alpha'], x=x3, recs=[])
-    others = [rest['recs'], third['recs']]
-    for i, ra in enumerate(first['recs']):
-        rec = {}
-        for k, v in ra.items():
-            rec[k] = whole(v, *[o[i][k] for o in others]) if torch.is_tensor(v) else v
-        ctx['recs'].append(rec)
-    return ctx
-
-
-def _slice_ctx(ctx, a, b, g0, g1):
-    """View of a batched context restricted to images [a,b) == groups [g0,g1)."""
-    sub = dict(NB=b - a, groups=g1 - g0, depth=ctx['depth'], alpha=ctx['alpha'], x=ctx['x'][a:b], recs=[])
-    for rec in ctx['recs']:
-        r2 = dict(rec)
-        for k in ('inp', 'a1', 'a2', 'mb', 'pf', 'inpb', 'a1b'):
-            if k in rec:
-                r2[k] = rec[k][a:b]
-        for k in ('r1', 'r2'):                       # PixelNorm scales, one per pixel: [NB*h*w]
-            if k in rec:
-                per = rec[k].numel() // ctx['NB']
-                r2[k] = rec[k][a * per:b * per]
-        if 'stats' in rec:
-            r2['stats'] = rec['stats'][g0:g1]
-        sub['recs'].append(r2)
-    return sub
-
-
 def _lazy_unpool_ok(rec, save_adjoints):
     """May the pool adjoint behind block ``rec`` stay un-evaluated, for the consumers of the block's c2 gradient to apply in their gathers
     (ops.conv2d_unpooled / conv2d_wgrad_unpooled)?  Needs c2's output as sign bytes and the 8-channel 3x3 layers those kernels are built for."""
-    c2 = rec['blk'].c2
+    c2 = rec.blk.c2
     w = c2.conv.weight.shape
-    return (USE_LAZY_UNPOOL and not save_adjoints and rec['a2'].dtype == torch.uint8 and w[3] == 8 and w[2] in (8, 16)
-            and c2.ksize == 3 and rec['H'] % 32 == 0)
+    return (USE_LAZY_UNPOOL and not save_adjoints and rec.a2.dtype == torch.uint8 and w[3] == 8 and w[2] in (8, 16)
+            and c2.ksize == 3 and rec.H % 32 == 0)
 
 
 def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
@@ -933,23 +893,23 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
 
     gscore [NB] : d loss / d score.   full: also accumulate weight/bias gradients.
     want_gimg   : return d loss / d input image (NCHW).
-    hvp         : (n_head, tx, tstats, gy_first) — the last ``NB-n_head`` images form one extra group
+    hvp         : saved.Hvp — the last ``NB-n_head`` images form one extra group
                   whose score gradient is zero and which only receives the minibatch-stddev
                   Hessian-vector injection; ``gscore`` then has n_head entries."""
     wait_pending(D)
     if getattr(D, 'pixelnorm', False):
         return _d_backward_pn(D, ctx, gscore, full, want_gimg, save_adjoints, hvp)
     D._ensure_buffers()
-    NB, alpha = ctx['NB'], ctx['alpha']
-    x = ctx['x']
+    NB, alpha = ctx.NB, ctx.alpha
+    x = ctx.x
     C = D.num_channels
-    recs = ctx['recs']
-    adj = [dict() for _ in recs]
+    recs = ctx.recs
+    adj = [saved.DAdjoint() for _ in recs] if save_adjoints else None
     lastrec = recs[-1]
-    nh = NB if hvp is None else hvp[0]
-    a2 = lastrec['a2']
-    lc2 = lastrec['blk'].c2
-    tail = _tail_wgrad_on_main(recs[0]['H']) if (full and ASYNC_WGRAD and D._rt.grad_hook is None and len(recs) > 1) else 0
+    nh = NB if hvp is None else hvp.n_head
+    a2 = lastrec.a2
+    lc2 = lastrec.blk.c2
+    tail = _tail_wgrad_on_main(recs[0].H) if (full and ASYNC_WGRAD and D._rt.grad_hook is None and len(recs) > 1) else 0
     if full:
         ops.linear1_wgrad(gscore, a2[:nh], D._lin_gw, D._lin_gb)
     g = ops.linear1_bwd_data(gscore, D.linear.weight.data, a2[:nh], (nh,) + tuple(a2.shape[1:]), lc2.slope)
@@ -959,12 +919,12 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
     carry = None
     for idx in range(len(recs) - 1, -1, -1):
         rec = recs[idx]
-        blk, H = rec['blk'], rec['H']
+        blk, H = rec.blk, rec.H
         c1, c2 = blk.c1, blk.c2
         fr_slope = blk.fromRGB.slope
-        if rec['last']:
+        if rec.last:
             gz2 = g                                                           # [nh,1,1,C]
-            a1, mb, inp = rec['a1'], rec['mb'], rec['inp']
+            a1, mb, inp = rec.a1, rec.mb, rec.inp
             if full:
                 _wgrad(a1[:nh], gz2, c2, nh, H)
             gz1 = _dgrad(D, gz2, c2, nh, 1, mask=a1[:nh], mask_slope=c1.slope)
@@ -973,11 +933,11 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
             gmb = _dgrad(D, gz1, c1, nh, H)                                   # [nh,4,4,CP]
             cp = c1.cin_store
             if hvp is None:
-                gin = _mbstd_bwd(D, gmb, inp, rec['stats'], cp, rec['first'], fr_slope)
+                gin = _mbstd_bwd(D, gmb, inp, rec.stats, cp, rec.first, fr_slope)
             else:
                 gin = _mbstd_bwd_hvp(D, gmb, None, rec, hvp, fr_slope)
             if save_adjoints:
-                adj[idx].update(gz2=gz2, gz1=gz1, gmb=gmb)
+                adj[idx].gz2, adj[idx].gz1, adj[idx].gmb = gz2, gz1, gmb
         else:
             gz2 = g
             if carry is not None:                  # gz2 = pool adjoint of the coarser gradient, evaluated inside the two consumers
@@ -985,45 +945,45 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
                 carry = None
                 try:
                     gz1 = ops.conv2d_unpooled(gc, _wt(D, c2), gb, gmul, gsl, NB, H, H, c2.c,
-                                              mask=rec.get('a1b') if rec.get('a1b') is not None else rec['a1'], mask_slope=c1.slope)
+                                              mask=rec.a1b if rec.a1b is not None else rec.a1, mask_slope=c1.slope)
                     if full:
                         _flush_wgrad(c2)           # (this launch does not go through _wgrad: a deferred tangent term rides nowhere)
-                        with _on_side(rec['a1'], gc, gb):
-                            ops.conv2d_wgrad_unpooled(rec['a1'], gc, gb, gmul, gsl, c2._gw, c2._gb, NB, H, H, c2.c)
+                        with _on_side(rec.a1, gc, gb):
+                            ops.conv2d_wgrad_unpooled(rec.a1, gc, gb, gmul, gsl, c2._gw, c2._gb, NB, H, H, c2.c)
                 except ops.Unsupported:                    # (shape checks are identical for both entry points: nothing was accumulated)
                     FALLBACKS['lazy unpool %dx%d' % (H, H)] += 1
                     gz2 = ops.avgpool2_bwd(gc, _mask32(gb), 4.0 * gmul, gsl)
                     if full:
-                        _wgrad(rec['a1'], gz2, c2, NB, H)
-                    gz1 = _dgrad(D, gz2, c2, NB, H, mask=(rec['a1'], rec.get('a1b')), mask_slope=c1.slope)
+                        _wgrad(rec.a1, gz2, c2, NB, H)
+                    gz1 = _dgrad(D, gz2, c2, NB, H, mask=(rec.a1, rec.a1b), mask_slope=c1.slope)
             else:
                 if full:
-                    _wgrad(rec['a1'], gz2, c2, NB, H)
-                gz1 = _dgrad(D, gz2, c2, NB, H, mask=(rec['a1'], rec.get('a1b')), mask_slope=c1.slope)
+                    _wgrad(rec.a1, gz2, c2, NB, H)
+                gz1 = _dgrad(D, gz2, c2, NB, H, mask=(rec.a1, rec.a1b), mask_slope=c1.slope)
             if full:
-                _wgrad(rec['inp'], gz1, c1, NB, H, on_main=rec['first'] and tail >= 2)
+                _wgrad(rec.inp, gz1, c1, NB, H, on_main=rec.first and tail >= 2)
             g_fused = None
-            if not rec['first'] and not (recs[idx - 1]['first'] and alpha < 1.0):
+            if not rec.first and not (recs[idx - 1].first and alpha < 1.0):
                 pv = recs[idx - 1]
                 if _lazy_unpool_ok(pv, save_adjoints):
                     # plain coarse gradient; the finer block's c2 consumers apply the pool adjoint in their gathers
-                    carry = (_dgrad(D, gz1, c1, NB, H), pv['a2'], 0.25, pv['blk'].c2.slope)
+                    carry = (_dgrad(D, gz1, c1, NB, H), pv.a2, 0.25, pv.blk.c2.slope)
                 else:
                     # backward-data conv + pool adjoint + LeakyReLU' of the finer block's output in one kernel
-                    g_fused = _dgrad_unpool(D, gz1, c1, NB, H, pv['a2'], 1.0, pv['blk'].c2.slope)
+                    g_fused = _dgrad_unpool(D, gz1, c1, NB, H, pv.a2, 1.0, pv.blk.c2.slope)
                 gin = None
             else:
                 gin = None
                 # fromRGB's weight gradient rides in the same epilogue when the sweep asks for weight gradients -- not under a bucketed
                 # gradient exchange, whose flushes wait for the weight-gradient stream only (as the tail launches on the main stream)
                 fw = full and D._rt.grad_hook is None
-                if (rec['first'] and (want_gimg or fw) and rec.get('inpb') is not None and x.is_cuda and c1.ksize == 3 and c1.pad == 1
+                if (rec.first and (want_gimg or fw) and rec.inpb is not None and x.is_cuda and c1.ksize == 3 and c1.pad == 1
                         and _wino(c1, NB, H, c1.conv.weight.shape[3], transposed=True) is None):
                     # the entry block's backward-data conv hands the IMAGE gradient on as well (fromRGB's backward-data in its epilogue); the
                     # 8-channel gradient itself is written only when somebody reads it afterwards (the tangent term of the gradient penalty)
                     fr0 = blk.fromRGB
                     try:
-                        gin, gi = ops.conv2d_masked_fromrgb_bwd(gz1, _wt(D, c1), rec['inpb'], fr_slope, fr0.conv.weight.data, fr0.c, NB, C, H, H, c1.c,
+                        gin, gi = ops.conv2d_masked_fromrgb_bwd(gz1, _wt(D, c1), rec.inpb, fr_slope, fr0.conv.weight.data, fr0.c, NB, C, H, H, c1.c,
                                                                 keep_gf=save_adjoints or (full and not fw), want_gimg=want_gimg,
                                                                 img=x if fw else None, rgb_dw=fr0._gw if fw else None, rgb_db=fr0._gb if fw else None)
                         if want_gimg:
@@ -1032,14 +992,14 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
                     except ops.Unsupported:
                         FALLBACKS['fromRGB adjoint in the epilogue %dx%d' % (H, H)] += 1
                 if not gimg_fused:
-                    gin = _dgrad(D, gz1, c1, NB, H, mask=(rec['inp'], rec.get('inpb')) if rec['first'] else None, mask_slope=fr_slope)
+                    gin = _dgrad(D, gz1, c1, NB, H, mask=(rec.inp, rec.inpb) if rec.first else None, mask_slope=fr_slope)
             if save_adjoints:
-                adj[idx].update(gz2=gz2, gz1=gz1)
-        if rec['first']:
+                adj[idx].gz2, adj[idx].gz1 = gz2, gz1
+        if rec.first:
             gf = gin                                                          # adjoint of fromRGB pre-activation
             fr = blk.fromRGB
             if save_adjoints:
-                adj[idx]['gf'] = gf
+                adj[idx].gf = gf
             if full and not fw_fused:
                 with (_on_main if tail >= 1 else _on_side)(gf, x):
                     ops.fromrgb_wgrad(gf, x, fr._gw, fr._gb, NB, C, H, H, fr.c)
@@ -1053,29 +1013,29 @@ def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
                                          pool=True, accumulate=True)
         else:
             prev = recs[idx - 1]
-            pc2 = prev['blk'].c2
-            if prev['first'] and alpha < 1.0:
+            pc2 = prev.blk.c2
+            if prev.first and alpha < 1.0:
                 if _lazy_unpool_ok(prev, save_adjoints):
                     # fade-in at the 1024^2 stage: the same lazy pool adjoint as in the fully grown stage (x alpha); the entry block's c2
                     # consumers evaluate it in their gathers instead of reading a 604 MB fine-resolution gradient (round 4)
-                    carry = (gin, prev['a2'], 0.25 * alpha, pc2.slope)
+                    carry = (gin, prev.a2, 0.25 * alpha, pc2.slope)
                     g = None
                 else:
-                    g = ops.avgpool2_bwd(gin, _mask32(prev['a2']), alpha, pc2.slope)
+                    g = ops.avgpool2_bwd(gin, _mask32(prev.a2), alpha, pc2.slope)
                 pfr = blk.fromRGB                                             # the block whose fromRGB fed the fade-in
-                gpf = ops.axpby_mask(gin, mask=prev['pf'], a=1.0 - alpha, mask_slope=pfr.slope)
+                gpf = ops.axpby_mask(gin, mask=prev.pf, a=1.0 - alpha, mask_slope=pfr.slope)
                 if save_adjoints:
-                    adj[idx - 1]['gpf'] = gpf
+                    adj[idx - 1].gpf = gpf
                 if full:
                     with _on_side(gpf, x):
                         ops.fromrgb_wgrad(gpf, x, pfr._gw, pfr._gb, NB, C, H, H, pfr.c, pool=True)
                 pending_prev = (gpf, pfr)
-            elif not rec['last'] and g_fused is not None:
+            elif not rec.last and g_fused is not None:
                 g = g_fused
             elif carry is not None:
                 g = None                            # consumed through ``carry`` by the next (finer) block
             else:
-                g = ops.avgpool2_bwd(gin, _mask32(prev['a2']), 1.0, pc2.slope)
+                g = ops.avgpool2_bwd(gin, _mask32(prev.a2), 1.0, pc2.slope)
         if full:
             _grads_ready(D, _d_block_done(D, recs, idx, alpha))
     return gimg, adj
@@ -1085,13 +1045,16 @@ def _d_block_done(D, recs, idx, alpha):
     """Layers whose weight gradients are complete once block ``idx`` of the batched backward sweep has been processed
     (the tangent pass ran before the sweep, so nothing else accumulates into them)."""
     rec = recs[idx]
-    blk = rec['blk']
+    blk = rec.blk
     done = [blk.c1, blk.c2]
-    if rec['last']:
+    if rec.last:
         done.append(D._lin_layer)
-    if rec['first'] or (recs[idx - 1]['first'] and alpha < 1.0):
+    if rec.first or (recs[idx - 1].first and alpha < 1.0):
         done.append(blk.fromRGB)                 # the entry block's fromRGB / the fade-in branch's fromRGB
     return done
+
+
+_NO_INJECTION = saved.PNInjection()
 
 
 def _pn_bwd(gy, y, r, slope, nh, inj):
@@ -1110,17 +1073,17 @@ def _d_backward_pn(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=Non
     """``d_backward`` for Discriminator(pixelnorm=True): every c1/c2 is conv -> LeakyReLU -> PixelNorm
     (network.py:32-41), so the masks can no longer be fused into the backward-data convs; the adjoint of each
     (LeakyReLU, PixelNorm) pair is one ``pixelnorm_lrelu_bwd`` launch.  With ``hvp`` the mixed images [nh:]
-    take the minibatch-stddev AND the per-layer PixelNorm Hessian-vector injections (hvp[4] = list of dicts)."""
+    take the minibatch-stddev AND the per-layer PixelNorm Hessian-vector injections (``hvp.injs``)."""
     D._ensure_buffers()
-    NB, alpha = ctx['NB'], ctx['alpha']
-    x = ctx['x']
+    NB, alpha = ctx.NB, ctx.alpha
+    x = ctx.x
     C = D.num_channels
-    recs = ctx['recs']
-    adj = [dict() for _ in recs]
+    recs = ctx.recs
+    adj = [saved.DAdjoint() for _ in recs] if save_adjoints else None
     lastrec = recs[-1]
-    nh = NB if hvp is None else hvp[0]
-    injs = None if hvp is None else hvp[4]
-    a2 = lastrec['a2']
+    nh = NB if hvp is None else hvp.n_head
+    injs = None if hvp is None else hvp.injs
+    a2 = lastrec.a2
     gtop = ops.linear1_bwd_data(gscore, D.linear.weight.data, None, (nh,) + tuple(a2.shape[1:]))
     if nh < NB:                                      # mixed images: zero score gradient, injections only
         g = torch.empty_like(a2)                     # (C-ABI launches, not ATen ops: a launch plan replays only those)
@@ -1134,43 +1097,43 @@ def _d_backward_pn(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=Non
     pending_prev = None
     for idx in range(len(recs) - 1, -1, -1):
         rec = recs[idx]
-        blk, H = rec['blk'], rec['H']
+        blk, H = rec.blk, rec.H
         c1, c2 = blk.c1, blk.c2
         fr_slope = blk.fromRGB.slope
-        inj = injs[idx] if injs is not None else {}
+        inj = injs[idx] if injs is not None else _NO_INJECTION
         if save_adjoints:
-            adj[idx]['gy2'] = ops.axpby_mask(g, a=1.0)          # device copy through the C-ABI (recorded by a launch plan)
-        gz2 = _pn_bwd(g, rec['a2'], rec['r2'], c2.slope, nh, inj.get('inj2'))
-        Hc2 = 1 if rec['last'] else H
+            adj[idx].gy2 = ops.axpby_mask(g, a=1.0)          # device copy through the C-ABI (recorded by a launch plan)
+        gz2 = _pn_bwd(g, rec.a2, rec.r2, c2.slope, nh, inj.inj2)
+        Hc2 = 1 if rec.last else H
         if full:
-            _wgrad(rec['a1'], gz2, c2, NB, H)
+            _wgrad(rec.a1, gz2, c2, NB, H)
         gy1 = _dgrad(D, gz2, c2, NB, Hc2)
         if save_adjoints:
-            adj[idx]['gy1'] = ops.axpby_mask(gy1, a=1.0)
-        gz1 = _pn_bwd(gy1, rec['a1'], rec['r1'], c1.slope, nh, inj.get('inj1'))
-        if rec['last']:
-            mb, inp = rec['mb'], rec['inp']
+            adj[idx].gy1 = ops.axpby_mask(gy1, a=1.0)
+        gz1 = _pn_bwd(gy1, rec.a1, rec.r1, c1.slope, nh, inj.inj1)
+        if rec.last:
+            mb, inp = rec.mb, rec.inp
             if full:
                 _wgrad(mb, gz1, c1, NB, H)
             gmb = _dgrad(D, gz1, c1, NB, H)                                   # [NB,4,4,CP]
             cp = c1.cin_store
             if hvp is None:
-                gin = _mbstd_bwd(D, gmb, inp, rec['stats'], cp, rec['first'], fr_slope)
+                gin = _mbstd_bwd(D, gmb, inp, rec.stats, cp, rec.first, fr_slope)
             else:
                 gin = _mbstd_bwd_hvp(D, gmb[:nh], gmb[nh:], rec, hvp, fr_slope)
             if save_adjoints:
-                adj[idx].update(gz2=gz2, gz1=gz1, gmb=gmb)
+                adj[idx].gz2, adj[idx].gz1, adj[idx].gmb = gz2, gz1, gmb
         else:
             if full:
-                _wgrad(rec['inp'], gz1, c1, NB, H)
-            gin = _dgrad(D, gz1, c1, NB, H, mask=rec['inp'] if rec['first'] else None, mask_slope=fr_slope)
+                _wgrad(rec.inp, gz1, c1, NB, H)
+            gin = _dgrad(D, gz1, c1, NB, H, mask=rec.inp if rec.first else None, mask_slope=fr_slope)
             if save_adjoints:
-                adj[idx].update(gz2=gz2, gz1=gz1)
-        if rec['first']:
+                adj[idx].gz2, adj[idx].gz1 = gz2, gz1
+        if rec.first:
             gf = gin
             fr = blk.fromRGB
             if save_adjoints:
-                adj[idx]['gf'] = gf
+                adj[idx].gf = gf
             if full:
                 with _on_side(gf, x):
                     ops.fromrgb_wgrad(gf, x, fr._gw, fr._gb, NB, C, H, H, fr.c)
@@ -1183,12 +1146,12 @@ def _d_backward_pn(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=Non
                                          pool=True, accumulate=True)
         else:
             prev = recs[idx - 1]
-            if prev['first'] and alpha < 1.0:
+            if prev.first and alpha < 1.0:
                 g = ops.avgpool2_bwd(gin, None, alpha)                        # adjoint wrt the NORMALISED a2
                 pfr = blk.fromRGB
-                gpf = ops.axpby_mask(gin, mask=prev['pf'], a=1.0 - alpha, mask_slope=pfr.slope)
+                gpf = ops.axpby_mask(gin, mask=prev.pf, a=1.0 - alpha, mask_slope=pfr.slope)
                 if save_adjoints:
-                    adj[idx - 1]['gpf'] = gpf
+                    adj[idx - 1].gpf = gpf
                 if full:
                     with _on_side(gpf, x):
                         ops.fromrgb_wgrad(gpf, x, pfr._gw, pfr._gb, NB, C, H, H, pfr.c, pool=True)
@@ -1203,66 +1166,67 @@ def _d_backward_pn(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=Non
 def d_tangent_wgrad(D, sub, adj, u):
     """Gradient-penalty second-order term, steps (i)+(ii): push the seed ``u`` (NCHW, same shape as the
     mixed batch) through the masked linear maps of D and accumulate, per layer,
-    dW += c * wgrad(tangent_input, first_backward_adjoint).  Returns the minibatch-stddev HVP inputs."""
+    dW += c * wgrad(tangent_input, first_backward_adjoint).  ``adj``: the saved.DAdjoint list of the first backward over ``sub``.
+    Returns the saved.Hvp of the batched sweep (``n_head`` is the caller's to set)."""
     wait_pending(D)
     D._ensure_buffers()
-    N, alpha = sub['NB'], sub['alpha']
+    N, alpha = sub.NB, sub.alpha
     C = D.num_channels
-    recs = sub['recs']
+    recs = sub.recs
     rec0 = recs[0]
-    fr = rec0['blk'].fromRGB
-    H = rec0['H']
-    with _on_side(adj[0]['gf'], u):
-        ops.fromrgb_wgrad(adj[0]['gf'], u, fr._gw, None, N, C, H, H, fr.c)
+    fr = rec0.blk.fromRGB
+    H = rec0.H
+    with _on_side(adj[0].gf, u):
+        ops.fromrgb_wgrad(adj[0].gf, u, fr._gw, None, N, C, H, H, fr.c)
     cur = None
-    if rec0.get('inpb') is not None:
+    if rec0.inpb is not None:
         try:
-            cur = ops.fromrgb_fwd(u, fr.conv.weight.data, None, N, C, H, H, fr.c, 1.0, mask=rec0['inpb'], mask_slope=fr.slope)
+            cur = ops.fromrgb_fwd(u, fr.conv.weight.data, None, N, C, H, H, fr.c, 1.0, mask=rec0.inpb, mask_slope=fr.slope)
         except ops.Unsupported:
             cur = None
     if cur is None:
-        cur = ops.fromrgb_fwd(u, fr.conv.weight.data, None, N, C, H, H, fr.c, 1.0, mask=rec0['inp'], mask_slope=fr.slope)
+        cur = ops.fromrgb_fwd(u, fr.conv.weight.data, None, N, C, H, H, fr.c, 1.0, mask=rec0.inp, mask_slope=fr.slope)
     hvp = None
     t2 = None
     pn = bool(getattr(D, 'pixelnorm', False))
-    injs = [dict() for _ in recs] if pn else None
+    injs = [saved.PNInjection() for _ in recs] if pn else None
     for idx, rec in enumerate(recs):
-        blk, H = rec['blk'], rec['H']
+        blk, H = rec.blk, rec.H
         c1, c2 = blk.c1, blk.c2
-        if rec['last']:
-            tmb, tstats = _mbstd_tangent(D, rec['inp'], cur, rec['stats'], c1.cin_store)
-            hvp = (cur, tstats, adj[idx]['gmb'])
-            _wgrad(tmb, adj[idx]['gz1'], c1, N, H, bias=False, defer=True)
-            t1 = _conv(tmb, c1, N, H, mask=rec['a1'], bias=False)
+        if rec.last:
+            tmb, tstats = _mbstd_tangent(D, rec.inp, cur, rec.stats, c1.cin_store)
+            hvp = saved.Hvp(tx=cur, tstats=tstats, gy_first=adj[idx].gmb, injs=injs)
+            _wgrad(tmb, adj[idx].gz1, c1, N, H, bias=False, defer=True)
+            t1 = _conv(tmb, c1, N, H, mask=rec.a1, bias=False)
             if pn:
-                t1, injs[idx]['inj1'] = ops.pixelnorm_tangent(t1, rec['a1'], rec['r1'], adj[idx]['gy1'])
-            _wgrad(t1, adj[idx]['gz2'], c2, N, H, bias=False, defer=True)
-            t2 = _conv(t1, c2, N, H, mask=rec['a2'], bias=False)
+                t1, injs[idx].inj1 = ops.pixelnorm_tangent(t1, rec.a1, rec.r1, adj[idx].gy1)
+            _wgrad(t1, adj[idx].gz2, c2, N, H, bias=False, defer=True)
+            t2 = _conv(t1, c2, N, H, mask=rec.a2, bias=False)
             if pn:
-                t2, injs[idx]['inj2'] = ops.pixelnorm_tangent(t2, rec['a2'], rec['r2'], adj[idx]['gy2'])
+                t2, injs[idx].inj2 = ops.pixelnorm_tangent(t2, rec.a2, rec.r2, adj[idx].gy2)
         else:
-            _wgrad(cur, adj[idx]['gz1'], c1, N, H, bias=False, defer=True)
-            t1 = _conv(cur, c1, N, H, mask=(rec['a1'], rec.get('a1b')), bias=False)
+            _wgrad(cur, adj[idx].gz1, c1, N, H, bias=False, defer=True)
+            t1 = _conv(cur, c1, N, H, mask=(rec.a1, rec.a1b), bias=False)
             if pn:
-                t1, injs[idx]['inj1'] = ops.pixelnorm_tangent(t1, rec['a1'], rec['r1'], adj[idx]['gy1'])
-            _wgrad(t1, adj[idx]['gz2'], c2, N, H, bias=False, defer=True)
+                t1, injs[idx].inj1 = ops.pixelnorm_tangent(t1, rec.a1, rec.r1, adj[idx].gy1)
+            _wgrad(t1, adj[idx].gz2, c2, N, H, bias=False, defer=True)
             tpf = None
-            if rec['first'] and alpha < 1.0:
-                nfr = recs[idx + 1]['blk'].fromRGB
-                with _on_side(adj[idx]['gpf'], u):
-                    ops.fromrgb_wgrad(adj[idx]['gpf'], u, nfr._gw, None, N, C, H // 2, H // 2, nfr.c, pool=True)
+            if rec.first and alpha < 1.0:
+                nfr = recs[idx + 1].blk.fromRGB
+                with _on_side(adj[idx].gpf, u):
+                    ops.fromrgb_wgrad(adj[idx].gpf, u, nfr._gw, None, N, C, H // 2, H // 2, nfr.c, pool=True)
                 tpf = ops.fromrgb_fwd(u, nfr.conv.weight.data, None, N, C, H // 2, H // 2, nfr.c, 1.0,
-                                      pool=True, mask=rec['pf'], mask_slope=nfr.slope)
+                                      pool=True, mask=rec.pf, mask_slope=nfr.slope)
             pa, pb = (alpha, 1.0 - alpha) if tpf is not None else (1.0, 0.0)
             if pn:
-                t2 = _conv(t1, c2, N, H, mask=rec['a2'], bias=False)
-                t2, injs[idx]['inj2'] = ops.pixelnorm_tangent(t2, rec['a2'], rec['r2'], adj[idx]['gy2'])
+                t2 = _conv(t1, c2, N, H, mask=rec.a2, bias=False)
+                t2, injs[idx].inj2 = ops.pixelnorm_tangent(t2, rec.a2, rec.r2, adj[idx].gy2)
                 cur = ops.avgpool2_fwd(t2, tpf, pa, pb)
             else:                                                 # only the pooled tangent is needed downstream
-                t2, cur = _conv_pool(t1, c2, N, H, bias=False, mask=rec['a2'], other=tpf, a=pa, b=pb, pool_only=True)
+                t2, cur = _conv_pool(t1, c2, N, H, bias=False, mask=rec.a2, other=tpf, a=pa, b=pb, pool_only=True)
     # Linear: d/dw <ones, w . t2> = sum_n t2[n]
     ops.linear1_wgrad(_ones(N, u.device), t2, D._lin_gw, None)
-    return hvp + (injs,) if pn else hvp
+    return hvp
 
 
 def d_active_params(D, depth, alpha):
@@ -1372,7 +1336,7 @@ def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_
         with st.arena.pass_(3):
             s_m, ctx_m = d_forward(D, x3[2 * N:], groups=1)                   # :20
         probe('D.mixed_fwd_end')
-        ctx = _merge_ctx(D, ctx_r, ctx_f, x3, N, third=ctx_m)
+        ctx = saved.DContext.merge([ctx_r, ctx_f, ctx_m])
         s = s_r._base if s_r._base is not None else s_r
     else:
         x3 = torch.empty((3 * N,) + tuple(real.shape[1:]), device=real.device, dtype=torch.float32)
@@ -1380,7 +1344,7 @@ def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_
         d_step_generator(D, G, latents, x3[N:2 * N])                        # :51-52  (no graph kept)
         ops.gp_mix(x3[:N], x3[N:2 * N], mix, out=x3[2 * N:])                  # :19
         s, ctx = d_forward(D, x3, groups=3)                                   # :47,54,20
-    sub = _slice_ctx(ctx, 2 * N, 3 * N, 2, 3)
+    sub = ctx.slice(2 * N, 3 * N, 2, 3)
     gimg, adj = d_backward(D, sub, _ones(N, real.device), full=False, want_gimg=True, save_adjoints=True)  # :25-28
     ss = ops.row_sumsq(gimg)
     gp, u = ops.gp_seed(gimg, ss, iwass_lambda, iwass_target, 1.0 / N)        # :29-31
@@ -1389,11 +1353,10 @@ def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_
         _wait_event(torch.cuda.current_stream(torch._C._cuda_getDevice()), fake_done)
     d_cost, d_real_loss, d_fake_loss, gscore = ops.d_loss(s, gp, N, iwass_epsilon)   # :48,55,62
     probe('D.loss_end')
-    state = dict(D=D, ctx=ctx, sub=sub, adj=adj, u=u, gscore=gscore, N=N, scores=s, gp=gp)
+    state = saved.DLossState(D=D, ctx=ctx, sub=sub, adj=adj, u=u, gscore=gscore, N=N, scores=s, gp=gp)
     if arena_st is not None:
-        tok = state['arena_use'] = _ArenaUse()
-        state['arena_st'] = arena_st
-        arena_st.owner = _weakref.ref(tok)
+        state.arena_use, state.arena_st = _ArenaUse(), arena_st
+        arena_st.owner = _weakref.ref(state.arena_use)
     return d_cost, d_real_loss, d_fake_loss, state
 
 
@@ -1449,23 +1412,6 @@ class EarlyG(object):
     __slots__ = ('fake', 'ctx', 'latents', 'stamp', 'event')
 
 
-def _slice_gctx(ctx, a, b):
-    """Images [a, b) of a generator context (every saved tensor is batch-major: activations [n,h,w,c], PixelNorm scales [n*h*w])."""
-    n = ctx['N']
-
-    def sl(t):
-        if t is None:
-            return None
-        per = t.shape[0] // n
-        return t[a * per:b * per]
-    out = dict(N=b - a, depth=ctx['depth'], alpha=ctx['alpha'], recs=[])
-    for k in ('zn', 'y1', 'r1', 'y2', 'r2'):
-        out[k] = sl(ctx.get(k))
-    for rec in ctx['recs']:
-        out['recs'].append(dict(blk=rec['blk'], H=rec['H'], inp=sl(rec['inp']), a1=sl(rec['a1']), r1=sl(rec['r1']), a2=sl(rec['a2']), r2=sl(rec['r2'])))
-    return out
-
-
 def d_step_generator(D, G, latents, out):
     """The D step's generator pass G(z) -> ``out`` (wgan_gp_loss.py:51-52, no graph kept).  EARLY_G_MODE 'batched': when Trainer has
     announced the G step's latents z' (``request_early_g``) the two passes run as ONE pass over [z | z'] -- the same weights, twice the
@@ -1483,7 +1429,7 @@ def d_step_generator(D, G, latents, out):
     eg = EarlyG()
     eg.fake = torch.empty_like(out)
     (img, _), ctx = generator_forward(G, z2, save=True, pair_out=(out, eg.fake))
-    eg.ctx = _slice_gctx(ctx, N, 2 * N)
+    eg.ctx = ctx.slice(N, 2 * N)
     eg.event = torch.cuda.Event()
     _record_event(eg.event, torch.cuda.current_stream(torch._C._cuda_getDevice()))
     eg.latents = zg
@@ -1513,10 +1459,9 @@ def _early_g_on_side(D, main, side):
         _record_event(eg.event, side)
         probe('D.early_g_end')
     # allocated under the second stream's context, consumed (and eventually freed) on the main stream
-    for t in [eg.fake, eg.ctx['zn'], eg.ctx['y1'], eg.ctx['y2'], eg.ctx.get('r1'), eg.ctx.get('r2')] + \
-            [r[k] for r in eg.ctx['recs'] for k in ('a1', 'a2', 'r1', 'r2')]:
-        if torch.is_tensor(t):
-            t.record_stream(main)
+    eg.fake.record_stream(main)
+    for t in saved.tensors(eg.ctx):
+        t.record_stream(main)
     eg.latents = z
     eg.stamp = (G._param_version, int(G.depth), float(G.alpha))
     G._rt.early_fwd = eg
@@ -1539,11 +1484,11 @@ def take_early_g(G, latents):
 
 def d_loss_backward(state, scale=1.0):
     """``D_cost.backward()`` (trainer.py:98): tangent pass + batched [real|fake|mixed] adjoint sweep."""
-    D, ctx, N = state['D'], state['ctx'], state['N']
+    D, ctx, N = state.D, state.ctx, state.N
     D._ensure_buffers()
-    tok = state.get('arena_use')
+    tok = state.arena_use
     if tok is not None:
-        if state['arena_st'].owner() is not tok:     # (second line of defence: a retained loss back-propagated again after a later forward)
+        if state.arena_st.owner() is not tok:     # (second line of defence: a retained loss back-propagated again after a later forward)
             raise RuntimeError('the activations of this D loss were overwritten by a later D-loss forward on the same network')
         tok.consumed = True
     ops.zero_(D._flat_grad)
@@ -1551,10 +1496,10 @@ def d_loss_backward(state, scale=1.0):
         D._rt.grad_hook = None                   # the gradients are rescaled after the sweep: nothing may travel early
     for lay in _live_conv_layers(D):             # (nothing of an aborted earlier step may ride along)
         lay._pending_wgrad = None
-    hvp = d_tangent_wgrad(D, state['sub'], state['adj'], state['u'])
+    hvp = d_tangent_wgrad(D, state.sub, state.adj, state.u)
     probe('D.tangent_end')
-    gs = state['gscore'][:2 * N]
-    d_backward(D, ctx, gs, full=True, want_gimg=False, hvp=(2 * N,) + hvp)
+    hvp.n_head = 2 * N                           # [real | fake] take the score gradients, the mixed third the injections only
+    d_backward(D, ctx, state.gscore[:2 * N], full=True, want_gimg=False, hvp=hvp)
     for lay in _live_conv_layers(D):             # (a deferred tangent contribution that no launch of the sweep carried)
         _flush_wgrad(lay)
     probe('D.sweep_end')
@@ -1568,7 +1513,7 @@ def d_loss_backward(state, scale=1.0):
     #  weight-gradient launches of the 1024^2 layers)
     if scale != 1.0:
         ops.axpby_mask(D._flat_grad, a=scale, out=D._flat_grad)
-    _assign_grads(D, d_active_params(D, ctx['depth'], ctx['alpha']), linear=True)
+    _assign_grads(D, d_active_params(D, ctx.depth, ctx.alpha), linear=True)
 
 
 def g_loss_forward(G, D, latents):
@@ -1587,20 +1532,20 @@ def g_loss_forward(G, D, latents):
     s, dctx = d_forward(D, fake, 1, keep_input=False)
     g_cost, gscore = ops.g_loss(s)
     probe('G.d_fwd_end')
-    return g_cost, dict(G=G, D=D, gctx=gctx, dctx=dctx, gscore=gscore)
+    return g_cost, saved.GLossState(G=G, D=D, gctx=gctx, dctx=dctx, gscore=gscore)
 
 
 def g_loss_backward(state, scale=1.0):
     """``G_cost.backward()`` (trainer.py:111).  D's weight gradients, which the reference computes here
     and throws away at its next D.zero_grad(), are not computed."""
-    G, D = state['G'], state['D']
+    G, D = state.G, state.D
     G._ensure_buffers()
     ops.zero_(G._flat_grad)
     if scale != 1.0:
         G._rt.grad_hook = None
-    gimg, _ = d_backward(D, state['dctx'], state['gscore'], full=False, want_gimg=True)
+    gimg, _ = d_backward(D, state.dctx, state.gscore, full=False, want_gimg=True)
     probe('G.d_bwd_end')
-    active = generator_backward(G, state['gctx'], gimg)
+    active = generator_backward(G, state.gctx, gimg)
     probe('G.g_bwd_end')
     if PROBES is not None and ASYNC_WGRAD and G._flat_param.is_cuda:
         with torch.cuda.stream(_side_stream()):
@@ -1609,4 +1554,4 @@ def g_loss_backward(state, scale=1.0):
     if scale != 1.0:
         ops.axpby_mask(G._flat_grad, a=scale, out=G._flat_grad)
     _assign_grads(G, active)
-    state['active_g'] = active
+    state.active_g = active

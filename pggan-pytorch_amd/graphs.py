@@ -80,7 +80,7 @@ def g_step(G, D, latents):
         def body():
             c, state = engine.g_loss_forward(G, D, g.static_in[0])
             engine.g_loss_backward(state)
-            return c, state['active_g']
+            return c, state.active_g
         if g.warm < 2:
             g.warm += 1
             return body()[0]

@@ -99,11 +99,11 @@ def require_gpu():
 
 
 # ------------------------------------------------------------------------------------ output allocation
-# engine.d_forward can run as TWO passes over disjoint image ranges that must leave their outputs in ONE set of batched tensors (the
-# real third of a D step's [real | fake | mixed] batch is evaluated ahead of the other two thirds): inside an ``Arena`` context the
-# forward ops below take their outputs from the arena instead of the allocator.  The first pass (leading extent n) creates every buffer
-# with leading extent 3n and gets rows [0, n); the second pass (leading extent 2n) walks the same buffers in the same order and gets rows
-# [n, 3n).  Buffers are kept for the next iteration (the launch plans bake their addresses).  Outside a context: torch.empty.
+# The D step evaluates the real, fake and mixed thirds of its [real | fake | mixed] batch as THREE passes of engine.d_forward (on two
+# streams) that must leave their outputs in ONE set of batched tensors: inside an ``Arena`` context the forward ops below take their
+# outputs from the arena instead of the allocator.  The first pass (part 0, leading extent n) creates every buffer with leading extent 3n
+# and gets rows [0, n); the passes of the fake and the mixed third (parts 2 and 3) walk the same buffers in the same order and get rows
+# [n, 2n) and [2n, 3n).  Buffers are kept for the next iteration (the launch plans bake their addresses).  Outside a context: torch.empty.
 _ARENA = None
 
 
@@ -209,7 +209,6 @@ def wino_transform_weights_batched(flat_w, flat_u, layers, transposed=False):
     """layers: [(w element offset in flat_w, u element offset in flat_u, cout, cin), ...]; one launch.  ``transposed``: every
     layer is the backward-data form of a forward layer, computed straight from that layer's parameter (cout / cin are those of
     the backward-data conv, i.e. the forward layer's cin / cout)."""
-    import ctypes
     n = len(layers)
     if n == 0:
         return
@@ -419,7 +418,6 @@ def pack_dgrad_weights(w, wt):
 
 def pack_dgrad_weights_batched(flat_w, flat_wt, layers):
     """layers: [(element offset, ks, cout, cin), ...] inside the flat weight buffer / its mirror; one launch."""
-    import ctypes
     n = len(layers)
     off = (ctypes.c_int64 * n)(*[l[0] for l in layers])
     ks = (ctypes.c_int * n)(*[l[1] for l in layers])

@@ -301,7 +301,7 @@ def g_step(G, D, latents):
     def body():
         c, state = engine.g_loss_forward(G, D, g.static_in[0])
         engine.g_loss_backward(state)
-        return c, state['active_g']
+        return c, state.active_g
     if g.entries is None:
         if g.warm < 2:
             g.warm += 1

@@ -441,3 +441,189 @@ def test_snapshot_with_loose_schedule_attributes_loads():
     lay2 = type(lay).__new__(type(lay))
     lay2.__setstate__(lstate)
     assert '_wt_ver' not in vars(lay2) and lay2._wt_wanted is False and lay2._wino_wanted is False and lay2._pending_wgrad is None
+
+
+# ---- saved-activation records (saved.py) ----------------------------------------------------------------------------------------------
+def _record_classes():
+    S = pg.saved
+    return [c for c in vars(S).values() if isinstance(c, type) and issubclass(c, S._Record) and c is not S._Record]
+
+
+def _walk(rec):
+    """``rec`` and every record it holds (directly or in a list)."""
+    yield rec
+    for f in rec.__slots__:
+        v = getattr(rec, f)
+        for r in (v if isinstance(v, list) else [v]):
+            if isinstance(r, pg.saved._Record):
+                for q in _walk(r):
+                    yield q
+
+
+def _pn_fade_in_nets():
+    """The flags16 configuration with a PixelNorm discriminator (the fixture itself holds no such case: no reference values are needed
+    here), at the fixture's fade-in stage."""
+    meta, _ = load_fixture('flags16')
+    torch.manual_seed(5)
+    G, D = build_flag_nets(meta, dict(g={}, d={'pixelnorm': True}))
+    G.depth = D.depth = 2
+    G.alpha = D.alpha = 0.45
+    return G, D
+
+
+def test_saved_records_are_closed_and_every_tensor_slot_has_a_layout(emu, monkeypatch):
+    S = pg.saved
+    classes = _record_classes()
+    assert len(classes) == 9
+    for cls in classes:
+        assert set(cls.LAYOUT) == set(cls.__slots__) and len(cls.__slots__) == len(cls.LAYOUT), cls      # one table, every field in it
+        assert set(cls.LAYOUT.values()) <= {S.IMG, S.PIX, S.GRP, S.EACH, None}, cls
+        rec = cls()
+        assert not hasattr(rec, '__dict__') and all(getattr(rec, f) is None for f in cls.__slots__)
+        with pytest.raises(AttributeError):
+            rec.undeclared = 1
+        with pytest.raises(AttributeError):
+            cls(undeclared=1)
+    # what a D step and a G step really store: PixelNorm discriminator while fading in (adjoints, injections, pf, r1 / r2) and the default
+    # network with sign bytes (inpb, a1b, byte a2)
+    hvps = []
+    tangent = pg.engine.d_tangent_wgrad
+    monkeypatch.setattr(pg.engine, 'd_tangent_wgrad', lambda *a: hvps.append(tangent(*a)) or hvps[-1])
+    monkeypatch.setattr(pg.engine, 'SIGN_BYTES_MIN_H', 8)
+    meta, _ = load_fixture('tiny32')
+    G2, D2 = build_nets(meta)
+    G2.depth = D2.depth = 3
+    states = []
+    for (G, D), res, latent in ((_pn_fade_in_nets(), 16, 32), ((G2, D2), 32, meta['cfg']['latent_size'])):
+        real, z_d, z_g, mix = synthetic(7, 2, 3, res, latent)
+        _, _, _, st = pg.engine.d_loss_forward(D, G, real, z_d, mix.view(-1), 10.0, 0.001, 1.0)
+        pg.engine.d_loss_backward(st)
+        _, gst = pg.engine.g_loss_forward(G, D, z_g)
+        pg.engine.g_loss_backward(gst)
+        states += [st, gst]
+    assert len(hvps) == 2 and hvps[0].injs is not None and hvps[0].n_head == 4
+    seen, tensor_fields = set(), set()
+    for top in states + hvps:
+        for rec in _walk(top):
+            seen.add(type(rec))
+            for f in rec.__slots__:                       # the SLOTS, not the table: a tensor in an undeclared-layout slot fails
+                if torch.is_tensor(getattr(rec, f)):
+                    assert type(rec).LAYOUT[f] in (S.IMG, S.PIX, S.GRP), (type(rec).__name__, f)
+                    tensor_fields.add((type(rec).__name__, f))
+    assert seen == set(classes)
+    for f in ('inpb', 'a1b', 'pf', 'r1', 'r2', 'mb', 'stats'):
+        assert ('DBlock', f) in tensor_fields, f
+    for f in S.DAdjoint.__slots__ + S.PNInjection.__slots__ + ('tx', 'tstats', 'gy_first'):
+        assert any(name == f for _, name in tensor_fields), f
+
+
+def _assert_row_range(full, sub, n, a, b, g0, g1):
+    """Every declared tensor of ``sub`` (and of its block records) is exactly rows [a, b) / groups [g0, g1) of the one in ``full``."""
+    S = pg.saved
+    checked = set()
+    for rf, rs in zip(_walk(full), _walk(sub)):
+        assert type(rf) is type(rs)
+        for f in rs.__slots__:
+            o, s = getattr(rf, f), getattr(rs, f)
+            layout = type(rs).LAYOUT[f]
+            if not torch.is_tensor(o):
+                assert not torch.is_tensor(s) and (layout in (None, S.EACH) or (o is None and s is None)), f
+                continue
+            if layout == S.GRP:
+                lo, hi = g0, g1
+                assert o.shape[0] == full.groups
+            else:
+                assert layout in (S.IMG, S.PIX) and o.shape[0] % n == 0 and (layout == S.PIX or o.shape[0] == n), (f, tuple(o.shape))
+                per = o.shape[0] // n
+                lo, hi = a * per, b * per
+            want = o[lo:hi]
+            assert s.shape == want.shape and s.shape[0] == hi - lo < o.shape[0], (f, tuple(s.shape))     # nothing left at full extent
+            assert s.untyped_storage().data_ptr() == o.untyped_storage().data_ptr(), f
+            assert s.data_ptr() == want.data_ptr() and s.stride() == want.stride() and s.dtype == o.dtype, f
+            checked.add(f)
+    return checked
+
+
+def _d_context(config, monkeypatch, n=2):
+    if config == 'pixelnorm-fade-in':
+        _, D = _pn_fade_in_nets()
+        res, covers = 16, {'r1', 'r2', 'pf'}
+    else:
+        meta, _ = load_fixture('tiny32')
+        _, D = build_nets(meta)
+        if config == 'sign-bytes':
+            monkeypatch.setattr(pg.engine, 'SIGN_BYTES_MIN_H', 8)          # (as tests/test_winograd.py::test_engine_with_sign_bytes_host)
+            monkeypatch.setattr(pg.engine, 'USE_SIGN_BYTES', True)
+            D.depth, res, covers = 3, 32, {'inpb', 'a1b', 'a2'}
+        else:
+            D.depth, res, covers = 0, 4, {'mb', 'stats'}
+    torch.manual_seed(3)
+    x = torch.rand(3 * n, 3, res, res) * 2 - 1
+    _, ctx = pg.engine.d_forward(D, x, groups=3)
+    if config == 'sign-bytes':
+        assert ctx.recs[0].a2.dtype == torch.uint8 and ctx.recs[0].inpb.dtype == torch.uint8 and ctx.recs[0].a1b.dtype == torch.uint8
+    if config == 'last-block':
+        assert len(ctx.recs) == 1 and ctx.recs[0].last
+    return D, x, ctx, covers
+
+
+D_SLICE_CONFIGS = ['pixelnorm-fade-in', 'sign-bytes', 'last-block']
+
+
+@pytest.mark.parametrize('config', D_SLICE_CONFIGS)
+def test_d_context_slice_is_the_row_range_of_every_declared_tensor(emu, monkeypatch, config):
+    n = 2
+    _, _, ctx, covers = _d_context(config, monkeypatch, n)
+    sub = ctx.slice(2 * n, 3 * n, 2, 3)
+    assert (sub.NB, sub.groups, sub.depth, sub.alpha) == (n, 1, ctx.depth, ctx.alpha) and (ctx.NB, ctx.groups) == (3 * n, 3)
+    checked = _assert_row_range(ctx, sub, 3 * n, 2 * n, 3 * n, 2, 3)
+    assert covers | {'x', 'inp', 'a1', 'a2'} <= checked, checked
+    for rf, rs in zip(ctx.recs, sub.recs):
+        assert (rs.blk, rs.H, rs.first, rs.last) == (rf.blk, rf.H, rf.first, rf.last)
+
+
+@pytest.mark.parametrize('config', D_SLICE_CONFIGS)
+def test_d_context_merge_round_trip(emu, monkeypatch, config):
+    n = 2
+    D, x, ctx, _ = _d_context(config, monkeypatch, n)
+    for rec in _walk(ctx):                                   # an emulated op may hand out a view of a temporary (PixelNorm's scales); the
+        for f in rec.__slots__:                              # device ops and the arena hand out tensors that own their rows
+            if torch.is_tensor(getattr(rec, f)) and getattr(rec, f)._base is not None:
+                setattr(rec, f, getattr(rec, f).clone())
+    parts = [ctx.slice(g * n, (g + 1) * n, g, g + 1) for g in range(3)]
+    whole = pg.saved.DContext.merge(parts)
+    assert (whole.NB, whole.groups, whole.depth, whole.alpha) == (ctx.NB, ctx.groups, ctx.depth, ctx.alpha)
+    count = 0
+    for rf, rw in zip(_walk(ctx), _walk(whole)):
+        for f in rf.__slots__:
+            o, w = getattr(rf, f), getattr(rw, f)
+            if torch.is_tensor(o):
+                assert w is o, f                              # the original tensors themselves
+                count += 1
+            elif not isinstance(o, list):
+                assert w is o or w == o, f
+    assert count >= 4
+    # slices of DIFFERENT base tensors (a second pass over the same images) are not one batch
+    _, other = pg.engine.d_forward(D, x, groups=3)
+    with pytest.raises(RuntimeError, match='did not write into one tensor'):
+        pg.saved.DContext.merge([parts[0], other.slice(n, 2 * n, 1, 2), parts[2]])
+    with pytest.raises(RuntimeError, match='did not write into one tensor'):
+        pg.saved.DContext.merge(parts[:2])                   # (two thirds do not cover the base tensors)
+
+
+def test_g_context_slice_is_the_row_range_of_every_declared_tensor(emu):
+    """The batched early generator pass: one pass over [z | z'], the second half is left for the G step."""
+    meta, _ = load_fixture('tiny32')
+    G, _ = build_nets(meta)
+    G.depth, n = 2, 3
+    torch.manual_seed(4)
+    z2 = torch.randn(2 * n, meta['cfg']['latent_size'])
+    _, ctx = pg.engine.generator_forward(G, z2, save=True)
+    sub = ctx.slice(n, 2 * n)
+    assert (sub.N, sub.depth, sub.alpha, len(sub.recs)) == (n, 2, ctx.alpha, 2) and ctx.N == 2 * n
+    checked = _assert_row_range(ctx, sub, 2 * n, n, 2 * n, None, None)
+    assert checked == {'zn', 'y1', 'r1', 'y2', 'r2', 'inp', 'a1', 'a2'}
+    assert sub.recs[0].blk is ctx.recs[0].blk and sub.recs[1].H == ctx.recs[1].H == 16
+    # enumeration for the cross-stream hand-over: each distinct tensor object once (a block's inp IS the coarser output)
+    ts = list(pg.saved.tensors(ctx))
+    assert len(ts) == len(set(id(t) for t in ts)) == 5 + 4 * 2 and ctx.recs[0].inp is ctx.y2 and ctx.recs[1].inp is ctx.recs[0].a2

@@ -49,25 +49,25 @@ def _d_signs(ctx, a, b, ch_last):
     """Sign patterns of images [a, b) of a batched D pass in the oracle's call order (network.py:225-240): entry block
     fromRGB, c1, c2, (fade-in: the next block's fromRGB), then c1, c2 of every further block."""
     out = []
-    for k, rec in enumerate(ctx['recs']):
+    for k, rec in enumerate(ctx.recs):
         if k == 0:
-            out.append(_nchw((rec['inp'] if rec['inp'] is not None else rec['inpb'])[a:b]))      # (the G step's pass keeps fromRGB's sign bytes only)
-        a1 = _nchw(rec['a1'][a:b])
+            out.append(_nchw((rec.inp if rec.inp is not None else rec.inpb)[a:b]))      # (the G step's pass keeps fromRGB's sign bytes only)
+        a1 = _nchw(rec.a1[a:b])
         out.append(a1)
-        a2 = rec['a2'][a:b]
+        a2 = rec.a2[a:b]
         out.append(_nchw(a2) if a2.dim() == 4 and a2.shape[1] == a2.shape[2] and a2.shape[1] > 1 else
                    (pg.ops.signbytes_to_mask(a2) if a2.dtype == torch.uint8 else a2).reshape(b - a, -1, 1, 1).cpu())
-        if k == 0 and 'pf' in rec:
-            out.append(_nchw(rec['pf'][a:b]))
+        if k == 0 and rec.pf is not None:
+            out.append(_nchw(rec.pf[a:b]))
     return out
 
 
 def _g_signs(gctx):
     """Sign patterns of a G pass (network.py:118-139): block0.c1, block0.c2, then c1, c2 of every block (toRGB has no
     activation).  The saved tensors are the PixelNorm outputs: same signs as the LeakyReLU inputs."""
-    out = [_nchw(gctx['y1']), _nchw(gctx['y2'])]
-    for rec in gctx['recs']:
-        out += [_nchw(rec['a1']), _nchw(rec['a2'])]
+    out = [_nchw(gctx.y1), _nchw(gctx.y2)]
+    for rec in gctx.recs:
+        out += [_nchw(rec.a1), _nchw(rec.a2)]
     return out
 
 
@@ -99,8 +99,8 @@ def _run(oracle, G, D, gp, dp, cfg, real, z_d, z_g, mix, depth, alpha, what):
     gp64, dp64 = _double(gp), _double(dp)
     # ---- D step (wgan_gp_D_loss + backward), on the fake / interpolated images and the activation branches of the HIP pass
     d_cost, _, _, state = eng.d_loss_forward(D, G, real.to(DEV), z_d.to(DEV), mix.to(DEV), 10.0, 0.001, 1.0)
-    ctx = state['ctx']
-    fake, mixed = ctx['x'][n:2 * n].cpu(), ctx['x'][2 * n:].cpu()
+    ctx = state.ctx
+    fake, mixed = ctx.x[n:2 * n].cpu(), ctx.x[2 * n:].cpu()
     signs = _d_signs(ctx, 0, n, True) + _d_signs(ctx, n, 2 * n, True) + _d_signs(ctx, 2 * n, 3 * n, True)
     eng.d_loss_backward(state)
     mine_d = reference_grads(D)
@@ -115,7 +115,7 @@ def _run(oracle, G, D, gp, dp, cfg, real, z_d, z_g, mix, depth, alpha, what):
     _adjudicate(mine_d, r32['grads'], r64['grads'], what + ' D step')
     # ---- G step (wgan_gp_G_loss + backward) on the branches of the HIP pass (G's and D's)
     g_cost, gstate = eng.g_loss_forward(G, D, z_g.to(DEV))
-    signs = _g_signs(gstate['gctx']) + _d_signs(gstate['dctx'], 0, n, True)
+    signs = _g_signs(gstate.gctx) + _d_signs(gstate.dctx, 0, n, True)
     eng.g_loss_backward(gstate)
     mine_g = reference_grads(G)
     with oracle.forced_signs(signs):

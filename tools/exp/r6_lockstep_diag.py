@@ -34,10 +34,10 @@ def signs(t):
 
 def collect(ctx):
     out = {}
-    for k, rec in enumerate(ctx['recs']):
+    for k, rec in enumerate(ctx.recs):
         for name in ('inp', 'a1', 'a2'):
-            if name in rec and torch.is_tensor(rec[name]):
-                out['blk%d.%s@%d' % (k, name, rec['H'])] = signs(rec[name]).clone()
+            if getattr(rec, name) is not None:
+                out['blk%d.%s@%d' % (k, name, rec.H)] = signs(getattr(rec, name)).clone()
     return out
 
 
@@ -73,7 +73,7 @@ def main():
             for G, D, opt in ((Ga, Da, oa), (Gb, Db, ob)):
                 D.zero_grad()
                 c, _, _, state = eng.d_loss_forward(D, G, real, z, mix, 10.0, 0.001, 1.0)
-                sg = collect(state['ctx'])
+                sg = collect(state.ctx)
                 eng.d_loss_backward(state)
                 res.append((float(c), D._flat_grad.clone(), sg))
                 opt.step()

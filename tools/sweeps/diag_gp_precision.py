@@ -22,26 +22,26 @@ dbl = lambda p: {k: (v.double() if torch.is_tensor(v) else float(v)) for k, v in
 r32 = oc.d_loss_and_grads(dp, gp, cfg, real, z_d, mix, depth, alpha)
 r64 = oc.d_loss_and_grads(dbl(dp), dbl(gp), cfg, real.double(), z_d.double(), mix.double(), depth, alpha)
 norm = lambda gpv: 1.0 + torch.sqrt(gpv.double() / 10.0)          # |g| = 1 +- sqrt(gp / lambda): sign resolved below
-print('gp   HIP ', st['gp'].cpu().double().tolist())
+print('gp   HIP ', st.gp.cpu().double().tolist())
 print('gp   fp32', r32['gp'].double().tolist())
 print('gp   fp64', r64['gp'].tolist())
-print('rel err of gp: HIP %.2e  fp32 %.2e' % (float(((st['gp'].cpu().double() - r64['gp']) / r64['gp']).abs().max()),
+print('rel err of gp: HIP %.2e  fp32 %.2e' % (float(((st.gp.cpu().double() - r64['gp']) / r64['gp']).abs().max()),
                                                float(((r32['gp'].double() - r64['gp']) / r64['gp']).abs().max())))
 print('|g| - 1 (from gp, unsigned): ', torch.sqrt(r64['gp'] / 10.0).tolist())
-sc = st['scores'].cpu().double()
+sc = st.scores.cpu().double()
 print('scores HIP', sc.tolist())
 print('scores rel err vs fp64 (real, fake): HIP %.2e %.2e | fp32 %.2e %.2e' % (
     float(((sc[:n] - r64['D_real'].reshape(-1)) / r64['D_real'].reshape(-1)).abs().max()),
     float(((sc[n:2 * n] - r64['D_fake'].reshape(-1)) / r64['D_fake'].reshape(-1)).abs().max()),
     float(((r32['D_real'].double() - r64['D_real']) / r64['D_real']).abs().max()),
     float(((r32['D_fake'].double() - r64['D_fake']) / r64['D_fake']).abs().max())))
-fk = st['ctx']['x'][n:2 * n].cpu().double()
+fk = st.ctx.x[n:2 * n].cpu().double()
 print('fake image rel L2 err vs fp64: HIP %.2e  fp32 %.2e' % (float((fk - r64['fake']).norm() / r64['fake'].norm()),
                                                               float((r32['fake'].double() - r64['fake']).norm() / r64['fake'].norm())))
 
 # ---- the input gradient of the penalty term itself: HIP first backward vs fp64 autograd
 ops, eng = pg.ops, pg.engine
-sub = st['sub']
+sub = st.sub
 gimg, adj = eng.d_backward(D, sub, eng._ones(n, 'cuda'), full=False, want_gimg=True, save_adjoints=True)
 ss = ops.row_sumsq(gimg)
 torch.cuda.synchronize()
@@ -58,5 +58,5 @@ for i in range(n):
     print('sample %d: |g| fp64 %.9e  HIP %.9e (rel %.2e)  fp32 %.9e (rel %.2e);  sqrt(ss) HIP %.9e;  elementwise rel-L2 HIP %.2e fp32 %.2e' % (
         i, float(g64[i].norm()), float(gh[i].norm()), float(gh[i].norm() / g64[i].norm() - 1), float(g32[i].norm()), float(g32[i].norm() / g64[i].norm() - 1),
         float(ss[i].sqrt()), float((gh[i] - g64[i]).norm() / g64[i].norm()), float((g32[i] - g64[i]).norm() / g64[i].norm())))
-mh = st['ctx']['x'][2 * n:].cpu().double()
+mh = st.ctx.x[2 * n:].cpu().double()
 print('mixed input rel-L2 err vs fp64: HIP %.2e' % float((mh - mixed.detach()).norm() / mixed.detach().norm()))
