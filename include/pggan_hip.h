@@ -451,6 +451,42 @@ int pg_minmax_f32(const float* x, int64_t n, float* lohi, pg_stream_t stream);
 int pg_stretch_to_u8(const float* x, uint8_t* out, int64_t n, const float* lohi, float max_out, pg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sliced Wasserstein distance between Laplacian-pyramid patch descriptors of two image sets (Karras et al. 2018, "Progressive
+ * growing of GANs", section 5): the quality metric of a run.  The reference has none; the definition is the published one
+ * (restated for the CPU in tests/swd_ref.py).  Images are fp32 [planes][S][S], S a power of two.
+ *   pg_lap_down:   out[y][x] = sum_{dy,dx} k[dy][dx] in[r(2y+dy-2)][r(2x+dx-2)],  k = outer(f,f), f = [1,4,6,4,1]/16,
+ *                  r() = reflection without the edge sample (d c b | a b c d | c b a).  in [planes][S][S] -> out [planes][S/2][S/2].
+ *   pg_lap_up_sub: out = fine - up(coarse), up() = the same convolution with 4k of the coarse map zero-inserted at the even
+ *                  positions of an SxS map (never formed: only the taps on a non-zero sample are evaluated).  fine, out
+ *                  [planes][S][S], coarse [planes][S/2][S/2].
+ *   pg_swd_gather: descriptor j < ndesc = the 3x7x7 neighbourhood of image j / P of level [ndesc/P][3][S][S] around
+ *                  (x, y) = centres[j] (int32 [ndesc][2], each in [3, S-4]; clamped to it), written as row row_offset + j of
+ *                  out [out_rows][PG_SWD_DESC] in (channel, dy, dx) order.
+ *   pg_swd_channel_stats: stats[0..2] = mean, stats[3..5] = population standard deviation of each channel over all M rows of
+ *                  desc [M][PG_SWD_DESC]; fp64 per-workgroup partials (partials: PG_SWD_REDUCE_BLOCKS * 6 doubles of scratch)
+ *                  summed by one workgroup -- no atomics.   pg_swd_normalize: desc = (desc - mean) / std in place.
+ *   pg_swd_project: out [K][M] = (desc [M][PG_SWD_DESC] x dirs [PG_SWD_DESC][K]) transposed, on v_mfma_f32_32x32x2_f32.
+ *   pg_swd_sort_rows: sorts each of the K rows of buf [K][M] ascending in place, 1 <= M <= PG_SWD_SORT_MAX_M.  Rows of up
+ *                  to PG_SWD_SORT_RUN elements are sorted in LDS by one workgroup; longer rows as runs of that length followed
+ *                  by merge passes between buf and tmp [K][M] (tmp may be NULL for M <= PG_SWD_SORT_RUN).  -0.0 orders before
+ *                  +0.0; NaN is out of contract.
+ *   pg_swd_l1:     out[0] = mean |a[i] - b[i]|, i < n, fp64 partials (partials: PG_SWD_REDUCE_BLOCKS doubles of scratch). */
+#define PG_SWD_DESC 147
+#define PG_SWD_REDUCE_BLOCKS 1024
+#define PG_SWD_SORT_RUN 8192
+#define PG_SWD_SORT_MERGE_TILE 2048
+#define PG_SWD_SORT_MAX_M (1 << 22)
+int pg_lap_down(const float* in, float* out, int64_t planes, int S, pg_stream_t stream);
+int pg_lap_up_sub(const float* fine, const float* coarse, float* out, int64_t planes, int S, pg_stream_t stream);
+int pg_swd_gather(const float* level, const int32_t* centres, float* out, int64_t ndesc, int P, int S,
+                  int64_t row_offset, int64_t out_rows, pg_stream_t stream);
+int pg_swd_channel_stats(const float* desc, int64_t M, double* partials, float* stats, pg_stream_t stream);
+int pg_swd_normalize(float* desc, int64_t M, const float* stats, pg_stream_t stream);
+int pg_swd_project(const float* desc, const float* dirs, float* out, int64_t M, int K, pg_stream_t stream);
+int pg_swd_sort_rows(float* buf, float* tmp, int K, int64_t M, pg_stream_t stream);
+int pg_swd_l1(const float* a, const float* b, int64_t n, double* partials, float* out, pg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Gradient exchange of the data-parallel step: RCCL over xGMI (SURVEY.md §8b "the all-reduce itself is a C-ABI call
  * taking ncclComm_t, buffer, count, stream", §8e).  The reference is single-GPU and has no collective; the exchange
  * points are after `D_loss.backward()` trainer.py:98 (before optimizer_d.step() :100) and after `G_loss.backward()`

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PGGAN_HIP_LIB') or os.path.join(_HERE, 'libpggan_hip.so')   # env override: kernel A/B experiments
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 class PgganLibraryError(RuntimeError):
@@ -91,6 +91,15 @@ SIGNATURES = {
     'pg_mono_f32': [P, L, I, P, L, P],
     'pg_minmax_f32': [P, L, P, P],
     'pg_stretch_to_u8': [P, P, L, P, F, P],
+    # sliced Wasserstein distance (csrc/swd.hip)
+    'pg_lap_down': [P, P, L, I, P],
+    'pg_lap_up_sub': [P, P, P, L, I, P],
+    'pg_swd_gather': [P, P, P, L, I, I, L, L, P],
+    'pg_swd_channel_stats': [P, L, P, P, P],
+    'pg_swd_normalize': [P, L, P, P],
+    'pg_swd_project': [P, P, P, L, I, P],
+    'pg_swd_sort_rows': [P, P, I, L, P],
+    'pg_swd_l1': [P, P, L, P, P, P],
     # gradient exchange (RCCL bound at run time inside the library)
     'pg_rccl_version': [P],
     'pg_comm_unique_id': [P],

@@ -1,0 +1,131 @@
+"""Quality metrics of a training run, evaluated on the device.
+
+``SlicedWasserstein``: the sliced Wasserstein distance between Laplacian-pyramid patch descriptors of real and generated images
+(Karras et al. 2018, "Progressive growing of GANs", section 5), one value per pyramid level -- the one metric of the paper that needs
+no pretrained network.  The reference has no metric; the definition is the published one:
+
+1. Laplacian pyramid of every image, levels ``R, R/2, ..., 16`` (``ops.lap_pyramid``);
+2. per level, ``patches_per_image`` 3x7x7 neighbourhoods of every image as rows of 147 floats (``ops.swd_gather``);
+3. per set and level, every channel normalised to zero mean and unit population standard deviation (``ops.swd_normalize_``);
+4. ``dir_repeats`` times: project both sets on ``dirs_per_repeat`` unit directions, sort every projection, take the mean absolute
+   difference of the sorted values (``ops.swd_project`` / ``swd_sort_rows_`` / ``swd_l1``); the value is the average x 1000.
+
+All randomness (patch centres, directions) comes from the object's own seeded CPU generator: the trainer's random stream is not touched
+and the same seed gives the same metric.  The two sets use the SAME patch centres (image i of one set is sampled where image i of the
+other is), so a set measured against itself gives exactly 0."""
+import torch
+
+from . import ops
+
+
+def swd_levels(resolution):
+    """Pyramid level sizes of a ``resolution`` x ``resolution`` image: resolution, resolution / 2, ..., 16."""
+    resolution = int(resolution)
+    if resolution < 16 or resolution & (resolution - 1):
+        raise ValueError('resolution must be a power of two >= 16, got %r' % (resolution,))
+    levels = []
+    while resolution >= 16:
+        levels.append(resolution)
+        resolution //= 2
+    return levels
+
+
+class SlicedWasserstein(object):
+    """Feed ``num_images`` real and as many generated fp32 ``[n,3,R,R]`` device batches (any split), then ``result()``.
+
+    ``centres``: list (one per level) of int32 CPU tensors ``[num_images * patches_per_image, 2]`` of (x, y);
+    ``directions``: fp32 CPU tensor ``[dir_repeats, 147, dirs_per_repeat]`` with unit columns.
+    ``phase_hook``: measurement aid (tools/swd_time.py), None by default; when set, ``hook(phase, fn, *args, **kw) -> fn(*args, **kw)``
+    runs every ``ops`` call of an evaluation, ``phase`` one of ``PHASES``."""
+
+    PHASES = ('pyramid', 'gather', 'normalise', 'project', 'sort', 'l1')
+
+    def __init__(self, resolution, num_images, patches_per_image=128, dir_repeats=4, dirs_per_repeat=128, seed=0, num_channels=3,
+                 device=None):
+        self.levels = swd_levels(resolution)
+        if int(num_channels) != 3:
+            raise ValueError('the descriptors are 3x7x7: single-channel (or any non-RGB) networks are out of contract')
+        for name, v in (('num_images', num_images), ('patches_per_image', patches_per_image), ('dir_repeats', dir_repeats),
+                        ('dirs_per_repeat', dirs_per_repeat)):
+            if int(v) != v or v < 1:
+                raise ValueError('%s must be a positive integer, got %r' % (name, v))
+        self.resolution, self.num_images, self.patches = int(resolution), int(num_images), int(patches_per_image)
+        self.dir_repeats, self.dirs_per_repeat, self.seed = int(dir_repeats), int(dirs_per_repeat), int(seed)
+        self.rows = self.num_images * self.patches
+        if self.rows > ops.SWD_SORT_MAX_M:
+            raise ValueError('num_images * patches_per_image = %d descriptors per level; the sort takes at most %d'
+                             % (self.rows, ops.SWD_SORT_MAX_M))
+        gen = torch.Generator(device='cpu')
+        gen.manual_seed(self.seed)
+        self.centres = [torch.randint(3, s - 3, (self.rows, 2), generator=gen, dtype=torch.int32) for s in self.levels]
+        for c, s in zip(self.centres, self.levels):              # checked here, on the host, once: _feed gathers with check_range=False
+            if int(c.min()) < 3 or int(c.max()) > s - 4:
+                raise ValueError('patch centres outside [3, %d] at level %d' % (s - 4, s))
+        d = torch.randn(self.dir_repeats, ops.SWD_DESC, self.dirs_per_repeat, generator=gen, dtype=torch.float32).double()
+        self.directions = (d / d.pow(2).sum(dim=1, keepdim=True).sqrt()).float().contiguous()
+        ops.require_gpu()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        dev = self.device
+        self._centres_dev = [c.to(dev) for c in self.centres]
+        self._dirs_dev = self.directions.to(dev)
+        self._desc = {which: [torch.empty((self.rows, ops.SWD_DESC), device=dev, dtype=torch.float32) for _ in self.levels]
+                      for which in ('real', 'fake')}
+        # work buffers of ONE repeat: the two projected sets and the scratch of the merge passes
+        shape = (self.dirs_per_repeat, self.rows)
+        self._proj = [torch.empty(shape, device=dev, dtype=torch.float32) for _ in range(2)]
+        self._tmp = torch.empty(shape, device=dev, dtype=torch.float32) if self.rows > ops.SWD_SORT_LDS_ROW else None
+        self.phase_hook = None
+        self.reset()
+
+    def _op(self, phase, fn, *args, **kw):
+        return fn(*args, **kw) if self.phase_hook is None else self.phase_hook(phase, fn, *args, **kw)
+
+    def reset(self):
+        """Forget what was fed: the buffers are reused for the next evaluation."""
+        self._fed = {'real': 0, 'fake': 0}
+        self._result = None
+
+    def _feed(self, which, batch):
+        if not torch.is_tensor(batch) or batch.dim() != 4 or tuple(batch.shape[1:]) != (3, self.resolution, self.resolution):
+            raise ValueError('expected a batch [n,3,%d,%d], got %s' % (self.resolution, self.resolution,
+                                                                       tuple(batch.shape) if torch.is_tensor(batch) else type(batch)))
+        n, fed = batch.shape[0], self._fed[which]
+        if n < 1 or fed + n > self.num_images:
+            raise ValueError('%d %s images fed, %d more would exceed num_images = %d' % (fed, which, n, self.num_images))
+        if self._result is not None:
+            raise RuntimeError('result() was taken: reset() before feeding again')
+        P = self.patches
+        for li, level in enumerate(self._op('pyramid', ops.lap_pyramid, batch)):
+            self._op('gather', ops.swd_gather, level, self._centres_dev[li][fed * P:(fed + n) * P], P, self._desc[which][li], fed * P,
+                     check_range=False)
+        self._fed[which] = fed + n
+
+    def feed_real(self, batch):
+        self._feed('real', batch)
+
+    def feed_fake(self, batch):
+        self._feed('fake', batch)
+
+    @property
+    def complete(self):
+        return self._fed['real'] == self.num_images and self._fed['fake'] == self.num_images
+
+    def result(self):
+        """{'levels': [R, R/2, ..., 16], 'swd': [one value per level, x 1000], 'mean': their mean}.  One device synchronisation."""
+        if self._result is None:
+            if not self.complete:
+                raise RuntimeError('fed %d real and %d fake images of %d' % (self._fed['real'], self._fed['fake'], self.num_images))
+            dists = []
+            for li in range(len(self.levels)):
+                real, fake = self._desc['real'][li], self._desc['fake'][li]
+                self._op('normalise', ops.swd_normalize_, real)
+                self._op('normalise', ops.swd_normalize_, fake)
+                for r in range(self.dir_repeats):
+                    for desc, proj in ((real, self._proj[0]), (fake, self._proj[1])):
+                        self._op('project', ops.swd_project, desc, self._dirs_dev[r], out=proj)
+                        self._op('sort', ops.swd_sort_rows_, proj, self._tmp)
+                    dists.append(self._op('l1', ops.swd_l1, self._proj[0], self._proj[1]))
+            d = torch.stack(dists).cpu().double().view(len(self.levels), self.dir_repeats)
+            swd = [float(v) for v in (d.mean(dim=1) * 1e3)]
+            self._result = {'levels': list(self.levels), 'swd': swd, 'mean': sum(swd) / len(swd)}
+        return self._result

@@ -777,3 +777,128 @@ def pyramid_level_u8(batch_u8, depthdiff, range_in=(0, 255)):
     _lib.call('pg_pyramid_level_u8', x.data_ptr(), out.data_ptr(), x.numel() // (H * W), H, W, int(depthdiff),
               float(range_in[0]), float(range_in[1]), _stream())
     return out
+
+
+# ------------------------------------------------------------------------- sliced Wasserstein distance (csrc/swd.hip)
+SWD_DESC = 147                     # PG_SWD_DESC: 3 channels x 7 x 7
+SWD_REDUCE_BLOCKS = 1024           # PG_SWD_REDUCE_BLOCKS
+SWD_SORT_LDS_ROW = 8192            # PG_SWD_SORT_RUN: the longest row one workgroup sorts in LDS ...
+SWD_SORT_MERGE_RUN = 8192          # ... and the run length the global merge of a longer row starts from
+SWD_SORT_MERGE_TILE = 2048         # PG_SWD_SORT_MERGE_TILE: outputs per workgroup of a merge pass
+SWD_SORT_MAX_M = 1 << 22           # PG_SWD_SORT_MAX_M
+
+
+def _f32_dev(t, what, ndim=None):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError('%s: expected a contiguous float32 device tensor' % what)
+    if ndim is not None and t.dim() != ndim:
+        raise ValueError('%s: expected %d dimensions, got shape %s' % (what, ndim, tuple(t.shape)))
+    return t
+
+
+def lap_pyramid(x, min_size=16):
+    """fp32 device batch [N,3,S,S] (S a power of two >= 16) -> Laplacian pyramid [S, S/2, ..., 16] (pg_lap_down / pg_lap_up_sub):
+    level i = g_i - up(g_{i+1}), the last level is the Gaussian level itself."""
+    _f32_dev(x, 'lap_pyramid', 4)
+    N, C, S, W = x.shape
+    if S != W or S < min_size or (S & (S - 1)) or N < 1 or C < 1:
+        raise ValueError('lap_pyramid: expected [N,C,S,S] with S a power of two >= %d, got %s' % (min_size, tuple(x.shape)))
+    s = _stream()
+    gauss = [x]
+    while gauss[-1].shape[-1] > min_size:
+        g = gauss[-1]
+        h = g.shape[-1] // 2
+        out = torch.empty((N, C, h, h), device=x.device, dtype=torch.float32)
+        _lib.call('pg_lap_down', _p(g), _p(out), N * C, g.shape[-1], s)
+        gauss.append(out)
+    levels = []
+    for fine, coarse in zip(gauss[:-1], gauss[1:]):
+        out = torch.empty_like(fine)
+        _lib.call('pg_lap_up_sub', _p(fine), _p(coarse), _p(out), N * C, fine.shape[-1], s)
+        levels.append(out)
+    levels.append(gauss[-1])
+    return levels
+
+
+def swd_gather(level, centres, P, out, row_offset, check_range=True):
+    """Rows ``row_offset .. row_offset + N*P`` of ``out`` [M,147] <- the 3x7x7 neighbourhoods of ``level`` [N,3,S,S] around
+    ``centres`` (int32 device [N*P,2] of (x, y) in [3, S-4]); descriptor j belongs to image j // P.  A centre outside that range is
+    a ValueError; the check reads the centres back (one synchronisation), so a caller that has validated them on the host, as
+    ``metrics.SlicedWasserstein`` does where it draws them, passes ``check_range=False``."""
+    _f32_dev(level, 'swd_gather level', 4)
+    _f32_dev(out, 'swd_gather out', 2)
+    N, C, S, W = level.shape
+    P, row_offset = int(P), int(row_offset)
+    if N < 1 or C != 3 or S != W or S < 7:
+        raise ValueError('swd_gather: expected a level [N,3,S,S] with N >= 1 and S >= 7, got %s' % (tuple(level.shape),))
+    if not torch.is_tensor(centres) or not centres.is_cuda or centres.dtype != torch.int32 or not centres.is_contiguous() \
+            or P < 1 or tuple(centres.shape) != (N * P, 2):
+        raise ValueError('swd_gather: expected contiguous int32 device centres [%d,2]' % (N * P))
+    if out.shape[1] != SWD_DESC or row_offset < 0 or row_offset + N * P > out.shape[0]:
+        raise ValueError('swd_gather: rows %d..%d do not fit out %s' % (row_offset, row_offset + N * P, tuple(out.shape)))
+    if check_range:
+        lo, hi = int(centres.min()), int(centres.max())
+        if lo < 3 or hi > S - 4:
+            raise ValueError('swd_gather: centres span %d..%d, outside [3, %d] of a %dx%d level' % (lo, hi, S - 4, S, S))
+    _lib.call('pg_swd_gather', _p(level), centres.data_ptr(), _p(out), N * P, P, S, row_offset, out.shape[0], _stream())
+    return out
+
+
+def _swd_partials(device, per_block=1):
+    return torch.empty(SWD_REDUCE_BLOCKS * per_block, device=device, dtype=torch.float64)
+
+
+def swd_normalize_(desc):
+    """In place: per channel, subtract the mean and divide by the population standard deviation over all rows of ``desc`` [M,147]."""
+    _f32_dev(desc, 'swd_normalize_', 2)
+    if desc.shape[1] != SWD_DESC or desc.shape[0] < 1:
+        raise ValueError('swd_normalize_: expected [M,147] with M >= 1, got %s' % (tuple(desc.shape),))
+    s = _stream()
+    partials = _swd_partials(desc.device, 6)
+    stats = torch.empty(6, device=desc.device, dtype=torch.float32)
+    _lib.call('pg_swd_channel_stats', _p(desc), desc.shape[0], partials.data_ptr(), _p(stats), s)
+    _lib.call('pg_swd_normalize', _p(desc), desc.shape[0], _p(stats), s)
+    return desc
+
+
+def swd_project(desc, dirs, out=None):
+    """``desc`` [M,147] x ``dirs`` [147,K] -> [K,M]: every direction's projections are one contiguous row."""
+    _f32_dev(desc, 'swd_project desc', 2)
+    _f32_dev(dirs, 'swd_project dirs', 2)
+    M, K = desc.shape[0], dirs.shape[1]
+    if desc.shape[1] != SWD_DESC or dirs.shape[0] != SWD_DESC or M < 1 or K < 1:
+        raise ValueError('swd_project: expected [M,147] and [147,K], got %s and %s' % (tuple(desc.shape), tuple(dirs.shape)))
+    if out is None:
+        out = torch.empty((K, M), device=desc.device, dtype=torch.float32)
+    elif tuple(_f32_dev(out, 'swd_project out', 2).shape) != (K, M):
+        raise ValueError('swd_project: out must be [%d,%d]' % (K, M))
+    _lib.call('pg_swd_project', _p(desc), _p(dirs), _p(out), M, K, _stream())
+    return out
+
+
+def swd_sort_rows_(buf, tmp=None):
+    """Sort every row of ``buf`` [K,M] ascending, in place.  Rows longer than SWD_SORT_LDS_ROW need a scratch of buf's shape
+    (``tmp``; allocated when not given)."""
+    _f32_dev(buf, 'swd_sort_rows_', 2)
+    K, M = buf.shape
+    if K < 1 or K > 65535 or M < 1 or M > SWD_SORT_MAX_M:
+        raise ValueError('swd_sort_rows_: expected [K,M] with 1 <= K <= 65535 and 1 <= M <= 2^22, got %s' % (tuple(buf.shape),))
+    if M > SWD_SORT_LDS_ROW:
+        if tmp is None:
+            tmp = torch.empty_like(buf)
+        elif _f32_dev(tmp, 'swd_sort_rows_ tmp').numel() < buf.numel() or tmp.data_ptr() == buf.data_ptr():
+            raise ValueError('swd_sort_rows_: tmp must be a separate buffer of at least %d floats' % buf.numel())
+    _lib.call('pg_swd_sort_rows', _p(buf), _p(tmp) if M > SWD_SORT_LDS_ROW else None, K, M, _stream())
+    return buf
+
+
+def swd_l1(a, b):
+    """mean |a - b| over two equal-shaped fp32 device tensors -> 0-dim device tensor."""
+    _f32_dev(a, 'swd_l1 a')
+    _f32_dev(b, 'swd_l1 b')
+    if a.shape != b.shape or a.numel() < 1:
+        raise ValueError('swd_l1: expected two equal, non-empty shapes, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    partials = _swd_partials(a.device)
+    out = torch.empty((), device=a.device, dtype=torch.float32)
+    _lib.call('pg_swd_l1', _p(a), _p(b), a.numel(), partials.data_ptr(), _p(out), _stream())
+    return out

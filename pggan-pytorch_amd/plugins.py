@@ -284,3 +284,61 @@ class OutputGenerator(Plugin):
 
     def end(self, *args):
         self.epoch(*args)
+
+
+class SWDMonitor(Plugin):
+    """Quality metric per tick (``metrics.SlicedWasserstein``; the reference reports none): every ``swd_ticks`` ticks and at the end,
+    ``num_images`` real images from ``real_batch_fn(n)`` (fp32 device batches ``[n,3,R,R]`` at the current stage's resolution, e.g.
+    ``utils.prepare_real_batch`` of a dataset batch) are measured against as many of ``G.forward(sample_fn(n).cuda())``, ``minibatch``
+    at a time.  Writes ``stats['swd']`` (the mean over the pyramid levels, x 1000) and one ``stats['swd_<res>']`` per level under the
+    stat-dict convention of the other monitors.  Stages below 16x16 have no pyramid level: nothing is written there.  Rank 0
+    evaluates (replicas are identical).  ``metric_kwargs`` go to ``SlicedWasserstein`` (patches_per_image, dir_repeats,
+    dirs_per_repeat, seed).  One metric object (buffers, patch centres, directions) is alive at a time: a new stage drops the last
+    stage's before it allocates its own (about 20 GB at the default size and 1024x1024).
+
+    The default period rests on an ESTIMATE, not on a measurement (docs/experiments_swd.md; no evaluation has been timed on the
+    device yet): 10-15 s per evaluation of 16384 images at the 1024x1024 stage, most of it the generator passes and the real
+    batches.  Under 1 % of that stage's time (a tick of 1 kimg is about 3.3 s there) then needs 300-450 ticks between evaluations:
+    400.  A run that wants the metric more often trades images for it (``num_images=2048, swd_ticks=50`` costs the same by the
+    same estimate and is noisier)."""
+
+    def __init__(self, real_batch_fn, sample_fn, num_images=16384, minibatch=16, swd_ticks=400, **metric_kwargs):
+        super(SWDMonitor, self).__init__([(swd_ticks, 'epoch'), (1, 'end')])
+        if int(num_images) < 1 or int(minibatch) < 1:
+            raise ValueError('num_images and minibatch must be positive')
+        self.real_batch_fn, self.sample_fn = real_batch_fn, sample_fn
+        self.num_images, self.minibatch = int(num_images), int(minibatch)
+        self.metric_kwargs = metric_kwargs
+        self._metric_obj = None
+
+    def register(self, trainer):
+        self.trainer = trainer
+
+    def _metric(self, resolution):
+        if self._metric_obj is None or self._metric_obj.resolution != resolution:
+            from .metrics import SlicedWasserstein
+            self._metric_obj = None                                      # a new stage: free the last one's buffers before allocating
+            self._metric_obj = SlicedWasserstein(resolution, self.num_images, **self.metric_kwargs)
+        return self._metric_obj
+
+    def epoch(self, epoch_index):
+        tr = self.trainer
+        if tr.parallel is not None and tr.parallel.rank != 0:
+            return
+        resolution = 4 * 2 ** tr.G.depth
+        if resolution < 16:
+            return
+        metric = self._metric(resolution)
+        metric.reset()
+        for start in range(0, self.num_images, self.minibatch):
+            n = min(self.minibatch, self.num_images - start)
+            metric.feed_real(self.real_batch_fn(n))
+            metric.feed_fake(tr.G.forward(self.sample_fn(n).cuda()))
+        res = metric.result()
+        tr.stats['swd'] = dict(log_name='swd', log_epoch_fields=['{val:.3f}'], val=res['mean'])
+        for size, value in zip(res['levels'], res['swd']):
+            name = 'swd_%d' % size
+            tr.stats[name] = dict(log_name=name, log_epoch_fields=['{val:.3f}'], val=value)
+
+    def end(self, *args):
+        self.epoch(*args)
