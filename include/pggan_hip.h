@@ -409,6 +409,14 @@ int pg_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, f
             float eps, float bc1, float bc2_sqrt, float grad_scale, pg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Smoothed generator Gs (Karras et al. 2018, "Training configuration"; the reference has none): exponential running average of
+ * a flat parameter segment, in the lerp form (not beta*avg + (1-beta)*p), each of its two operations rounded once:
+ *   avg[i] = fma(1 - beta, p[i] - avg[i], avg[i])
+ * beta in [0, 1] (PG_E_ARG otherwise, NaN included); beta == 1 leaves avg bit-identical.  avg and p: 16-byte aligned (PG_E_ALIGN),
+ * the ranges [avg, avg+n) and [p, p+n) must not overlap (PG_E_ARG).  p is only read.                              */
+int pg_ema_f32(float* avg, const float* p, int64_t n, float beta, pg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Steps either side of the path.
  * Real-image input: replaces DepthDataset.__getitem__ dataset.py:54-67 (alpha_fade :109-113 when alpha < 1,
  * adjust_dynamic_range utils.py:24-30, astype float32) for a whole uint8 batch on the device:

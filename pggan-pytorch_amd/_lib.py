@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PGGAN_HIP_LIB') or os.path.join(_HERE, 'libpggan_hip.so')   # env override: kernel A/B experiments
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 class PgganLibraryError(RuntimeError):
@@ -81,6 +81,7 @@ SIGNATURES = {
     'pg_d_loss': [P, P, P, P, P, P, I, F, P],
     'pg_g_loss': [P, P, P, I, P],
     'pg_adam': [P, P, P, P, L, F, F, F, F, F, F, F, P],
+    'pg_ema_f32': [P, P, L, F, P],
     'pg_real_prepare_u8': [P, P, L, I, I, D, D, D, D, D, P],
     'pg_image_grid_u8': [P, P, I, I, I, I, I, F, F, P],
     'pg_pyramid_level_u8': [P, P, L, I, I, I, F, F, P],

@@ -1,6 +1,6 @@
 // HBM-streaming and small-reduction kernels of the PGGAN hot path: pooling / upsample adjoint,
 // fade-in blends, PixelNorm, minibatch-stddev (forward, adjoint, tangent, Hessian-vector term),
-// the final Linear(nf0,1), WGAN-GP mixing / norms / seeds, loss algebra and Adam.
+// the final Linear(nf0,1), WGAN-GP mixing / norms / seeds, loss algebra, Adam and the weight average of the smoothed generator.
 // All are float4-vectorised, grid-stride, with wavefront (64-lane) shuffle reductions.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -628,6 +628,31 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 #undef ADAM1
 }
 
+// ---------------------------------------------------------------------------------------- smoothed generator (Gs)
+// avg += (1 - beta) * (p - avg), Karras et al. 2018: one rounding of the difference and one of the fma, spelled out so that the result does
+// not depend on what the compiler contracts.  Three streams of this bandwidth-bound kernel (Adam above: six); same launch shape.
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ avg, const float* __restrict__ p, size_t n, float omb)
+{
+    const size_t n4 = n >> 2;
+    float4* a4 = reinterpret_cast<float4*>(avg);
+    const float4* p4 = reinterpret_cast<const float4*>(p);
+#define EMA1(A, P) A = __fmaf_rn(omb, __fsub_rn(P, A), A);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        float4 aa = a4[i]; const float4 pp = p4[i];
+        EMA1(aa.x, pp.x) EMA1(aa.y, pp.y) EMA1(aa.z, pp.z) EMA1(aa.w, pp.w)
+        a4[i] = aa;
+    }
+    // tail (n not a multiple of 4)
+    const size_t tail0 = n4 << 2;
+    if (blockIdx.x == 0 && threadIdx.x < (n - tail0)) {
+        const size_t i = tail0 + threadIdx.x;
+        float aa = avg[i];
+        EMA1(aa, p[i])
+        avg[i] = aa;
+    }
+#undef EMA1
+}
+
 }  // namespace
 
 #define LAUNCH(kern, grid, block, smem, stream, ...) \
@@ -652,7 +677,7 @@ extern "C" int pg_signbytes_to_mask(const unsigned char* bytes, float* mask, int
     return (int)hipGetLastError();
 }
 
-extern "C" int pg_abi_version(void) { return 26; }
+extern "C" int pg_abi_version(void) { return 27; }
 
 extern "C" int pg_avgpool2_fwd(const float* x, const float* other, float* y, int N, int H, int W, int C,
                                float a, float b, pg_stream_t stream)
@@ -912,6 +937,16 @@ extern "C" int pg_adam(float* p, const float* g, float* m, float* v, int64_t n, 
     }
     LAUNCH(adam_kernel<false>, dim3(grid_for(((size_t)n + 3) >> 2, 256, 2048)), dim3(256), 0, stream, p, g, m, v, (size_t)n,
            lr / bc1, beta1, beta2, eps, 1.f / bc2_sqrt, grad_scale);
+}
+
+extern "C" int pg_ema_f32(float* avg, const float* p, int64_t n, float beta, pg_stream_t stream)
+{
+    if (!avg || !p || n <= 0 || !(beta >= 0.f && beta <= 1.f)) return PG_E_ARG;       // (the negated form also refuses a NaN)
+    if (((uintptr_t)avg | (uintptr_t)p) & 15) return PG_E_ALIGN;
+    if ((uintptr_t)avg < (uintptr_t)(p + n) && (uintptr_t)p < (uintptr_t)(avg + n)) return PG_E_ARG;      // overlapping ranges
+    const float omb = 1.f - beta;
+    if (omb == 0.f) return 0;                    // beta == 1: avg stays as it is, bit for bit (an fma would turn a -0 into +0)
+    LAUNCH(ema_kernel, dim3(grid_for(((size_t)n + 3) >> 2, 256, 2048)), dim3(256), 0, stream, avg, p, (size_t)n, omb);
 }
 
 // U[0,1) draws for the gradient-penalty mixing factors (reference wgan_gp_loss.py:15-17: torch.cuda.FloatTensor(n, 1).uniform_()).

@@ -696,6 +696,13 @@ def adam(p, g, m, v, lr, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale=1.0):
     _lib.call('pg_adam', _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, _stream())
 
 
+def ema(avg, p, beta):
+    """avg += (1 - beta) * (p - avg) over two flat fp32 device tensors of one length (pg_ema_f32: the smoothed generator's weights)."""
+    if avg.numel() != p.numel():
+        raise ValueError('ema: %d averaged elements for %d parameters' % (avg.numel(), p.numel()))
+    _lib.call('pg_ema_f32', _p(avg), _p(p), avg.numel(), beta, _stream())
+
+
 def uniform_(t, seed, offset):
     """Fill the fp32 device tensor with U[0,1) draws: element i = Philox4x32-10(seed, offset, i) (wgan_gp_loss.py:15-17)."""
     require_gpu()

@@ -25,6 +25,20 @@ class Plugin(object):
 _STAT_FMT = ['{val:.2f}']
 
 
+def _check_smoothed(trainer, smoothed, who):
+    if smoothed and getattr(trainer, 'g_ema', None) is None:
+        raise ValueError('%s(smoothed=True) needs Trainer(g_ema=GeneratorEMA(G))' % who)
+
+
+def _output_generator(trainer, smoothed):
+    """The network an output plugin evaluates: the smoothed generator Gs when the trainer keeps one (``smoothed=None``: use it if it is
+    there; ``False``: raw G), at G's growth stage and ordered behind its last update."""
+    ema = getattr(trainer, 'g_ema', None)
+    if ema is None or smoothed is False:
+        return trainer.G
+    return ema.network()
+
+
 def growth_stage(cur_nimg, lod_training_nimg, lod_transition_nimg, max_depth):
     """The progressive-growing schedule as a pure integer function of the images shown so far (behaviour of reference
     plugins.py:58-63, bit for bit): time is cut into cycles of ``stabilise`` (lod_training_nimg) + ``fade``
@@ -199,7 +213,9 @@ class SaverPlugin(Plugin):
     ``c`` outside the state_dict, so whole-module pickling is what makes a snapshot resumable).
 
     Addition over the reference: ``network-snapshot-trainer-{kimg:06}.dat`` with both Adam
-    states and ``cur_nimg`` — the reference restarts Adam from zero moments on resume."""
+    states and ``cur_nimg`` — the reference restarts Adam from zero moments on resume.  A trainer with a smoothed generator
+    (``Trainer(g_ema=...)``) also gets ``network-snapshot-generator_smoothed-{kimg:06}.dat``, a whole-module pickle of Gs (an ordinary
+    ``Generator``: ``utils.output_samples`` takes it), and ``ema_beta`` / ``ema_halflife_kimg`` in the trainer file."""
 
     last_pattern = 'network-snapshot-{}-{}.dat'
 
@@ -219,10 +235,15 @@ class SaverPlugin(Plugin):
         if not self.keep_old_checkpoints:
             self._clear(self.last_pattern.format('*', '*'))
         kimg = '{:06}'.format(tr.cur_nimg // 1000)
-        for model, name in [(tr.G, 'generator'), (tr.D, 'discriminator')]:
-            torch.save(model, os.path.join(self.checkpoints_path, self.last_pattern.format(name, kimg)))
+        models = [(tr.G, 'generator'), (tr.D, 'discriminator')]
         state = {'cur_nimg': tr.cur_nimg, 'optimizer_d': tr.optimizer_d.state_dict(),
                  'optimizer_g': tr.optimizer_g.state_dict()}
+        ema = getattr(tr, 'g_ema', None)
+        if ema is not None:
+            models.append((ema.network(), 'generator_smoothed'))             # (network(): this stream is behind the last average)
+            state.update(ema_beta=ema.beta, ema_halflife_kimg=ema.halflife_kimg)
+        for model, name in models:
+            torch.save(model, os.path.join(self.checkpoints_path, self.last_pattern.format(name, kimg)))
         torch.save(state, os.path.join(self.checkpoints_path, self.last_pattern.format('trainer', kimg)))
 
     def end(self, *args):
@@ -243,6 +264,16 @@ def load_models(resume_network, result_dir, logger=None):
     return G, D
 
 
+def load_smoothed_generator(resume_network, result_dir):
+    """The smoothed generator SaverPlugin wrote next to ``load_models``' pair, for ``GeneratorEMA(G, Gs=...)``; None when the snapshot has
+    none (written without an average, or by an earlier version): the caller starts the average from G."""
+    import torch
+    path = os.path.join(result_dir, resume_network.format('generator_smoothed'))
+    if not os.path.exists(path):
+        return None
+    return torch.load(path, weights_only=False)
+
+
 def load_trainer_state(resume_network, result_dir, optimizer_d, optimizer_g):
     """Restore the Adam moments / step counts written by SaverPlugin; returns ``resume_nimg`` for Trainer."""
     import torch
@@ -256,15 +287,18 @@ class OutputGenerator(Plugin):
     """Sample-grid hook (plugins.py:177-195): every ``output_snapshot_ticks`` ticks run G on fresh latents and
     hand the fp32 ``[n,C,H,W]`` array to each postprocessor as ``proc(out, kimg)``.  A postprocessor exposing
     ``accepts_device_tensors`` (``utils.DeviceImageSaver``) gets the device tensor instead, so only the final
-    uint8 grid crosses PCIe."""
+    uint8 grid crosses PCIe.  ``smoothed``: None = the smoothed generator of ``Trainer(g_ema=...)`` when there is one, else G;
+    False = G; True = the smoothed one, or an error at ``register``."""
 
-    def __init__(self, sample_fn, output_postprocessors, samples_count=6, output_snapshot_ticks=3):
+    def __init__(self, sample_fn, output_postprocessors, samples_count=6, output_snapshot_ticks=3, smoothed=None):
         super(OutputGenerator, self).__init__([(output_snapshot_ticks, 'epoch'), (1, 'end')])
         self.sample_fn = sample_fn
         self.output_postprocessors = output_postprocessors
         self.samples_count = samples_count
+        self.smoothed = smoothed
 
     def register(self, trainer):
+        _check_smoothed(trainer, self.smoothed, 'OutputGenerator')
         self.trainer = trainer
 
     def epoch(self, epoch_index):
@@ -272,7 +306,7 @@ class OutputGenerator(Plugin):
         if tr.parallel is not None and tr.parallel.rank != 0:
             return
         gen_input = self.sample_fn(self.samples_count).cuda()
-        out_dev = tr.G.forward(gen_input)
+        out_dev = _output_generator(tr, self.smoothed).forward(gen_input)
         out_host = None
         for proc in self.output_postprocessors:
             if getattr(proc, 'accepts_device_tensors', False):
@@ -290,8 +324,9 @@ class SWDMonitor(Plugin):
     """Quality metric per tick (``metrics.SlicedWasserstein``; the reference reports none): every ``swd_ticks`` ticks and at the end,
     ``num_images`` real images from ``real_batch_fn(n)`` (fp32 device batches ``[n,3,R,R]`` at the current stage's resolution, e.g.
     ``utils.prepare_real_batch`` of a dataset batch) are measured against as many of ``G.forward(sample_fn(n).cuda())``, ``minibatch``
-    at a time.  Writes ``stats['swd']`` (the mean over the pyramid levels, x 1000) and one ``stats['swd_<res>']`` per level under the
-    stat-dict convention of the other monitors.  Stages below 16x16 have no pyramid level: nothing is written there.  Rank 0
+    at a time -- of the smoothed generator when the trainer keeps one, which is what the paper measures (``smoothed`` as in
+    ``OutputGenerator``: None = Gs if there is one, False = raw G, True = Gs or an error at ``register``).  Writes ``stats['swd']``
+    (the mean over the pyramid levels, x 1000) and one ``stats['swd_<res>']`` per level under the stat-dict convention of the other monitors.  Stages below 16x16 have no pyramid level: nothing is written there.  Rank 0
     evaluates (replicas are identical).  ``metric_kwargs`` go to ``SlicedWasserstein`` (patches_per_image, dir_repeats,
     dirs_per_repeat, seed).  One metric object (buffers, patch centres, directions) is alive at a time: a new stage drops the last
     stage's before it allocates its own (about 20 GB at the default size and 1024x1024).
@@ -302,16 +337,18 @@ class SWDMonitor(Plugin):
     400.  A run that wants the metric more often trades images for it (``num_images=2048, swd_ticks=50`` costs the same by the
     same estimate and is noisier)."""
 
-    def __init__(self, real_batch_fn, sample_fn, num_images=16384, minibatch=16, swd_ticks=400, **metric_kwargs):
+    def __init__(self, real_batch_fn, sample_fn, num_images=16384, minibatch=16, swd_ticks=400, smoothed=None, **metric_kwargs):
         super(SWDMonitor, self).__init__([(swd_ticks, 'epoch'), (1, 'end')])
         if int(num_images) < 1 or int(minibatch) < 1:
             raise ValueError('num_images and minibatch must be positive')
         self.real_batch_fn, self.sample_fn = real_batch_fn, sample_fn
         self.num_images, self.minibatch = int(num_images), int(minibatch)
         self.metric_kwargs = metric_kwargs
+        self.smoothed = smoothed
         self._metric_obj = None
 
     def register(self, trainer):
+        _check_smoothed(trainer, self.smoothed, 'SWDMonitor')
         self.trainer = trainer
 
     def _metric(self, resolution):
@@ -330,10 +367,11 @@ class SWDMonitor(Plugin):
             return
         metric = self._metric(resolution)
         metric.reset()
+        gen = _output_generator(tr, self.smoothed)
         for start in range(0, self.num_images, self.minibatch):
             n = min(self.minibatch, self.num_images - start)
             metric.feed_real(self.real_batch_fn(n))
-            metric.feed_fake(tr.G.forward(self.sample_fn(n).cuda()))
+            metric.feed_fake(gen.forward(self.sample_fn(n).cuda()))
         res = metric.result()
         tr.stats['swd'] = dict(log_name='swd', log_epoch_fields=['{val:.3f}'], val=res['mean'])
         for size, value in zip(res['levels'], res['swd']):

@@ -6,7 +6,7 @@ after a reload.  The class is closed: a schedule feature that needs a new piece 
 class NetRuntime(object):
     __slots__ = ('derived_ver', 'derived_live', 'derived_ev', 'derived_waited', 'derived_bwd_ev', 'derived_bwd_waited', 'bwd_wanted',
                  'defer_active', 'pending_ev', 'pending', 'skip_join', 'plan_unjoined', 'grad_hook', 'grad_exchange',
-                 'global_stddev', 'gs_checked', 'early_g_request', 'early_fwd', 'd_fwd_buffers')
+                 'global_stddev', 'gs_checked', 'early_g_request', 'early_fwd', 'd_fwd_buffers', 'ema_ev')
 
     def __init__(self):
         # ---- derived weights: written by engine._derived; plans._prologue re-checks the version before a replay
@@ -35,6 +35,10 @@ class NetRuntime(object):
         self.early_fwd = None               # on G: the engine.EarlyG the D step left; taken by the G step (engine.take_early_g, plans.g_step)
         # ---- three-pass D forward
         self.d_fwd_buffers = None           # engine._DForwardBuffers of the current (stage, shape); graphs.d_step keeps them alive
+        # ---- smoothed generator (on G)
+        self.ema_ev = None                  # event behind the last second-stream launch of ema.GeneratorEMA.update, which writes it (None: inline);
+        #                                     waited for by the stream of G's next parameter update (Trainer, before optimizer_g.step(): the launch
+        #                                     READS G's parameters) and by GeneratorEMA.network() (its consumers read what the launch wrote)
 
     def reset_derived(self):
         self.derived_ver = None

@@ -12,6 +12,8 @@ MI355X data-parallel additions (optional, default off):
     are sum-all-reduced over RCCL on the flat gradient buffers, ``cur_nimg`` advances by ``world_size * minibatch``
     so the depth/alpha schedule stays a pure function of the images shown, and the optimizers' gradient pre-scale is
     set to 1/world_size here (a plain ``torch.optim`` optimizer gets averaged gradients from the all-reduce instead);
+  * ``g_ema``: an ``ema.GeneratorEMA`` of ``G`` -- the smoothed generator Gs follows every G update (one launch on the second stream);
+    plugins read it as ``trainer.g_ema``.  Under data parallelism every rank keeps its own (identical) Gs: no exchange;
   * ``global_stddev=True`` (with ``parallel``): exact-global minibatch stddev -- the statistic of reference network.py:174-187 and the scalars
     of its adjoint / Hessian-vector term are reduced over all ranks, so world x minibatch equals one process at batch world * minibatch
     (default: every rank's own minibatch, SURVEY.md §8e);
@@ -136,7 +138,7 @@ class Trainer(object):
 
     def __init__(self, D, G, D_loss, G_loss, optimizer_d, optimizer_g, dataset, dataiter, random_latents_generator,
                  D_training_repeats=1, tick_nimg_default=2 * 1000, resume_nimg=0, parallel=None, input_transform=None,
-                 prefetch_inputs=False, global_stddev=False):
+                 prefetch_inputs=False, global_stddev=False, g_ema=None):
         # networks, losses, optimizers, data sources: the names are API (plugins read and replace them)
         self.D, self.G = D, G
         self.D_loss, self.G_loss = D_loss, G_loss
@@ -154,6 +156,9 @@ class Trainer(object):
         }
         self.plugin_queues = {unit: [] for unit in PLUGIN_UNITS}
         self.parallel = parallel
+        if g_ema is not None and g_ema.G is not G:
+            raise ValueError('g_ema averages another generator than the one this Trainer updates')
+        self.g_ema = g_ema             # None (default): no launch, event or wait is added to the iteration
         # input path: host -> device upload of the real batches on a copy stream (no-op for device-resident batches);
         # ``input_transform(device_batch) -> fp32 images`` runs on the device when the batch is consumed, e.g.
         # ``lambda u8: utils.prepare_real_batch(u8, dataset.alpha)`` for uint8 sources (a quarter of the PCIe bytes)
@@ -331,10 +336,15 @@ class Trainer(object):
             if g_rt is not None:
                 g_rt.grad_hook = None
         self._exchange(self.G)
+        if self.g_ema is not None:
+            self.g_ema.await_last()                  # (write after read: the last average may still be READING G's parameters on the second stream;
+            #                                           here and not in FusedAdam, so that a torch.optim optimizer is covered too)
         self.optimizer_g.step()                                                   # :112
         if getattr(self.G, '_flat_param', None) is not None and self.G._flat_param.is_cuda:
             engine._derived(self.G)                  # (the next generator pass needs them first thing; never part of a replayed plan)
             engine.probe('G.update_end')
+        if self.g_ema is not None:
+            self.g_ema.update(latents.size(0) * world)           # Gs follows G: global images of this iteration; outside the launch plans, like Adam
         if d_rt is not None:
             engine.wait_pending(self.D)              # (a G_loss that never ran D: nothing may outlive the iteration)
         if g_rt is not None and g_rt.take('early_fwd') is not None:               # (... nor a generator pass nobody took)
