@@ -458,6 +458,35 @@ int pg_mono_f32(const float* y, int64_t nsamp, int channels, float* out, int64_t
 int pg_minmax_f32(const float* x, int64_t n, float* lohi, pg_stream_t stream);
 int pg_stretch_to_u8(const float* x, uint8_t* out, int64_t n, const float* lohi, float max_out, pg_stream_t stream);
 
+/* Sound output step: replaces SoundSaver.image_to_sound / reconstruct_from_magnitude, output_postprocess.py:92-127, for samples that
+ * are on the device (csrc/griffinlim.hip).  Everything is fp64 without contraction, nothing uses atomics (bit-identical from run to
+ * run); librosa's stft / istft by their published definitions (oracle/sound_steps.py: parity unpinned).  n_fft (= 2 H) is a power of
+ * two in 8 .. 2048, PG_E_UNSUP otherwise.  Asynchronous on the stream, nothing is allocated.
+ *   pg_gl_spectrum_f64: output_postprocess.py:109-118.  img [n][H][W] fp32 (channel 0 of G's output) -> spec [n][W frames][H + 1 bins]:
+ *       v = ((double)img - lo_in) * scale + lo_out (adjust_dynamic_range, utils.py:24-30) for bins < H and the same formula applied to
+ *       0 for bin H -- the reference pads with zeros (:109-111) BEFORE it adjusts the range.  PG_SOUND_ABSLOG (:118) stores v, which
+ *       Griffin-Lim then takes as the magnitude as it is (the reference does not invert log(1 + |s|)); PG_SOUND_REALLOG (:113-115, the
+ *       caller passes the output range (-1, 1)) stores (exp(|v|) - 1) * sign(v).
+ *   pg_gl_pieces_f64: one Griffin-Lim round up to the overlap-add, :96-98 and the transform half of lbr.istft (:101).  x [batch][nsamp],
+ *       spec as above with frames = W and n_fft/2 + 1 bins, pieces [batch][frames][n_fft].  Frame t of x[b] (reflect padding by n_fft/2,
+ *       periodic Hann window) -> FFT -> every bin k <= n_fft/2 becomes spec[b][t][k] * S/|S| (S == 0: the phase factor (1, 0), as
+ *       np.angle(0) = 0) -> irfft (Hermitian extension; imaginary parts of DC and Nyquist ignored) -> times window * 2/3.
+ *       x == NULL: no forward transform, the spectrum is spec taken as real numbers (the single lbr.istft of 'reallog', :116).
+ *       nsamp > n_fft/2 and nsamp == hop * (frames - 1), PG_E_ARG otherwise.
+ *   pg_overlap_add_f64: the overlap-add half of lbr.istft (:101, :116): x[b][j] = sum_t pieces[b][t][j + n_fft/2 - t hop] over the
+ *       frames that cover padded index j + n_fft/2, added in ascending t from 0.0 (the host loop's order); samples no frame covers
+ *       (hop > n_fft) are 0.0.  Any hop >= 1; nsamp == hop * (frames - 1).
+ *   pg_wave_normalize_f32: :126, numpy_upsample_nearest(signal, 1, repeat) :152 and the float32 cast of the WAV writer :136:
+ *       peak[b] = max_j |x[b][j]|, out[b][j repeat + r] = (float)(x[b][j] / peak[b]) -- an fp64 division, then round to nearest.
+ *       peak: scratch of batch doubles owned by the caller. */
+int pg_gl_spectrum_f64(const float* img, double* spec, int n, int H, int W, double lo_in, double scale, double lo_out,
+                       int mode, pg_stream_t stream);
+int pg_gl_pieces_f64(const double* x, int64_t nsamp, const double* spec, double* pieces, int n_fft, int hop, int frames,
+                     int batch, pg_stream_t stream);
+int pg_overlap_add_f64(const double* pieces, double* x, int64_t nsamp, int n_fft, int hop, int frames, int batch,
+                       pg_stream_t stream);
+int pg_wave_normalize_f32(const double* x, float* out, int64_t nsamp, int repeat, int batch, double* peak, pg_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sliced Wasserstein distance between Laplacian-pyramid patch descriptors of two image sets (Karras et al. 2018, "Progressive
  * growing of GANs", section 5): the quality metric of a run.  The reference has none; the definition is the published one

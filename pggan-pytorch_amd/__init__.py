@@ -13,9 +13,10 @@ from .plugins import (Plugin, DepthManager, LRScheduler, RampupLR, TimeMonitor, 
 from .optim import FusedAdam  # noqa: F401
 from .ema import GeneratorEMA  # noqa: F401
 from .parallel import DataParallel  # noqa: F401
-from .sound import SoundSaver, spectrogram_u8  # noqa: F401
+from .sound import SoundSaver, DeviceSoundSaver, spectrogram_u8  # noqa: F401
 from ._lib import PgganLibraryError, LIB_PATH  # noqa: F401
 
 __all__ = ['Generator', 'Discriminator', 'PGConv2d', 'wgan_gp_D_loss', 'wgan_gp_G_loss', 'Trainer', 'Plugin',
            'DepthManager', 'LRScheduler', 'RampupLR', 'TimeMonitor', 'AbsoluteTimeMonitor', 'SaverPlugin', 'OutputGenerator', 'SWDMonitor', 'load_models',
-           'load_smoothed_generator', 'load_trainer_state', 'FusedAdam', 'GeneratorEMA', 'DataParallel', 'SoundSaver', 'spectrogram_u8']
+           'load_smoothed_generator', 'load_trainer_state', 'FusedAdam', 'GeneratorEMA', 'DataParallel', 'SoundSaver', 'DeviceSoundSaver',
+           'spectrogram_u8']

@@ -92,6 +92,11 @@ SIGNATURES = {
     'pg_mono_f32': [P, L, I, P, L, P],
     'pg_minmax_f32': [P, L, P, P],
     'pg_stretch_to_u8': [P, P, L, P, F, P],
+    # Griffin-Lim on the device (csrc/griffinlim.hip)
+    'pg_gl_spectrum_f64': [P, P, I, I, I, D, D, D, I, P],
+    'pg_gl_pieces_f64': [P, L, P, P, I, I, I, I, P],
+    'pg_overlap_add_f64': [P, P, L, I, I, I, I, P],
+    'pg_wave_normalize_f32': [P, P, L, I, I, P, P],
     # sliced Wasserstein distance (csrc/swd.hip)
     'pg_lap_down': [P, P, L, I, P],
     'pg_lap_up_sub': [P, P, P, L, I, P],

@@ -909,3 +909,128 @@ def swd_l1(a, b):
     out = torch.empty((), device=a.device, dtype=torch.float32)
     _lib.call('pg_swd_l1', _p(a), _p(b), a.numel(), partials.data_ptr(), _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------- Griffin-Lim on the device (csrc/griffinlim.hip)
+GL_MIN_N, GL_MAX_N = 8, 2048       # n_fft = 2 H: a power of two in this range (image heights 4 .. 1024)
+
+
+def _f64_dev(t, what, ndim=None):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+        raise ValueError('%s: expected a contiguous float64 device tensor' % what)
+    if ndim is not None and t.dim() != ndim:
+        raise ValueError('%s: expected %d dimensions, got shape %s' % (what, ndim, tuple(t.shape)))
+    return t
+
+
+def _gl_n_fft(n_fft, what):
+    if n_fft < GL_MIN_N or n_fft > GL_MAX_N or n_fft & (n_fft - 1):
+        raise ValueError('%s: n_fft must be a power of two in %d .. %d, got %d' % (what, GL_MIN_N, GL_MAX_N, n_fft))
+
+
+def gl_spectrum(images, mode='abslog', drange=(-1, 1)):
+    """fp32 device images [n,H,W] (or [n,1,H,W]) -> the float64 spectrum [n, W frames, H + 1 bins] Griffin-Lim keeps
+    (pg_gl_spectrum_f64, output_postprocess.py:109-118): zero-padded to H + 1 bins, THEN range-adjusted from ``drange`` to (0, 255)
+    ('abslog': the value is the magnitude) or to (-1, 1) followed by (exp(|v|) - 1) * sign(v) ('reallog')."""
+    if mode not in SOUND_MODES:
+        raise ValueError("gl_spectrum: mode must be 'abslog' or 'reallog' (got %r)" % (mode,))
+    _f32_dev(images, 'gl_spectrum images')
+    if images.dim() == 4 and images.shape[1] == 1:
+        images = images[:, 0]
+    if images.dim() != 3 or images.shape[0] < 1:
+        raise ValueError('gl_spectrum images: expected [n,H,W] or [n,1,H,W], got shape %s' % (tuple(images.shape),))
+    n, H, W = images.shape
+    _gl_n_fft(2 * H, 'gl_spectrum images of height %d' % H)
+    range_out = (0, 255) if mode == 'abslog' else (-1, 1)
+    lo_in, scale, lo_out = 0.0, 1.0, 0.0                     # adjust_dynamic_range (utils.py:24-30) leaves equal ranges untouched
+    if tuple(drange) != range_out:
+        lo_in, scale, lo_out = drange[0], (range_out[1] - range_out[0]) / (drange[1] - drange[0]), range_out[0]
+    spec = torch.empty((n, W, H + 1), device=images.device, dtype=torch.float64)
+    _lib.call('pg_gl_spectrum_f64', _p(images), spec.data_ptr(), n, H, W, float(lo_in), float(scale), float(lo_out),
+              SOUND_MODES[mode], _stream())
+    return spec
+
+
+def _gl_shapes(spec, hop, what):
+    _f64_dev(spec, what + ' spec', 3)
+    batch, frames, bins = spec.shape
+    hop = int(hop)
+    n_fft = 2 * (bins - 1)
+    _gl_n_fft(n_fft, what)
+    if hop < 1 or batch < 1:
+        raise ValueError('%s: hop must be >= 1 and the batch non-empty' % what)
+    nsamp = hop * (frames - 1)
+    if nsamp <= n_fft // 2:
+        raise ValueError('%s: %d frames every %d samples give %d samples, reflect padding by n_fft/2 = %d needs more'
+                         % (what, frames, hop, nsamp, n_fft // 2))
+    return batch, frames, n_fft, hop, nsamp
+
+
+def gl_pieces(x, spec, hop, out=None):
+    """One Griffin-Lim round up to the overlap-add (pg_gl_pieces_f64): float64 device ``x`` [batch, hop (frames - 1)] and ``spec``
+    [batch, frames, n_fft/2 + 1] -> windowed frames [batch, frames, n_fft] that carry spec's magnitudes and the phases of STFT(x).
+    ``x`` None: the inverse transform of ``spec`` taken as a real spectrum ('reallog')."""
+    batch, frames, n_fft, hop, nsamp = _gl_shapes(spec, hop, 'gl_pieces')
+    if x is not None and tuple(_f64_dev(x, 'gl_pieces x', 2).shape) != (batch, nsamp):
+        raise ValueError('gl_pieces x: expected [%d,%d], got %s' % (batch, nsamp, tuple(x.shape)))
+    if out is None:
+        out = torch.empty((batch, frames, n_fft), device=spec.device, dtype=torch.float64)
+    elif tuple(_f64_dev(out, 'gl_pieces out', 3).shape) != (batch, frames, n_fft):
+        raise ValueError('gl_pieces out: expected [%d,%d,%d], got %s' % (batch, frames, n_fft, tuple(out.shape)))
+    _lib.call('pg_gl_pieces_f64', None if x is None else x.data_ptr(), nsamp, spec.data_ptr(), out.data_ptr(), n_fft, hop, frames,
+              batch, _stream())
+    return out
+
+
+def overlap_add(pieces, hop, out=None):
+    """float64 device frames [batch, frames, n_fft] -> signal [batch, hop (frames - 1)] (pg_overlap_add_f64): librosa's istft
+    overlap-add with the centring pad cut off, the frames added in ascending order."""
+    _f64_dev(pieces, 'overlap_add pieces', 3)
+    batch, frames, n_fft = pieces.shape
+    hop = int(hop)
+    _gl_n_fft(n_fft, 'overlap_add')
+    if hop < 1 or batch < 1 or frames < 2:
+        raise ValueError('overlap_add: hop must be >= 1, the batch non-empty and frames >= 2')
+    nsamp = hop * (frames - 1)
+    if out is None:
+        out = torch.empty((batch, nsamp), device=pieces.device, dtype=torch.float64)
+    elif tuple(_f64_dev(out, 'overlap_add out', 2).shape) != (batch, nsamp):
+        raise ValueError('overlap_add out: expected [%d,%d], got %s' % (batch, nsamp, tuple(out.shape)))
+    _lib.call('pg_overlap_add_f64', pieces.data_ptr(), out.data_ptr(), nsamp, n_fft, hop, frames, batch, _stream())
+    return out
+
+
+def wave_normalize(x, repeat=1):
+    """float64 device signals [batch, nsamp] -> float32 [batch, nsamp * repeat]: each divided by its peak max|x| in fp64, rounded to
+    float32, every sample repeated ``repeat`` times (pg_wave_normalize_f32; output_postprocess.py:126, :152 and the WAV writer's cast)."""
+    _f64_dev(x, 'wave_normalize x', 2)
+    batch, nsamp = x.shape
+    repeat = int(repeat)
+    if batch < 1 or nsamp < 1 or repeat < 1:
+        raise ValueError('wave_normalize: expected a non-empty [batch, nsamp] and repeat >= 1, got %s and %d' % (tuple(x.shape), repeat))
+    peak = torch.empty(batch, device=x.device, dtype=torch.float64)
+    out = torch.empty((batch, nsamp * repeat), device=x.device, dtype=torch.float32)
+    _lib.call('pg_wave_normalize_f32', x.data_ptr(), _p(out), nsamp, repeat, batch, peak.data_ptr(), _stream())
+    return out
+
+
+def griffin_lim(images, x0, hop, rounds, mode='abslog', drange=(-1, 1), round_hook=None):
+    """SoundSaver.image_to_sound up to the normalisation (output_postprocess.py:107-119) for a batch: fp32 device ``images`` [n,H,W]
+    (or [n,1,H,W]) -> float64 device signals [n, hop (W - 1)].  'abslog': ``rounds`` rounds of Griffin-Lim from the float64 device
+    starts ``x0`` [n, hop (W - 1)] (left unchanged); 'reallog': one inverse STFT (``x0`` and ``rounds`` unused).  1 + 2 rounds launches
+    on the current stream (3 for 'reallog'), no host synchronisation -- unless ``round_hook(i, previous, x)`` is given, a debugging
+    aid that is called with the two device signals after every round."""
+    spec = gl_spectrum(images, mode, drange)
+    if mode == 'reallog':
+        return overlap_add(gl_pieces(None, spec, hop), hop)
+    if x0 is None:
+        raise ValueError("griffin_lim x0: 'abslog' needs the start signals")
+    x = x0
+    pieces = nxt = None
+    for i in range(int(rounds)):
+        pieces = gl_pieces(x, spec, hop, out=pieces)
+        prev, x = x, overlap_add(pieces, hop, out=nxt)
+        nxt = prev if prev is not x0 else None              # two signal buffers alternate; the caller's start is never written
+        if round_hook is not None:
+            round_hook(i, prev, x)
+    return x

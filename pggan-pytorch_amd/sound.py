@@ -7,6 +7,8 @@ post-processor with the reference's hook signature.
     ``[n, 1, H, W]`` samples of G; 'abslog' images go through Griffin-Lim (``griffin_lim_iter`` rounds of STFT / inverse
     STFT), 'raw' images are the waveform itself; one 32-bit float WAV per sample, names as in the reference.  It runs on the
     host with numpy, as the reference does and as SURVEY.md §8f allows (6 samples every 3 ticks).
+  * ``DeviceSoundSaver`` — the same files from the device: the spectrum, every Griffin-Lim round and the normalisation are the fp64
+    HIP kernels of csrc/griffinlim.hip; only the float32 waveforms are copied back.  Opt-in: ``SoundSaver`` stays the default.
 
 The reference delegates the transforms to librosa 0.4.3 (requirements.txt:1), which is not in this image; both ends follow
 its published definitions (periodic Hann window, center=True with reflect padding, hop_length; inverse: windowed
@@ -125,3 +127,60 @@ class SoundSaver(object):
             if times_smaller > 1:
                 signal = signal.repeat(times_smaller, axis=-1)                # utils.numpy_upsample_nearest(signal, 1, scale_factor=...)
             self.output_wav(signal, samples_description, i)
+
+
+def _to_device(t):
+    return t.cuda()
+
+
+class DeviceSoundSaver(SoundSaver):
+    """``SoundSaver`` with the arithmetic on the device (csrc/griffinlim.hip): same constructor, ``seed``, file names and WAV writer.
+    ``plugins.OutputGenerator`` and ``utils.output_samples`` hand it G's device tensor (``accepts_device_tensors``); the samples of
+    one call are transformed as one batch, and only their float32 waveforms cross to the host.  The random starts of Griffin-Lim are
+    drawn on the HOST from the object's RNG -- one ``randn((W - 1) * hop_length)`` per sample in sample order, exactly the draws
+    ``SoundSaver`` makes -- and uploaded once, so ``seed=`` gives the same WAVs from both savers (``metrics.SlicedWasserstein``
+    treats its randomness the same way).  Images must be square with a power-of-two side in 4 .. 1024; there is no fallback to the
+    host.  ``verbose=True`` prints the host saver's line per round and sample; it copies both signals back after every round, a slow
+    debugging aid."""
+
+    accepts_device_tensors = True            # plugins.OutputGenerator then skips the D2H copy of the fp32 samples
+
+    def to_waveforms(self, output):
+        """fp32 ``[n, 1, H, W]`` samples (device tensor, or numpy array / host tensor, which is uploaded) -> float32 device tensor
+        ``[n, nsamp * times_smaller]``: each sample's waveform, peak-normalised and stretched as ``SoundSaver.__call__`` writes it."""
+        import torch
+        from . import ops
+        if self.mode not in ('abslog', 'reallog', 'raw'):
+            raise ValueError('SoundSaver mode %r is not one of abslog / reallog / raw' % (self.mode,))
+        t = output if torch.is_tensor(output) else torch.from_numpy(np.ascontiguousarray(output, dtype=np.float32))
+        if t.dim() != 4 or t.shape[0] < 1:
+            raise ValueError('DeviceSoundSaver: expected samples [n, 1, H, W], got shape %s' % (tuple(t.shape),))
+        n, _, H, W = t.shape
+        if H != W or H < 4 or H > 1024 or H & (H - 1):
+            raise ValueError('DeviceSoundSaver: images must be square with a power-of-two side in 4 .. 1024, got %dx%d' % (H, W))
+        times_smaller = self.resolution // W
+        if self.mode == 'raw':
+            times_smaller *= times_smaller
+        nsamp = (W - 1) * self.hop_length
+        if self.mode != 'raw' and nsamp <= H:
+            raise ValueError('DeviceSoundSaver: %d frames every %d samples give %d samples, the reflect padding by n_fft/2 = %d '
+                             'needs more' % (W, self.hop_length, nsamp, H))
+        img = _to_device(t)[:, 0].to(torch.float32).contiguous()             # channel 0, as image_to_sound(img[0])
+        if self.mode == 'raw':
+            x = img.reshape(n, H * W).to(torch.float64)                       # image.ravel(): a cast, the arithmetic is the kernel's
+        else:
+            x0, hook = None, None
+            if self.mode == 'abslog':
+                x0 = _to_device(torch.from_numpy(np.stack([self._rng.randn(nsamp) for _ in range(n)])))
+                hook = self._print_round if self.verbose else None
+            x = ops.griffin_lim(img, x0, self.hop_length, self.griffin_lim_iter, self.mode, self.drange, round_hook=hook)
+        return ops.wave_normalize(x, max(1, times_smaller))
+
+    @staticmethod
+    def _print_round(i, previous, x):
+        for a, b in zip(x.cpu().numpy(), previous.cpu().numpy()):
+            print('Griffin-Lim: change of the signal in this round (L2) = %g' % np.sqrt(np.square(a - b).sum()))
+
+    def __call__(self, output, samples_description):
+        for i, wav in enumerate(self.to_waveforms(output).cpu().numpy()):
+            self.output_wav(wav, samples_description, i)                      # (its own normalisation is the identity: the peak is 1)
