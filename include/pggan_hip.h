@@ -524,6 +524,32 @@ int pg_swd_sort_rows(float* buf, float* tmp, int K, int64_t M, pg_stream_t strea
 int pg_swd_l1(const float* a, const float* b, int64_t n, double* partials, float* out, pg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Multi-scale structural similarity between pairs of images (Wang, Simoncelli & Bovik 2003, as Karras et al. 2018 use it to detect
+ * loss of variation): the diversity metric of a run, defined per channel (C = 1 or 3).  The reference has none; the definition is
+ * the published one (restated for the CPU in tests/msssim_ref.py).  Images are fp32 [planes][side][side],
+ * planes = pairs x channels, side a power of two >= 16.
+ *   pg_msssim_scale:  one scale.  mode 2 maps [lo, hi] to [0, 255] with pg_image_grid_u8's arithmetic ((x - lo) * (float)(255 / (hi -
+ *                     lo)), one rounding each, round half to even, clip); mode 1 maps only; mode 0 takes a, b as they are (a pooled
+ *                     image).  Per plane and 11x11 window position ('valid': (side - 10)^2 of them; Gaussian taps, sigma 1.5,
+ *                     normalised in fp64, then fp32) the moments mu_a, mu_b, E[aa], E[bb], E[ab] give
+ *                         cs = (2 s_ab + C2) / (s_aa + s_bb + C2),   ssim = (2 mu_a mu_b + C1) / (mu_a^2 + mu_b^2 + C1) * cs
+ *                     with C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2.  One workgroup per PG_MSSSIM_TILE^2 block of a plane writes
+ *                     partials[2 * wg] = its sum of ssim and partials[2 * wg + 1] = its sum of cs over the valid positions,
+ *                     wg = (plane * tiles + tile_y) * tiles + tile_x, tiles = ceil((side - 10) / PG_MSSSIM_TILE): 2 * planes *
+ *                     tiles^2 doubles.  pool_a / pool_b (both or neither; side >= 32): [planes][side/2][side/2], the 2x2 box mean
+ *                     ((p00 + p01) + p10) + p11, then x 0.25, of the images as the moments saw them (quantised under mode 2).
+ *   pg_msssim_finish: partials = the blocks of scale 0 (side R), 1 (R / 2), ... one after the other, S = min(PG_MSSSIM_MAX_SCALES,
+ *                     log2(R) - 3) of them.  terms [n][S]: per pair the mean cs over positions and channels of every scale below
+ *                     the last and the mean ssim of the last; values [n]: prod_s max(terms[s], 0) ^ w_s, w = the first S of
+ *                     [0.0448, 0.2856, 0.3001, 0.2363, 0.1333] over their sum.  fp64.
+ * No atomics: the same inputs give the same bits, and a pair's value does not depend on the rest of the batch. */
+#define PG_MSSSIM_TILE 32
+#define PG_MSSSIM_MAX_SCALES 5
+int pg_msssim_scale(const float* a, const float* b, float* pool_a, float* pool_b, double* partials, int64_t planes, int side,
+                    int mode, float lo, float hi, pg_stream_t stream);
+int pg_msssim_finish(const double* partials, double* values, double* terms, int64_t n, int C, int R, pg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Gradient exchange of the data-parallel step: RCCL over xGMI (SURVEY.md §8b "the all-reduce itself is a C-ABI call
  * taking ncclComm_t, buffer, count, stream", §8e).  The reference is single-GPU and has no collective; the exchange
  * points are after `D_loss.backward()` trainer.py:98 (before optimizer_d.step() :100) and after `G_loss.backward()`

@@ -106,6 +106,9 @@ SIGNATURES = {
     'pg_swd_project': [P, P, P, L, I, P],
     'pg_swd_sort_rows': [P, P, I, L, P],
     'pg_swd_l1': [P, P, L, P, P, P],
+    # multi-scale SSIM between image pairs (csrc/msssim.hip)
+    'pg_msssim_scale': [P, P, P, P, P, L, I, I, F, F, P],
+    'pg_msssim_finish': [P, P, P, L, I, I, P],
     # gradient exchange (RCCL bound at run time inside the library)
     'pg_rccl_version': [P],
     'pg_comm_unique_id': [P],

@@ -1,8 +1,8 @@
 """Quality metrics of a training run, evaluated on the device.
 
 ``SlicedWasserstein``: the sliced Wasserstein distance between Laplacian-pyramid patch descriptors of real and generated images
-(Karras et al. 2018, "Progressive growing of GANs", section 5), one value per pyramid level -- the one metric of the paper that needs
-no pretrained network.  The reference has no metric; the definition is the published one:
+(Karras et al. 2018, "Progressive growing of GANs", section 5), one value per pyramid level -- one of the two metrics of the paper that need
+no pretrained network (``MultiScaleSSIM`` below is the other).  The reference has no metric; the definition is the published one:
 
 1. Laplacian pyramid of every image, levels ``R, R/2, ..., 16`` (``ops.lap_pyramid``);
 2. per level, ``patches_per_image`` 3x7x7 neighbourhoods of every image as rows of 147 floats (``ops.swd_gather``);
@@ -12,7 +12,14 @@ no pretrained network.  The reference has no metric; the definition (DESIGN.md s
 
 All randomness (patch centres, directions) comes from the object's own seeded CPU generator: the trainer's random stream is not touched
 and the same seed gives the same metric.  The two sets use the SAME patch centres (image i of one set is sampled where image i of the
-other is), so a set measured against itself gives exactly 0."""
+other is), so a set measured against itself gives exactly 0.
+
+``MultiScaleSSIM``: the multi-scale structural similarity (Wang, Simoncelli & Bovik 2003) between pairs of GENERATED images, which
+the paper uses to detect loss of variation: a generator that collapses onto a few images keeps a fair SWD for a while, but its
+independent samples start to resemble each other and the mean MS-SSIM rises.  It is defined per channel, so one-channel (spectrogram)
+networks, which ``SlicedWasserstein`` refuses, have a metric too.  Definition: DESIGN.md section 7 (``ops.msssim_pairs``); it draws
+no random numbers, so it has no seed.  Like the SWD it is UNPINNED: no vectors of the authors' implementation are at hand, the
+values are comparable within a growth stage and between runs of this project."""
 import torch
 
 from . import ops
@@ -128,4 +135,68 @@ class SlicedWasserstein(object):
             d = torch.stack(dists).cpu().double().view(len(self.levels), self.dir_repeats)
             swd = [float(v) for v in (d.mean(dim=1) * 1e3)]
             self._result = {'levels': list(self.levels), 'swd': swd, 'mean': sum(swd) / len(swd)}
+        return self._result
+
+
+class MultiScaleSSIM(object):
+    """Feed ``num_pairs`` pairs of fp32 device batches ``a, b [n,C,R,R]`` (any split; pair i is ``(a[i], b[i])``), then ``result()``.
+
+    ``quantize``: measure the 0..255 levels of the saved image (``drange`` mapped, rounded half to even, clipped), the default;
+    False maps the range only.  Scratch is the pooled images and partial sums of ONE fed batch, allocated at the first ``feed`` for
+    that batch size (a larger batch later re-allocates) and reused."""
+
+    def __init__(self, resolution, num_pairs, num_channels=3, drange=(-1, 1), quantize=True, device=None):
+        self.scales, self.weights = ops.msssim_scales(resolution)
+        if int(num_channels) not in (1, 3):
+            raise ValueError('num_channels must be 1 or 3, got %r' % (num_channels,))
+        if int(num_pairs) != num_pairs or num_pairs < 1:
+            raise ValueError('num_pairs must be a positive integer, got %r' % (num_pairs,))
+        if not float(drange[1]) > float(drange[0]):
+            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
+        self.resolution, self.num_pairs, self.num_channels = int(resolution), int(num_pairs), int(num_channels)
+        self.drange, self.quantize = (float(drange[0]), float(drange[1])), bool(quantize)
+        ops.require_gpu()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._values = torch.empty(self.num_pairs, device=self.device, dtype=torch.float64)
+        self._terms = torch.empty((self.num_pairs, len(self.scales)), device=self.device, dtype=torch.float64)
+        self._scratch = None
+        self.reset()
+
+    def reset(self):
+        """Forget what was fed: the buffers are reused for the next evaluation."""
+        self._fed = 0
+        self._result = None
+
+    def feed(self, a, b):
+        shape = (self.num_channels, self.resolution, self.resolution)
+        for t in (a, b):
+            if not torch.is_tensor(t) or t.dim() != 4 or tuple(t.shape[1:]) != shape:
+                raise ValueError('expected batches [n,%d,%d,%d], got %s' % (shape + (tuple(t.shape) if torch.is_tensor(t) else type(t),)))
+        if self._result is not None:                                        # (before the count: a finished evaluation is full by definition)
+            raise RuntimeError('result() was taken: reset() before feeding again')
+        n, fed = a.shape[0], self._fed
+        if n < 1 or fed + n > self.num_pairs:
+            raise ValueError('%d pairs fed, %d more would exceed num_pairs = %d' % (fed, n, self.num_pairs))
+        if self._scratch is None or self._scratch.n < n:
+            self._scratch = None
+            self._scratch = ops.MSSSIMScratch(n, self.num_channels, self.resolution, self.device)
+        ops.msssim_pairs(a, b, self.drange, self.quantize, out=(self._values[fed:fed + n], self._terms[fed:fed + n]),
+                         scratch=self._scratch)
+        self._fed = fed + n
+
+    @property
+    def complete(self):
+        return self._fed == self.num_pairs
+
+    def result(self):
+        """{'msssim': mean over the pairs, 'std': their population standard deviation, 'scales': [R, R/2, ...], 'terms': the mean of
+        every scale's term (contrast-structure below the last scale, ssim at the last)}, in fp64 on the host.  One device synchronisation."""
+        if self._result is None:
+            if not self.complete:
+                raise RuntimeError('fed %d pairs of %d' % (self._fed, self.num_pairs))
+            both = torch.cat([self._values.view(-1, 1), self._terms], dim=1).cpu()
+            v = both[:, 0]
+            mean = float(v.mean())
+            self._result = {'msssim': mean, 'std': float((v - mean).pow(2).mean().sqrt()), 'scales': list(self.scales),
+                            'terms': [float(t) for t in both[:, 1:].mean(dim=0)]}
         return self._result

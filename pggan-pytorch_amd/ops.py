@@ -911,6 +911,105 @@ def swd_l1(a, b):
     return out
 
 
+# ------------------------------------------------------------------------- multi-scale SSIM between image pairs (csrc/msssim.hip)
+MSSSIM_TILE = 32                   # PG_MSSSIM_TILE: outputs (and pixels) per workgroup side
+MSSSIM_WINDOW = 11                 # taps of the Gaussian window; a scale's side is at least 16 so that the window always fits whole
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli & Bovik 2003; PG_MSSSIM_MAX_SCALES of them
+MSSSIM_MODES = {'as_is': 0, 'range': 1, 'quantize': 2}
+
+
+def msssim_scales(resolution):
+    """Host function: (sides, weights) of the scales of a ``resolution`` x ``resolution`` image.  S = min(5, log2(R) - 3) scales of
+    side R, R/2, ... (each >= 16); the weights are the first S published ones over their sum."""
+    resolution = int(resolution)
+    if resolution < 16 or resolution & (resolution - 1):
+        raise ValueError('resolution must be a power of two >= 16, got %r' % (resolution,))
+    S = min(len(MSSSIM_WEIGHTS), resolution.bit_length() - 4)
+    total = sum(MSSSIM_WEIGHTS[:S])
+    return [resolution >> s for s in range(S)], [w / total for w in MSSSIM_WEIGHTS[:S]]
+
+
+def _msssim_tiles(side):
+    return (side - (MSSSIM_WINDOW - 1) + MSSSIM_TILE - 1) // MSSSIM_TILE
+
+
+def _msssim_check(a, b, what):
+    for t, name in ((a, 'a'), (b, 'b')):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('%s %s: expected a contiguous float32 device tensor' % (what, name))
+    if a.dim() != 4 or a.shape != b.shape:
+        raise ValueError('%s: expected two equal shapes [n,C,R,R], got %s and %s' % (what, tuple(a.shape), tuple(b.shape)))
+    n, C, R, W = a.shape
+    if n < 1 or C not in (1, 3) or R != W or R < 16 or (R & (R - 1)):
+        raise ValueError('%s: expected [n,C,R,R] with n >= 1, C in (1, 3) and R a power of two >= 16, got %s' % (what, tuple(a.shape)))
+    return n, C, R
+
+
+class MSSSIMScratch(object):
+    """Work buffers of ``msssim_pairs`` for batches of up to ``n`` pairs ``[n,C,R,R]``: per scale below the finest the pooled images of
+    a and of b (``pooled[s - 1] = (a_s, b_s)``, fp32 ``[n,C,R >> s,R >> s]``) and the per-workgroup partial sums of every scale
+    (``partials[s]``, fp64 ``[n * C * tiles_s^2, 2]`` of (sum of ssim, sum of cs))."""
+
+    def __init__(self, n, C, R, device):
+        self.n, self.C, self.R = int(n), int(C), int(R)
+        self.sides, self.weights = msssim_scales(R)
+        self.pooled = [tuple(torch.empty((self.n, self.C, s, s), device=device, dtype=torch.float32) for _ in range(2))
+                       for s in self.sides[1:]]
+        self.partial_rows = [self.C * _msssim_tiles(s) ** 2 for s in self.sides]          # per pair
+        self._partials = torch.empty((self.n * sum(self.partial_rows), 2), device=device, dtype=torch.float64)
+
+    def partials(self, n):
+        """The blocks of the scales for a batch of ``n`` pairs, one after the other from the start of the buffer (what pg_msssim_finish reads)."""
+        out, start = [], 0
+        for rows in self.partial_rows:
+            out.append(self._partials[start:start + n * rows])
+            start += n * rows
+        return out
+
+
+def msssim_scale(a, b, pool_a, pool_b, partials, mode, drange=(-1, 1)):
+    """One scale (pg_msssim_scale) of the planes ``a``, ``b`` [n,C,s,s]: fills ``partials`` [n*C*tiles^2, 2] and, when given, the
+    pooled images [n,C,s/2,s/2].  ``mode``: 'quantize' / 'range' (the finest scale, with / without rounding and clipping) or 'as_is'."""
+    n, C, side, _ = a.shape
+    _lib.call('pg_msssim_scale', _p(a), _p(b), _p(pool_a), _p(pool_b), partials.data_ptr(), n * C, side, MSSSIM_MODES[mode],
+              float(drange[0]), float(drange[1]), _stream())
+
+
+def msssim_pairs(a, b, drange=(-1, 1), quantize=True, out=None, scratch=None):
+    """MS-SSIM of the pairs ``(a[i], b[i])`` of two fp32 device batches [n,C,R,R], C in (1, 3), R a power of two >= 16 (DESIGN.md
+    section 7; one launch per scale plus one).  Returns ``(values [n], terms [n,S])``, fp64 device tensors: ``terms`` holds the mean
+    contrast-structure term of every scale below the last and the mean ssim of the last, ``values`` the weighted product of the terms
+    clamped at 0.  ``quantize``: round and clip to the 0..255 levels of the saved image first (``ops.image_grid_u8``'s arithmetic);
+    False maps ``drange`` to [0, 255] only.  ``out``: a ``(values, terms)`` pair to write into; ``scratch``: an ``MSSSIMScratch`` of
+    at least this batch (allocated when not given; ``scratch.pooled`` holds the pooled images afterwards).  No host synchronisation."""
+    n, C, R = _msssim_check(a, b, 'msssim_pairs')
+    lo, hi = float(drange[0]), float(drange[1])
+    if not hi > lo:
+        raise ValueError('msssim_pairs: drange must be (lo, hi) with hi > lo, got %r' % (drange,))
+    if scratch is None:
+        scratch = MSSSIMScratch(n, C, R, a.device)
+    elif scratch.n < n or (scratch.C, scratch.R) != (C, R) or scratch._partials.device != a.device:
+        raise ValueError('msssim_pairs: scratch is for up to %d pairs [%d,%d,%d] on %s' % (scratch.n, scratch.C, scratch.R, scratch.R,
+                                                                                          scratch._partials.device))
+    S = len(scratch.sides)
+    if out is None:
+        values = torch.empty(n, device=a.device, dtype=torch.float64)
+        terms = torch.empty((n, S), device=a.device, dtype=torch.float64)
+    else:
+        values, terms = out
+        for t, shape in ((values, (n,)), (terms, (n, S))):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError('msssim_pairs: out must be contiguous float64 device tensors [%d] and [%d,%d]' % (n, n, S))
+    partials = scratch.partials(n)
+    cur_a, cur_b = a, b
+    for s in range(S):
+        nxt = (None, None) if s == S - 1 else tuple(t[:n] for t in scratch.pooled[s])
+        msssim_scale(cur_a, cur_b, nxt[0], nxt[1], partials[s], ('quantize' if quantize else 'range') if s == 0 else 'as_is', (lo, hi))
+        cur_a, cur_b = nxt
+    _lib.call('pg_msssim_finish', partials[0].data_ptr(), values.data_ptr(), terms.data_ptr(), n, C, R, _stream())
+    return values, terms
+
+
 # ------------------------------------------------------------------------- Griffin-Lim on the device (csrc/griffinlim.hip)
 GL_MIN_N, GL_MAX_N = 8, 2048       # n_fft = 2 H: a power of two in this range (image heights 4 .. 1024)
 
