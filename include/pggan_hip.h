@@ -54,7 +54,8 @@ int pg_abi_version(void);
  *   xin = x, or (ups != 0) the nearest-neighbour x2 upsampling of x   (network.py:127,129)
  *   y = mask ? z * (mask>0 ? 1 : mask_slope)                          (LeakyReLU' re-applied)
  *            : lrelu_slope(z + bias)      (slope 1.0 == no activation; bias may be NULL)
- *   Hin,Win: dims of xin (AFTER upsampling).  Hout = Hin + 2*pad - KS + 1.  KS in {1,3,4}.
+ *   Hin,Win: dims of xin (AFTER upsampling).  Hout = Hin + 2*pad - KS + 1.  KS in {1,3,4}.  Hin and Win need not be equal;
+ *   Hout and Wout must be powers of two (PG_E_UNSUP otherwise: the 4x4 valid kernel therefore serves 4x4 maps, not e.g. 8x16).
  *   x: [N][Hin/(ups?2:1)][Win/(ups?2:1)][Cin]   y,mask: [N][Hout][Wout][Cout]
  */
 int pg_conv2d_nhwc(const float* x, const float* w, const float* bias, const float* mask, float* y,

@@ -1506,7 +1506,8 @@ int dispatch_conv(ConvP& p, hipStream_t s)
     } else {
         if constexpr (VEC == 4) {
             const long long Mpx = (long long)p.N * p.Hout * p.Wout;
-            if (!p.ups && !p.ypool && !p.yup && !p.pn_r && !p.pnb_y && p.Cin >= 128 && g_tune[PG_TUNE_CONV_TILE] < 0 &&
+            // (conv_ksplit_kernel's epilogue knows fp32 masks only: sign-byte masks / outputs keep the generic tile kernel)
+            if (!p.ups && !p.ypool && !p.yup && !p.pn_r && !p.pnb_y && !p.mask_bytes && !p.y_bytes && !p.ysigns && p.Cin >= 128 && g_tune[PG_TUNE_CONV_TILE] < 0 &&
                 g_tune[PG_TUNE_PATH] != PG_PATH_NO_SMALLMAP_SPLIT && Mpx <= (g_tune[PG_TUNE_PATH] == PG_PATH_SMALLMAP_SPLIT_2304 ? 2304 : 576)) {
                 const int rc = Mpx <= 256 ? launch_ksplit<1>(p, s) : launch_ksplit<2>(p, s);
                 if (rc != PG_E_UNSUP) return rc;
