@@ -432,6 +432,16 @@ int pg_real_prepare_u8(const uint8_t* in, float* out, int64_t planes, int H, int
 int pg_pyramid_level_u8(const uint8_t* in, uint8_t* out, int64_t planes, int H, int W, int depthdiff,
                         float min_in, float max_in, pg_stream_t stream);
 
+/* The real-image batch of a training step from a device-resident uint8 stack, in one launch (csrc/real_batch.hip): for output
+ * image j, level = src[idx[j]] (depthdiff == 0) or its pg_pyramid_level_u8 level (the level bytes clipped to [min_in, max_in] as
+ * there); flip[j] != 0 mirrors the LEVEL image (column r-1-x; flip may be NULL); then pg_real_prepare_u8's fade (alpha < 1) and
+ * range change.  Bit-identical to those two entry points around an index_select and a flip of the last axis.
+ * src [M][C][S][S] uint8, idx [n] int64 and flip [n] uint8 on the device, out [n][C][r][r] fp32 with r = S >> depthdiff.
+ * C in {1, 3} (PG_E_ARG otherwise); S a power of two and r >= 2 (PG_E_ALIGN otherwise); 16-byte aligned src and out.  The
+ * values of idx are NOT checked on the device: every one must be in [0, M). */
+int pg_real_batch_u8(const uint8_t* src, int64_t M, int C, int S, int depthdiff, const int64_t* idx, const uint8_t* flip, int n,
+                     float* out, double alpha, double min_in, double max_in, double min_out, double max_out, pg_stream_t stream);
+
 /* Sample output: replaces ImageSaver.__call__ output_postprocess.py:35-62 up to the PIL hand-off: nearest
  * upsample by `up` (utils.py:33-53), tiled grid of ceil(sqrt(n)) columns, CHW->HWC, range (min_in,max_in)->(0,255)
  * in fp32, round-half-even, clip, uint8.  grid: [grid_h*h*up][grid_w*w*up][C].                                  */

@@ -85,6 +85,7 @@ SIGNATURES = {
     'pg_real_prepare_u8': [P, P, L, I, I, D, D, D, D, D, P],
     'pg_image_grid_u8': [P, P, I, I, I, I, I, F, F, P],
     'pg_pyramid_level_u8': [P, P, L, I, I, I, F, F, P],
+    'pg_real_batch_u8': [P, L, I, I, I, P, P, I, P, D, D, D, D, D, P],
     'pg_zero': [P, L, P],
     'pg_uniform_f32': [P, L, ctypes.c_uint64, ctypes.c_uint64, P],
     'pg_stft_abslog': [P, L, I, P, I, I, I, I, P],

@@ -1,0 +1,297 @@
+"""Device-resident real-image dataset: the reference's ``DepthDataset`` protocol (dataset.py:31-70) on a uint8 image stack
+that lives in HBM, with the whole batch -- gather, pyramid level, mirror, fade-in, dynamic range -- in one launch
+(``ops.real_batch_u8`` / csrc/real_batch.hip).  Nothing crosses PCIe per step and no host worker prepares anything, so the
+stale ``dataset.alpha`` of forked DataLoader workers cannot occur: every batch is made with the depth and alpha of
+the moment it is drawn.
+
+``device='cpu'`` (host mode) evaluates the same definition with numpy in fp64, as the reference computes it; it backs
+``__getitem__`` and is the twin the device path is compared with, bit for bit (tests/golden/io_steps.npz pins both)."""
+import os
+
+import numpy as np
+import torch
+
+UPLOAD_CHUNK_BYTES = 256 << 20          # the stack is uploaded in pieces of at most this size: no host copy of the whole set is made
+
+
+# ------------------------------------------------------------------------------------------------ host definition
+def level_host(images_u8, depthdiff, range_in=(0, 255)):
+    """Pyramid level ``depthdiff`` below a uint8 array [..., S, S] (create_datapoint_from_depth, dataset.py:243-250): the four
+    samples at (y st + {0,1}, x st + {0,1}), st = 2^depthdiff, added in fp32 in the reference's order, / 4, rounded half to even,
+    clipped to ``range_in``, uint8.  ``depthdiff == 0`` is the array itself."""
+    x = np.asarray(images_u8)
+    if depthdiff == 0:
+        return x
+    d = x.astype(np.float32)
+    st = 2 ** int(depthdiff)
+    acc = 0
+    for a in range(2):
+        for b in range(2):
+            acc = acc + d[..., a::st, b::st]
+    acc = acc / 4
+    return np.uint8(np.clip(np.round(acc), np.float32(range_in[0]), np.float32(range_in[1])))
+
+
+def prepare_host(level_u8, alpha, range_in=(0, 255), range_out=(-1, 1)):
+    """DepthDataset.__getitem__ (dataset.py:54-67) for a uint8 array [..., r, r]: fade with the 2x2 box-filtered copy when
+    ``alpha < 1`` (:109-113), adjust_dynamic_range (utils.py:24-30), float32 -- everything in fp64, rounded once."""
+    d = np.asarray(level_u8).astype(np.float64)
+    if alpha < 1.0:
+        lead, r = d.shape[:-2], d.shape[-1]
+        t = d.reshape(lead + (r // 2, 2, r // 2, 2)).mean((-3, -1)).repeat(2, -2).repeat(2, -1)
+        d = d + (t - d) * (1.0 - float(alpha))
+    lo_in, hi_in, lo_out, hi_out = (float(v) for v in tuple(range_in) + tuple(range_out))
+    if (lo_in, hi_in) != (lo_out, hi_out):
+        scale = (hi_out - lo_out) / (hi_in - lo_in)
+        d = (d - lo_in) * scale + lo_out
+    return d.astype(np.float32)
+
+
+def batch_host(stack_u8, idx, flip, depthdiff, alpha, range_in=(0, 255), range_out=(-1, 1)):
+    """What ``ops.real_batch_u8`` computes, on the host: a float32 array [n,C,r,r]."""
+    level = level_host(np.asarray(stack_u8)[np.asarray(idx)], depthdiff, range_in)
+    if flip is not None:
+        f = np.asarray(flip).astype(bool)
+        level = np.where(f[:, None, None, None], level[..., ::-1], level)       # the mirror acts on the LEVEL image
+    return prepare_host(level, alpha, range_in, range_out)
+
+
+# --------------------------------------------------------------------------------------------------- index stream
+class IndexStream(object):
+    """The positions 0, 1, 2, ... of an endless sequence of image indices: ``torch.randperm(M, generator=g)`` per epoch, ``g`` a
+    CPU generator seeded with ``seed`` (the reference's InfiniteRandomSampler, train.py:51-56); ``arange(M)`` per epoch without
+    ``shuffle``.  Mirror flags (``flags=True``) belong to positions too: ``torch.randint(0, 2, (M,), generator=g2,
+    dtype=torch.uint8)`` per epoch, ``g2`` seeded ``seed + 1``.  An epoch's two arrays are made once and moved to ``device`` once;
+    ``take`` hands out slices of them (concatenated on the device across an epoch boundary): no copy and no synchronisation
+    per batch.  ``cursor`` is the next unread position."""
+
+    def __init__(self, M, shuffle=True, seed=0, flags=False, device='cpu'):
+        if int(M) < 1:
+            raise ValueError('an index stream needs at least one image')
+        self.M, self.shuffle, self.flags, self.device = int(M), bool(shuffle), bool(flags), torch.device(device)
+        self._g = torch.Generator().manual_seed(int(seed))
+        self._g2 = torch.Generator().manual_seed(int(seed) + 1)
+        self._epochs = {}                # epoch number -> (idx, flip or None) on ``device``
+        self._made = 0                   # epochs generated so far (they must be drawn in order)
+        self.cursor = 0
+
+    def _epoch(self, e):
+        while self._made <= e:
+            idx = torch.randperm(self.M, generator=self._g) if self.shuffle else torch.arange(self.M)
+            flip = torch.randint(0, 2, (self.M,), generator=self._g2, dtype=torch.uint8) if self.flags else None
+            self._epochs[self._made] = (idx.to(self.device), None if flip is None else flip.to(self.device))
+            self._made += 1
+        return self._epochs[e]
+
+    def take(self, n, rank=0, world=1):
+        """(idx [n] int64, flip [n] uint8 or None) at positions [cursor + rank n, cursor + (rank + 1) n); the cursor moves by n world."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('a draw needs at least one image')
+        start = self.cursor + rank * n
+        self.cursor += n * world
+        for e in [k for k in self._epochs if k < start // self.M]:              # epochs every rank has left behind
+            del self._epochs[e]
+        parts, pos = [], start
+        while pos < start + n:
+            e, off = divmod(pos, self.M)
+            m = min(self.M - off, start + n - pos)
+            idx, flip = self._epoch(e)
+            parts.append((idx[off:off + m], None if flip is None else flip[off:off + m]))
+            pos += m
+        if self.device.type == 'cuda':
+            s = torch.cuda.current_stream()
+            for t in (t for p in parts for t in p if t is not None):
+                t.record_stream(s)                                              # (read on this stream; freed when its epoch is over)
+        if len(parts) == 1:
+            return parts[0]
+        return torch.cat([p[0] for p in parts]), (torch.cat([p[1] for p in parts]) if self.flags else None)
+
+
+def _log2(v):
+    return int(v).bit_length() - 1
+
+
+class DeviceImageDataset(object):
+    """``images``: uint8 numpy array or torch tensor [M,C,R,R], C in {1, 3}, R a power of two >= 4 (ValueError otherwise); at most
+    ``max_images`` of them are used.  The stack is uploaded once (in chunks) and stays on ``device``.
+
+    The stage is dataset depth ``model_depth + model_dataset_depth_offset`` (side 2^depth, so the default offset 2 starts at 4x4).
+    ``pyramid`` picks which of the reference's two behaviours supplies a stage below the source resolution:
+
+      'chain'   the ``preload=True`` pyramid (dataset.py:144-162): level k is made from level k + 1 with depth difference 1 -- a
+                true 2x2 box mean, rounded to uint8 at EVERY level -- once, at construction (``ops.pyramid_level_u8``), and kept
+                (+1/3 memory); batches read the stage's level.
+      'direct'  the ``preload=False`` path (dataset.py:201-203): nothing is stored, every batch is taken from the full-resolution
+                stack with depth difference log2(R) - depth, the reference's 4-SAMPLE SUBSAMPLING (the top-left 2x2 of every
+                2^diff block).
+
+    The two give different images for stages two or more levels below the source; they agree one level below and at the source.
+
+    Protocol of the reference's DepthDataset: ``model_depth`` and ``alpha`` are plain attributes (DepthManager writes them),
+    ``shape``, ``len()``, ``close()``, and ``dataset[i]`` = the reference's host tensor [C,r,r] fp32 of image i at the current depth
+    and alpha (no mirror), so a plain ``DataLoader(dataset)`` still works.
+
+    Batches: ``batch(n)`` -> fp32 [n,C,r,r] on ``device``, issued on the current stream; ``loader(n)`` -> endless iterator of
+    them, what ``DepthManager(create_dataloader_fun=ds.loader, ...)`` takes; ``metric_batches()`` -> ``f(n)`` for
+    ``SWDMonitor(real_batch_fn=...)``.  The training batches follow one ``IndexStream`` whose cursor belongs to the dataset: a
+    loader made at a stage change continues it, and the sequence does not depend on the batch sizes.  ``mirror_augment`` flips
+    images left-right by the stream's per-position flags.  Under data parallelism (``rank`` of ``world``, one seed everywhere) a
+    draw of n takes positions [cursor + rank n, cursor + (rank + 1) n) and moves the cursor by n world: disjoint images of one epoch.
+
+    ``device='cpu'``: host mode, the same definition in numpy (fp64)."""
+
+    def __init__(self, images, model_dataset_depth_offset=2, model_initial_depth=0, alpha=1.0, range_in=(0, 255), range_out=(-1, 1),
+                 pyramid='chain', mirror_augment=False, shuffle=True, seed=0, max_images=None, rank=0, world=1, device='cuda'):
+        if torch.is_tensor(images):
+            ok = images.dtype == torch.uint8
+        else:
+            ok = isinstance(images, np.ndarray) and images.dtype == np.uint8
+        if not ok:
+            raise ValueError('images: expected a uint8 numpy array or torch tensor [M,C,R,R]')
+        if images.ndim != 4 or images.shape[0] < 1:
+            raise ValueError('images: expected [M,C,R,R] with M >= 1, got shape %s' % (tuple(images.shape),))
+        M, C, R, R2 = (int(v) for v in images.shape)
+        if C not in (1, 3):
+            raise ValueError('images: %d channels (1 or 3 are supported)' % C)
+        if R != R2 or R < 4 or R & (R - 1):
+            raise ValueError('images: %dx%d (the side must be a power of two >= 4)' % (R, R2))
+        if max_images is not None:
+            if isinstance(max_images, bool) or int(max_images) != max_images or max_images < 1:
+                raise ValueError('max_images must be None or a positive integer, got %r' % (max_images,))
+            M = min(M, int(max_images))
+        if pyramid not in ('chain', 'direct'):
+            raise ValueError("pyramid must be 'chain' or 'direct', got %r" % (pyramid,))
+        if int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError('rank %r of world %r' % (rank, world))
+        self.model_depth, self.alpha = model_initial_depth, alpha
+        self.model_dataset_depth_offset = int(model_dataset_depth_offset)
+        self.range_in, self.range_out = tuple(range_in), tuple(range_out)
+        self.pyramid, self.mirror_augment, self.shuffle, self.seed = pyramid, bool(mirror_augment), bool(shuffle), int(seed)
+        self.rank, self.world = int(rank), int(world)
+        self.device = torch.device(device)
+        self._shape = (M, C, R, R)
+        self.max_dataset_depth = _log2(R)
+        self.min_dataset_depth = self.max_dataset_depth if pyramid == 'direct' else min(self.max_dataset_depth, max(1, self.model_dataset_depth_offset))
+        self._levels = {self.max_dataset_depth: self._upload(images, M)}
+        for depth in range(self.max_dataset_depth - 1, self.min_dataset_depth - 1, -1):       # 'chain' only
+            self._levels[depth] = self._level_below(self._levels[depth + 1])
+        self._train = IndexStream(M, self.shuffle, self.seed, flags=self.mirror_augment, device=self.device)
+
+    # --------------------------------------------------------------------------------------------- construction
+    @classmethod
+    def from_npy(cls, path, **kw):
+        """The stack of an ``.npy`` file [M,C,R,R] uint8, memory-mapped: only the chunk being uploaded is resident on the host."""
+        return cls(np.load(path, mmap_mode='r'), **kw)
+
+    @classmethod
+    def from_folder(cls, dir_path, imread_mode='L', **kw):
+        """Every file of ``dir_path`` in sorted order, read with PIL in ``imread_mode`` ('L', 'RGB') as the reference's ``load_file``
+        reads it (dataset.py:229-236): [H,W] -> [1,H,W], [H,W,C] -> [C,H,W]."""
+        import PIL.Image
+        files = sorted(os.path.join(dir_path, f) for f in os.listdir(dir_path))
+        if not files:
+            raise ValueError('no files in %s' % dir_path)
+        ims = []
+        for f in files:
+            im = np.asarray(PIL.Image.open(f).convert(imread_mode), dtype=np.uint8)
+            ims.append(im[np.newaxis] if im.ndim == 2 else im.transpose(2, 0, 1))
+            if ims[-1].shape != ims[0].shape:
+                raise ValueError('%s is %s, %s is %s' % (files[0], ims[0].shape, f, ims[-1].shape))
+        return cls(np.stack(ims), **kw)
+
+    def _upload(self, images, M):
+        if self.device.type != 'cuda':
+            host = images[:M] if torch.is_tensor(images) else torch.from_numpy(np.array(images[:M]))
+            return host.contiguous()
+        from . import ops
+        ops.require_gpu()
+        per = int(np.prod(images.shape[1:]))
+        step = max(1, UPLOAD_CHUNK_BYTES // per)
+        dev = torch.empty((M,) + tuple(int(v) for v in images.shape[1:]), dtype=torch.uint8, device=self.device)
+        for a in range(0, M, step):
+            b = min(M, a + step)
+            chunk = images[a:b] if torch.is_tensor(images) else torch.from_numpy(np.array(images[a:b]))      # (a copy: a memory-mapped file is read here)
+            dev[a:b].copy_(chunk)
+        return dev
+
+    def _level_below(self, stack):
+        if stack.is_cuda:
+            from . import ops
+            return ops.pyramid_level_u8(stack, 1, self.range_in)
+        return torch.from_numpy(level_host(stack.numpy(), 1, self.range_in))
+
+    # ------------------------------------------------------------------------------------------------- protocol
+    @property
+    def shape(self):
+        return self._shape
+
+    def __len__(self):
+        return self._shape[0]
+
+    def close(self):
+        """Free the device buffers; the object is of no use afterwards."""
+        self._levels = {}
+        self._train = None
+
+    def _stage(self):
+        """(stack to read, depth difference) of the current ``model_depth``."""
+        if not self._levels:
+            raise RuntimeError('the dataset is closed')
+        depth = int(self.model_depth) + self.model_dataset_depth_offset
+        lowest = self.min_dataset_depth if self.pyramid == 'chain' else 1
+        if not lowest <= depth <= self.max_dataset_depth:
+            raise ValueError('model_depth %r + offset %d is dataset depth %d; this dataset has depths %d .. %d'
+                             % (self.model_depth, self.model_dataset_depth_offset, depth, lowest, self.max_dataset_depth))
+        if self.pyramid == 'chain':
+            return self._levels[depth], 0
+        return self._levels[self.max_dataset_depth], self.max_dataset_depth - depth
+
+    def __getitem__(self, item):
+        i = int(item)
+        if not -len(self) <= i < len(self):
+            raise IndexError('image %d of %d' % (i, len(self)))
+        stack, dd = self._stage()
+        image = stack[i % len(self)].cpu().numpy()
+        return torch.from_numpy(prepare_host(level_host(image, dd, self.range_in), self.alpha, self.range_in, self.range_out))
+
+    # -------------------------------------------------------------------------------------------------- batches
+    def _make(self, idx, flip, alpha):
+        stack, dd = self._stage()
+        if stack.is_cuda:
+            from . import ops
+            return ops.real_batch_u8(stack, idx, flip, dd, alpha, self.range_in, self.range_out)
+        return torch.from_numpy(batch_host(stack.numpy(), idx.numpy(), None if flip is None else flip.numpy(), dd, alpha,
+                                           self.range_in, self.range_out))
+
+    def draw_indices(self, n):
+        """The next ``n`` (image indices, mirror flags or None) of this rank from the training stream; moves the cursor."""
+        if self._train is None:
+            raise RuntimeError('the dataset is closed')
+        return self._train.take(n, self.rank, self.world)
+
+    @property
+    def cursor(self):
+        """Next unread position of the training stream (images drawn so far, over all ranks)."""
+        return self._train.cursor
+
+    def batch(self, n, alpha=None):
+        """fp32 batch [n,C,r,r] at the current ``model_depth``, with ``self.alpha`` unless ``alpha`` is given, on the current stream."""
+        idx, flip = self.draw_indices(n)
+        return self._make(idx, flip, self.alpha if alpha is None else alpha)
+
+    def loader(self, minibatch_size):
+        """Endless iterator of ``batch(minibatch_size)``; every batch is drawn with the depth and alpha of that moment."""
+        while True:
+            yield self.batch(minibatch_size)
+
+    def metric_batches(self, seed=1):
+        """``f(n)`` -> fp32 batch [n,C,r,r] at the current ``model_depth`` with alpha = 1 and no mirror, from an index stream and a
+        cursor of its own: evaluating a metric does not move the training stream."""
+        stream = IndexStream(len(self), self.shuffle, seed, flags=False, device=self.device)
+
+        def real_batch_fn(n):
+            idx, _ = stream.take(n)
+            return self._make(idx, None, 1.0)
+        real_batch_fn.stream = stream
+        return real_batch_fn

@@ -786,6 +786,35 @@ def pyramid_level_u8(batch_u8, depthdiff, range_in=(0, 255)):
     return out
 
 
+def real_batch_u8(stack_u8, idx, flip=None, depthdiff=0, alpha=1.0, range_in=(0, 255), range_out=(-1, 1), check=False):
+    """uint8 device stack [M,C,S,S] -> fp32 batch [n,C,r,r], r = S >> depthdiff, in one launch (pg_real_batch_u8, csrc/real_batch.hip):
+    image ``idx[j]`` (int64 device tensor [n]), its pyramid level (``pyramid_level_u8``), mirrored where ``flip[j] != 0`` (uint8 device
+    tensor [n] or None), faded and range-adjusted (``real_prepare_u8``).  The device does not check ``idx``: ``check=True`` reads its
+    minimum and maximum back (a host synchronisation) and raises IndexError for a value outside [0, M)."""
+    require_gpu()
+    if not torch.is_tensor(stack_u8) or not stack_u8.is_cuda or stack_u8.dtype != torch.uint8 or not stack_u8.is_contiguous() or stack_u8.dim() != 4:
+        raise ValueError('expected a contiguous uint8 device stack [M,C,S,S]')
+    M, C, S, S2 = stack_u8.shape
+    if S != S2 or M < 1:
+        raise ValueError('expected at least one square image, got a stack of shape %s' % (tuple(stack_u8.shape),))
+    if not torch.is_tensor(idx) or idx.device != stack_u8.device or idx.dtype != torch.int64 or not idx.is_contiguous() or idx.dim() != 1 or idx.numel() < 1:
+        raise ValueError('idx: expected a contiguous, non-empty int64 tensor [n] on the device of the stack')
+    n = idx.numel()
+    if flip is not None and (not torch.is_tensor(flip) or flip.device != stack_u8.device or flip.dtype != torch.uint8
+                             or not flip.is_contiguous() or tuple(flip.shape) != (n,)):
+        raise ValueError('flip: expected None or a contiguous uint8 tensor [%d] on the device of the stack' % n)
+    if check:
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= M:
+            raise IndexError('idx holds values in [%d, %d] for a stack of %d images' % (lo, hi, M))
+    depthdiff = int(depthdiff)
+    r = S >> depthdiff if 0 <= depthdiff < 31 else 0
+    out = torch.empty((n, C, r, r), device=stack_u8.device, dtype=torch.float32)
+    _lib.call('pg_real_batch_u8', stack_u8.data_ptr(), M, C, S, depthdiff, idx.data_ptr(), None if flip is None else flip.data_ptr(), n,
+              out.data_ptr(), float(alpha), float(range_in[0]), float(range_in[1]), float(range_out[0]), float(range_out[1]), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------- sliced Wasserstein distance (csrc/swd.hip)
 SWD_DESC = 147                     # PG_SWD_DESC: 3 channels x 7 x 7
 SWD_REDUCE_BLOCKS = 1024           # PG_SWD_REDUCE_BLOCKS
