@@ -561,6 +561,25 @@ int pg_msssim_scale(const float* a, const float* b, float* pool_a, float* pool_b
 int pg_msssim_finish(const double* partials, double* values, double* terms, int64_t n, int C, int R, pg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Nearest training images of generated samples (Karras et al. 2018 show them to tell new images from copies), searched in the uint8
+ * image stack that DeviceImageDataset keeps in HBM (csrc/nn_search.hip; DESIGN.md section 7, restated for the CPU in tests/nn_ref.py).
+ * Integer arithmetic throughout: exact, and the same bits from run to run.
+ *   pg_quantize_u8:       out[i] = clip(rint((in[i] - lo) * (float)(255 / (hi - lo))), 0, 255): pg_image_grid_u8's arithmetic (one fp32
+ *                         rounding per operation, round half to even), element for element -- the levels the saved PNG shows.
+ *   pg_l2dist_u8:         out [K][M] int64, out[k][m] = sum_d (stack[m][d] - queries[k][d])^2 over the D bytes of an image, exact.
+ *                         1 <= K <= PG_NN_MAX_QUERIES per call; D a multiple of 16, stack and queries 16-byte aligned (PG_E_ALIGN
+ *                         otherwise).  Every stack byte is read once per call; the two norms of the expansion come from the
+ *                         registers of the product, no separate pass.  Workgroups split M and D; when D is split the call zeroes
+ *                         out and the slices add with 64-bit integer atomics (order-independent).
+ *   pg_topk_smallest_i64: the k smallest of each of the K rows of dist [K][M], ascending by (value, index) -- equal values: the
+ *                         lower index first -- as values [K][k] and indices [K][k], 1 <= k <= min(M, PG_NN_MAX_TOPK).  No atomics. */
+#define PG_NN_MAX_QUERIES 64
+#define PG_NN_MAX_TOPK 16
+int pg_quantize_u8(const float* in, uint8_t* out, int64_t n, float lo, float hi, pg_stream_t stream);
+int pg_l2dist_u8(const uint8_t* stack, int64_t M, const uint8_t* queries, int K, int64_t D, int64_t* out, pg_stream_t stream);
+int pg_topk_smallest_i64(const int64_t* dist, int K, int64_t M, int k, int64_t* values, int64_t* indices, pg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Gradient exchange of the data-parallel step: RCCL over xGMI (SURVEY.md §8b "the all-reduce itself is a C-ABI call
  * taking ncclComm_t, buffer, count, stream", §8e).  The reference is single-GPU and has no collective; the exchange
  * points are after `D_loss.backward()` trainer.py:98 (before optimizer_d.step() :100) and after `G_loss.backward()`

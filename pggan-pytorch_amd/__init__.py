@@ -9,15 +9,16 @@ from .network import Generator, Discriminator, PGConv2d  # noqa: F401
 from .wgan_gp_loss import wgan_gp_D_loss, wgan_gp_G_loss  # noqa: F401
 from .trainer import Trainer  # noqa: F401
 from .plugins import (Plugin, DepthManager, LRScheduler, RampupLR, TimeMonitor, AbsoluteTimeMonitor, SaverPlugin, OutputGenerator,  # noqa: F401
-                      SWDMonitor, MSSSIMMonitor, load_models, load_smoothed_generator, load_trainer_state)
+                      SWDMonitor, MSSSIMMonitor, NNMonitor, load_models, load_smoothed_generator, load_trainer_state)
 from .optim import FusedAdam  # noqa: F401
 from .ema import GeneratorEMA  # noqa: F401
 from .parallel import DataParallel  # noqa: F401
 from .sound import SoundSaver, DeviceSoundSaver, spectrogram_u8  # noqa: F401
 from .dataset import DeviceImageDataset  # noqa: F401
+from .metrics import NearestNeighbours  # noqa: F401
 from ._lib import PgganLibraryError, LIB_PATH  # noqa: F401
 
 __all__ = ['Generator', 'Discriminator', 'PGConv2d', 'wgan_gp_D_loss', 'wgan_gp_G_loss', 'Trainer', 'Plugin',
-           'DepthManager', 'LRScheduler', 'RampupLR', 'TimeMonitor', 'AbsoluteTimeMonitor', 'SaverPlugin', 'OutputGenerator', 'SWDMonitor', 'MSSSIMMonitor', 'load_models',
+           'DepthManager', 'LRScheduler', 'RampupLR', 'TimeMonitor', 'AbsoluteTimeMonitor', 'SaverPlugin', 'OutputGenerator', 'SWDMonitor', 'MSSSIMMonitor', 'NNMonitor', 'load_models',
            'load_smoothed_generator', 'load_trainer_state', 'FusedAdam', 'GeneratorEMA', 'DataParallel', 'SoundSaver', 'DeviceSoundSaver',
-           'spectrogram_u8', 'DeviceImageDataset']
+           'spectrogram_u8', 'DeviceImageDataset', 'NearestNeighbours']

@@ -110,6 +110,10 @@ SIGNATURES = {
     # multi-scale SSIM between image pairs (csrc/msssim.hip)
     'pg_msssim_scale': [P, P, P, P, P, L, I, I, F, F, P],
     'pg_msssim_finish': [P, P, P, L, I, I, P],
+    # nearest training images (csrc/nn_search.hip)
+    'pg_quantize_u8': [P, P, L, F, F, P],
+    'pg_l2dist_u8': [P, L, P, I, L, P, P],
+    'pg_topk_smallest_i64': [P, I, L, I, P, P, P],
     # gradient exchange (RCCL bound at run time inside the library)
     'pg_rccl_version': [P],
     'pg_comm_unique_id': [P],

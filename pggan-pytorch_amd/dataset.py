@@ -247,6 +247,27 @@ class DeviceImageDataset(object):
             return self._levels[depth], 0
         return self._levels[self.max_dataset_depth], self.max_dataset_depth - depth
 
+    def level_stack(self):
+        """The uint8 stack [M,C,r,r] of the current ``model_depth``: what the batches of this stage are made from before fade-in, mirror
+        and range (``metrics.NearestNeighbours`` searches it).  'chain': the stored level itself, no copy.  'direct': the stack itself at
+        the source resolution; below it the level is made here, ``UPLOAD_CHUNK_BYTES`` of the stack at a time (``ops.pyramid_level_u8``
+        on the device, ``level_host`` in host mode), and is NOT kept -- a caller that needs it repeatedly within a stage keeps it."""
+        stack, dd = self._stage()
+        if dd == 0:
+            return stack
+        M, C, R, _ = self._shape
+        r = R >> dd
+        out = torch.empty((M, C, r, r), dtype=torch.uint8, device=stack.device)
+        step = max(1, UPLOAD_CHUNK_BYTES // (C * R * R))
+        for a in range(0, M, step):
+            b = min(M, a + step)
+            if stack.is_cuda:
+                from . import ops
+                out[a:b].copy_(ops.pyramid_level_u8(stack[a:b], dd, self.range_in))
+            else:
+                out[a:b].copy_(torch.from_numpy(level_host(stack[a:b].numpy(), dd, self.range_in)))
+        return out
+
     def __getitem__(self, item):
         i = int(item)
         if not -len(self) <= i < len(self):

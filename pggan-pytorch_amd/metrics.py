@@ -19,7 +19,12 @@ the paper uses to detect loss of variation: a generator that collapses onto a fe
 independent samples start to resemble each other and the mean MS-SSIM rises.  It is defined per channel, so one-channel (spectrogram)
 networks, which ``SlicedWasserstein`` refuses, have a metric too.  Definition: DESIGN.md section 7 (``ops.msssim_pairs``); it draws
 no random numbers, so it has no seed.  Like the SWD it is UNPINNED: no vectors of the authors' implementation are at hand, the
-values are comparable within a growth stage and between runs of this project."""
+values are comparable within a growth stage and between runs of this project.
+
+``NearestNeighbours``: the nearest training images of generated samples by exact squared L2 distance over the 0..255 levels of the saved
+image -- the paper's answer to "is that a new image or a copy of a training image?", which neither metric above can give (a generator
+that memorises keeps a fine SWD, and MS-SSIM only sees collapse between samples).  Integer arithmetic: exact, the same from run to run."""
+import numpy as np
 import torch
 
 from . import ops
@@ -200,3 +205,109 @@ class MultiScaleSSIM(object):
             self._result = {'msssim': mean, 'std': float((v - mean).pow(2).mean().sqrt()), 'scales': list(self.scales),
                             'terms': [float(t) for t in both[:, 1:].mean(dim=0)]}
         return self._result
+
+
+def _quantise_host(x, drange):
+    """``ops.quantize_u8`` in numpy float32: one rounding per operation, round half to even, clip."""
+    lo, hi = float(drange[0]), float(drange[1])
+    y = (np.asarray(x, dtype=np.float32) - np.float32(lo)) * np.float32(255.0 / (hi - lo))
+    return np.clip(np.round(y), 0, 255).astype(np.uint8)
+
+
+def _search_host(stack, queries, k):
+    """``ops.nn_search_u8`` in numpy int64: (sqdist [K,k], index [K,k]), ascending by (distance, index)."""
+    M = stack.shape[0]
+    x = stack.reshape(M, -1).astype(np.int32)
+    sq, ix = [], []
+    for q in queries.reshape(queries.shape[0], -1).astype(np.int32):
+        d = x - q[None]
+        dist = (d * d).sum(axis=1, dtype=np.int64)                     # (a difference squared is at most 65025)
+        order = np.lexsort((np.arange(M), dist))[:k]
+        sq.append(dist[order])
+        ix.append(order)
+    return np.stack(sq).astype(np.int64), np.stack(ix).astype(np.int64)
+
+
+class NearestNeighbours(object):
+    """``search(samples)``: the ``k`` nearest training images of every generated sample.
+
+    ``source``: a ``DeviceImageDataset`` -- the stack of its current ``model_depth`` is taken at every call (``level_stack()``), so the
+    search follows the growth stage; its ``range_in`` must be (0, 255) -- or a uint8 tensor [M,C,r,r].  The samples (fp32 [K,C,r,r] in
+    ``drange``) are rounded to the 0..255 levels of the saved image (``ops.quantize_u8``) and compared byte for byte with the stack:
+    ``sqdist = sum_d (x_d - q_d)^2``, exact (``ops.nn_search_u8``: one pass over the stack per ``ops.NN_MAX_QUERIES`` queries), neighbours
+    ascending by (sqdist, index).  ``mirror``: also compare every sample's left-right mirror image (the queries are doubled with their
+    flipped copies) and merge the two lists of a sample on the host by (sqdist, index, mirrored) -- for a data set trained with
+    ``mirror_augment`` a mirrored training image is a training image.  1 <= k <= min(M, ops.NN_MAX_TOPK).
+
+    ``device``: None = where the source is; 'cpu' = the numpy twin in int64 (the same definition, no device)."""
+
+    def __init__(self, source, k=1, mirror=False, drange=(-1, 1), device=None):
+        if torch.is_tensor(source):
+            if source.dtype != torch.uint8 or source.dim() != 4 or source.shape[0] < 1:
+                raise ValueError('source: expected a DeviceImageDataset or a uint8 tensor [M,C,r,r]')
+            M, src_device = source.shape[0], source.device
+        elif hasattr(source, 'level_stack'):
+            if tuple(source.range_in) != (0, 255):
+                raise ValueError('source: the data set holds range_in = %r; the search compares 0..255 levels' % (tuple(source.range_in),))
+            M, src_device = len(source), source.device
+        else:
+            raise ValueError('source: expected a DeviceImageDataset or a uint8 tensor [M,C,r,r], got %s' % type(source))
+        if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(M, ops.NN_MAX_TOPK):
+            raise ValueError('k = %r for %d images (1 <= k <= min(M, %d))' % (k, M, ops.NN_MAX_TOPK))
+        if not float(drange[1]) > float(drange[0]):
+            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
+        self.source, self.k, self.mirror = source, int(k), bool(mirror)
+        self.drange = (float(drange[0]), float(drange[1]))
+        self.device = torch.device(src_device if device is None else device)
+
+    def stack(self):
+        """The uint8 stack [M,C,r,r] a search made now would read, on ``device``."""
+        s = self.source if torch.is_tensor(self.source) else self.source.level_stack()
+        return s if s.device == self.device else s.to(self.device)
+
+    def _check(self, samples, stack):
+        if not torch.is_tensor(samples) or samples.dtype != torch.float32 or samples.dim() != 4 or samples.shape[0] < 1 \
+                or tuple(samples.shape[1:]) != tuple(stack.shape[1:]):
+            raise ValueError('expected float32 samples [K,%d,%d,%d], got %s'
+                             % (tuple(stack.shape[1:]) + (tuple(samples.shape) if torch.is_tensor(samples) else type(samples),)))
+
+    def search(self, samples):
+        """{'index': int64 [K,k], 'sqdist': int64 [K,k], 'rms': float64 [K,k] = sqrt(sqdist / D) in 0..255 levels (fp64, host),
+        'mirrored': bool [K,k] (the neighbour matches the sample's mirror image)} as host tensors.  One device synchronisation."""
+        stack = self.stack()
+        self._check(samples, stack)
+        K, k = samples.shape[0], self.k
+        if self.device.type == 'cuda':
+            q = ops.quantize_u8(samples.to(self.device).contiguous(), self.drange)
+            if self.mirror:
+                q = torch.cat([q, q.flip(-1)])
+            sq, ix = ops.nn_search_u8(stack.contiguous(), q, k)
+            both = torch.stack([sq, ix]).cpu().numpy()
+            sq, ix = both[0], both[1]
+        else:
+            q = _quantise_host(samples.cpu().numpy(), self.drange)
+            if self.mirror:
+                q = np.concatenate([q, q[..., ::-1]])
+            sq, ix = _search_host(stack.numpy(), q, k)
+        mirrored = np.zeros((K, k), dtype=bool)
+        if self.mirror:                                                  # two sorted lists of k per sample -> the k smallest keys of both
+            sq2 = np.concatenate([sq[:K], sq[K:]], axis=1)
+            ix2 = np.concatenate([ix[:K], ix[K:]], axis=1)
+            mr2 = np.concatenate([np.zeros((K, k), dtype=bool), np.ones((K, k), dtype=bool)], axis=1)
+            order = np.stack([np.lexsort((mr2[i], ix2[i], sq2[i]))[:k] for i in range(K)])
+            sq, ix, mirrored = (np.take_along_axis(a, order, axis=1) for a in (sq2, ix2, mr2))
+        D = int(np.prod(stack.shape[1:]))
+        return {'index': torch.from_numpy(np.ascontiguousarray(ix)), 'sqdist': torch.from_numpy(np.ascontiguousarray(sq)),
+                'rms': torch.from_numpy(np.sqrt(sq.astype(np.float64) / D)), 'mirrored': torch.from_numpy(np.ascontiguousarray(mirrored))}
+
+    def neighbours(self, result):
+        """The images a ``search`` result names: fp32 [K,k,C,r,r] in ``drange`` on ``device``, mirrored where the result says so
+        (``ops.real_batch_u8`` with alpha 1)."""
+        stack = self.stack()
+        idx, flip = result['index'].reshape(-1), result['mirrored'].reshape(-1).to(torch.uint8)
+        if self.device.type == 'cuda':
+            out = ops.real_batch_u8(stack.contiguous(), idx.to(self.device), flip.to(self.device), 0, 1.0, (0, 255), self.drange)
+        else:
+            from .dataset import batch_host
+            out = torch.from_numpy(batch_host(stack.numpy(), idx.numpy(), flip.numpy(), 0, 1.0, (0, 255), self.drange))
+        return out.view(tuple(result['index'].shape) + tuple(stack.shape[1:]))

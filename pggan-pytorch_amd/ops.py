@@ -1039,6 +1039,83 @@ def msssim_pairs(a, b, drange=(-1, 1), quantize=True, out=None, scratch=None):
     return values, terms
 
 
+# ------------------------------------------------------------------------- nearest training images (csrc/nn_search.hip)
+NN_MAX_QUERIES = 64                # PG_NN_MAX_QUERIES: queries of one pass over the stack; more are split into several passes
+NN_MAX_TOPK = 16                   # PG_NN_MAX_TOPK
+
+
+def _u8_images(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[0] < 1:
+        raise ValueError('%s: expected a contiguous, non-empty uint8 device tensor [n,C,r,r]' % what)
+
+
+def quantize_u8(images, drange=(-1, 1)):
+    """fp32 device images [n,C,r,r] in ``drange`` -> the uint8 levels of the saved image in the same layout (pg_quantize_u8):
+    ``(x - lo) * (255 / (hi - lo))`` in fp32 with one rounding per operation, round half to even, clip to [0, 255] -- the arithmetic of
+    ``image_grid_u8`` and ``msssim_pairs``."""
+    if not torch.is_tensor(images) or not images.is_cuda or images.dtype != torch.float32 or not images.is_contiguous() or images.numel() < 1:
+        raise ValueError('quantize_u8: expected a contiguous, non-empty float32 device tensor')
+    lo, hi = float(drange[0]), float(drange[1])
+    if not hi > lo:
+        raise ValueError('quantize_u8: drange must be (lo, hi) with hi > lo, got %r' % (drange,))
+    require_gpu()
+    out = torch.empty(tuple(images.shape), device=images.device, dtype=torch.uint8)
+    _lib.call('pg_quantize_u8', images.data_ptr(), out.data_ptr(), images.numel(), lo, hi, _stream())
+    return out
+
+
+def l2dist_u8(stack_u8, queries_u8, out=None):
+    """Exact squared L2 distances between uint8 device images: ``stack_u8`` [M,C,r,r], ``queries_u8`` [K,C,r,r] -> int64 [K,M],
+    ``out[k, m] = sum_d (stack[m, d] - queries[k, d])^2`` (pg_l2dist_u8, on the int8 MFMA).  Every pass reads the stack once for up to
+    ``NN_MAX_QUERIES`` queries; more queries take ceil(K / NN_MAX_QUERIES) passes, each into its rows of ``out``.  ``out``: a
+    contiguous int64 device tensor [K,M] to write into.  No host synchronisation."""
+    _u8_images(stack_u8, 'l2dist_u8 stack')
+    _u8_images(queries_u8, 'l2dist_u8 queries')
+    if queries_u8.device != stack_u8.device or tuple(queries_u8.shape[1:]) != tuple(stack_u8.shape[1:]):
+        raise ValueError('l2dist_u8: queries %s on %s do not match the stack %s on %s'
+                         % (tuple(queries_u8.shape), queries_u8.device, tuple(stack_u8.shape), stack_u8.device))
+    M, K = stack_u8.shape[0], queries_u8.shape[0]
+    D = stack_u8.numel() // M
+    if D % 16:
+        raise ValueError('l2dist_u8: an image of %d bytes (a multiple of 16 is required)' % D)
+    if out is None:
+        out = torch.empty((K, M), device=stack_u8.device, dtype=torch.int64)
+    elif (not torch.is_tensor(out) or out.device != stack_u8.device or out.dtype != torch.int64 or not out.is_contiguous()
+          or tuple(out.shape) != (K, M)):
+        raise ValueError('l2dist_u8: out must be a contiguous int64 tensor [%d,%d] on the device of the stack' % (K, M))
+    require_gpu()
+    s = _stream()
+    for k0 in range(0, K, NN_MAX_QUERIES):
+        k1 = min(K, k0 + NN_MAX_QUERIES)
+        _lib.call('pg_l2dist_u8', stack_u8.data_ptr(), M, queries_u8[k0:k1].data_ptr(), k1 - k0, D, out[k0:k1].data_ptr(), s)
+    return out
+
+
+def topk_smallest_i64(dist, k):
+    """int64 device tensor [K,M] -> (values [K,k], indices [K,k]) int64: the ``k`` smallest of every row, ascending by (value, index) --
+    of equal values the lower index comes first (pg_topk_smallest_i64).  1 <= k <= min(M, NN_MAX_TOPK)."""
+    if not torch.is_tensor(dist) or not dist.is_cuda or dist.dtype != torch.int64 or not dist.is_contiguous() or dist.dim() != 2 or dist.numel() < 1:
+        raise ValueError('topk_smallest_i64: expected a contiguous, non-empty int64 device tensor [K,M]')
+    K, M = dist.shape
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(M, NN_MAX_TOPK):
+        raise ValueError('topk_smallest_i64: k = %r for rows of %d (1 <= k <= min(M, %d))' % (k, M, NN_MAX_TOPK))
+    k = int(k)
+    require_gpu()
+    values = torch.empty((K, k), device=dist.device, dtype=torch.int64)
+    indices = torch.empty((K, k), device=dist.device, dtype=torch.int64)
+    _lib.call('pg_topk_smallest_i64', dist.data_ptr(), K, M, k, values.data_ptr(), indices.data_ptr(), _stream())
+    return values, indices
+
+
+def nn_search_u8(stack_u8, queries_u8, k=1):
+    """The ``k`` nearest stack images of every query by exact squared L2 distance over the uint8 levels: ``(sqdist [K,k], index [K,k])``,
+    int64 device tensors, ascending by (distance, index).  ``l2dist_u8`` followed by ``topk_smallest_i64``; ``k > M`` is a ValueError."""
+    _u8_images(stack_u8, 'nn_search_u8 stack')
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(stack_u8.shape[0], NN_MAX_TOPK):
+        raise ValueError('nn_search_u8: k = %r for a stack of %d images (1 <= k <= min(M, %d))' % (k, stack_u8.shape[0], NN_MAX_TOPK))
+    return topk_smallest_i64(l2dist_u8(stack_u8, queries_u8), k)
+
+
 # ------------------------------------------------------------------------- Griffin-Lim on the device (csrc/griffinlim.hip)
 GL_MIN_N, GL_MAX_N = 8, 2048       # n_fft = 2 H: a power of two in this range (image heights 4 .. 1024)
 

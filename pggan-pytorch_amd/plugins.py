@@ -439,3 +439,78 @@ class MSSSIMMonitor(Plugin):
 
     def end(self, *args):
         self.epoch(*args)
+
+
+class NNMonitor(Plugin):
+    """Novelty check per tick (``metrics.NearestNeighbours``; the reference reports none): every ``nn_ticks`` ticks and at the end,
+    ``num_samples`` images of ``G.forward(sample_fn(num_samples).cuda())`` -- of the smoothed generator when the trainer keeps one
+    (``smoothed`` as in ``OutputGenerator``) -- are searched for their ``k`` nearest training images in ``dataset`` (a
+    ``DeviceImageDataset``; the stack of the current growth stage is searched) by exact L2 distance over the 0..255 levels of the saved
+    image.  Writes ``stats['nn_rms']``, the mean over the samples of the distance to the nearest training image as an RMS difference per
+    byte in levels, and ``stats['nn_rms_min']``, the smallest of them -- the most suspicious sample: a value near 0 is a copy -- under the
+    stat-dict convention of the other monitors.  ``mirror``: also match mirrored training images; None takes ``dataset.mirror_augment``.
+    Rank 0 evaluates (replicas are identical; every rank's shard is NOT searched: the distances are to rank 0's images).
+
+    Every post-processor gets ONE batch of (k + 1)^2 images as ``proc(batch, 'nn_%06d' % kimg)``: the first k + 1 samples, each followed
+    by its k neighbours.  The image grid is ceil(sqrt(n)) = k + 1 wide, so a row of ``fakes_nn_<kimg>.png`` is a sample and, to its
+    right, its nearest training images in ascending distance.  A post-processor with ``accepts_device_tensors`` gets the device tensor.
+
+    The default period follows docs/experiments_nn.md: a pass over the stack measured 0.39 ms per GB at 1024x1024 (2.6 TB/s with 64
+    queries), i.e. 36 ms for 30 000 images of 3 x 1024^2 by proportion (that size itself was not run), 64 samples and their mirrors are
+    two passes, and the 64 generator passes are bounded by 64/3 measured train steps of 10.1 ms = 0.22 s; an evaluation is under 0.3 s,
+    and under 1 % of a 3.3 s tick of 1 kimg (the rule of docs/experiments_swd.md) needs ticks >= 100 x 0.3 / 3.3 = 9: 10."""
+
+    def __init__(self, dataset, sample_fn, num_samples=64, k=3, nn_ticks=10, postprocessors=(), smoothed=None, mirror=None,
+                 drange=(-1, 1)):
+        super(NNMonitor, self).__init__([(nn_ticks, 'epoch'), (1, 'end')])
+        if isinstance(k, bool) or int(k) != k or int(k) < 1:
+            raise ValueError('k must be a positive integer, got %r' % (k,))
+        if int(num_samples) != num_samples or int(num_samples) < int(k) + 1:
+            raise ValueError('num_samples = %r: the sheet shows k + 1 = %d samples' % (num_samples, int(k) + 1))
+        self.dataset, self.sample_fn = dataset, sample_fn
+        self.num_samples, self.k = int(num_samples), int(k)
+        self.postprocessors = postprocessors
+        self.smoothed = smoothed
+        self.mirror = bool(getattr(dataset, 'mirror_augment', False)) if mirror is None else bool(mirror)
+        self.drange = drange
+        self._nn = None
+
+    def register(self, trainer):
+        _check_smoothed(trainer, self.smoothed, 'NNMonitor')
+        self.trainer = trainer
+
+    def _search(self):
+        if self._nn is None:
+            from .metrics import NearestNeighbours
+            self._nn = NearestNeighbours(self.dataset, k=self.k, mirror=self.mirror, drange=self.drange)
+        return self._nn
+
+    def epoch(self, epoch_index):
+        tr = self.trainer
+        if tr.parallel is not None and tr.parallel.rank != 0:
+            return
+        import torch
+        nn = self._search()
+        samples = _output_generator(tr, self.smoothed).forward(self.sample_fn(self.num_samples).cuda())
+        res = nn.search(samples)
+        nearest = res['rms'][:, 0].numpy()                                 # fp64 on the host
+        tr.stats['nn_rms'] = dict(log_name='nn_rms', log_epoch_fields=_STAT_FMT, val=float(nearest.mean()))
+        tr.stats['nn_rms_min'] = dict(log_name='nn_rms_min', log_epoch_fields=_STAT_FMT, val=float(nearest.min()))
+        if not self.postprocessors:
+            return
+        rows = self.k + 1
+        near = nn.neighbours({name: res[name][:rows] for name in ('index', 'mirrored')})          # [rows, k, C, r, r]
+        shown = samples[:rows].to(near.device)
+        batch = torch.cat([shown.unsqueeze(1), near], dim=1).reshape((rows * rows,) + tuple(shown.shape[1:]))
+        description = 'nn_%06d' % (tr.cur_nimg // 1000)
+        host = None
+        for proc in self.postprocessors:
+            if getattr(proc, 'accepts_device_tensors', False):
+                proc(batch, description)
+            else:
+                if host is None:
+                    host = batch.cpu().numpy()
+                proc(host, description)
+
+    def end(self, *args):
+        self.epoch(*args)
