@@ -580,6 +580,52 @@ int pg_l2dist_u8(const uint8_t* stack, int64_t M, const uint8_t* queries, int K,
 int pg_topk_smallest_i64(const int64_t* dist, int K, int64_t M, int k, int64_t* values, int64_t* indices, pg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Statistics of the training process (csrc/telemetry.hip; DESIGN.md section 7, restated for the CPU in tests/telemetry_ref.py): the
+ * losses of every iteration and the per-layer norms of a network's flat parameter / Adam-moment buffers, without a host
+ * synchronisation per iteration.  The reference reads each loss on the host every iteration (plugins.py:102-111).  Everything is fp64
+ * in a fixed order and nothing uses atomics: the same inputs give the same bits.
+ *   pg_scalar_stats_push: ONE launch of one workgroup for K <= PG_STATS_MAX_SOURCES sources.  sources / lengths are HOST arrays of K
+ *                         entries, read before the call returns and passed in the kernel arguments (no copy to the device): source k
+ *                         is a device fp32 pointer to lengths[k] elements, 1 <= lengths[k] <= PG_STATS_MAX_LENGTH (PG_E_ARG
+ *                         otherwise); a NULL pointer skips slot k.  The VALUE of a source is the mean of its elements in fp64: 64
+ *                         running sums (sum l takes elements l, l + 64, ... in that order from 0.0), combined pairwise with strides
+ *                         32, 16, 8, 4, 2, 1 (sum i += sum i + stride), divided by the length.  It is folded into slot k of `record`
+ *                         [K][PG_STATS_RECORD] doubles on the device:
+ *                             {n_finite, sum, sumsq, min, max, last, n_nonfinite, first_bad}
+ *                         A NaN / +-Inf value is counted in n_nonfinite and becomes `last`; it never enters sum, sumsq, min or max.
+ *                         first_bad is the 0-based index, among the slot's pushes since the last reset, of the first such value, -1
+ *                         while there is none.  RESET IS A FLAG OF THE PUSH: reset != 0 first puts all K slots (skipped ones
+ *                         included) into the state {0, 0, 0, +Inf, -Inf, NaN, 0, -1} and then folds the sources of this call;
+ *                         sources may then be NULL (a reset alone).  The record is read and written by this call only; pushes to one
+ *                         record must be ordered (one stream, or events).
+ *   pg_segment_stats_plan:   HOST only, no device call.  Cuts S segments (offsets[s], lengths[s]) of a flat buffer of n_flat floats
+ *                         into chunks of at most PG_SEG_CHUNK floats, segment after segment, a chunk never spanning two segments:
+ *                         chunks [nchunks][2] = (offset, length), ranges [S][2] = (first chunk, chunk count) of every segment,
+ *                         *nchunks = the total.  chunks == NULL: only the count (call twice).  Offsets must be multiples of 4
+ *                         elements (PG_E_ALIGN: the networks' layout guarantees it); lengths >= 1 and every segment inside the
+ *                         buffer (PG_E_ARG).  Segments may come in any order and need not cover the buffer.
+ *   pg_segment_stats_f32:    chunks: that table on the DEVICE (uploaded once by the caller).  One workgroup per chunk writes
+ *                         partials[chunk] = {sum, sumsq, maxabs, n_nonfinite} of the chunk's finite elements in fp64 -- sumsq is
+ *                         sum (double)x * (double)x, every term exact; NaN / +-Inf elements are counted and left out of the other
+ *                         three.  16-byte loads, scalar loads for the up to three elements behind the last whole group, a fixed
+ *                         tree through LDS (csrc/telemetry.hip states the order).  flat: 16-byte aligned (PG_E_ALIGN).  A chunk
+ *                         that does not lie inside [0, n_flat) is clipped, never read.
+ *   pg_segment_stats_finish: ranges on the device; out [S][4] doubles: segment s = its partials combined in ascending chunk order
+ *                         (sum, sumsq, n_nonfinite by addition from 0.0; maxabs by maximum).  A segment's numbers depend on its own
+ *                         elements only. */
+#define PG_STATS_MAX_SOURCES 8
+#define PG_STATS_RECORD 8
+#define PG_STATS_MAX_LENGTH 4096
+#define PG_SEG_CHUNK 8192
+int pg_scalar_stats_push(double* record, const float* const* sources /* host */, const int* lengths /* host */, int K, int reset,
+                         pg_stream_t stream);
+int pg_segment_stats_plan(const int64_t* offsets /* host */, const int64_t* lengths /* host */, int S, int64_t n_flat,
+                          int64_t* chunks /* host, may be NULL */, int64_t capacity, int64_t* ranges /* host */, int64_t* nchunks);
+int pg_segment_stats_f32(const float* flat, int64_t n_flat, const int64_t* chunks, int64_t nchunks, double* partials,
+                         pg_stream_t stream);
+int pg_segment_stats_finish(const double* partials, int64_t nchunks, const int64_t* ranges, int S, double* out, pg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Gradient exchange of the data-parallel step: RCCL over xGMI (SURVEY.md §8b "the all-reduce itself is a C-ABI call
  * taking ncclComm_t, buffer, count, stream", §8e).  The reference is single-GPU and has no collective; the exchange
  * points are after `D_loss.backward()` trainer.py:98 (before optimizer_d.step() :100) and after `G_loss.backward()`

@@ -114,6 +114,11 @@ SIGNATURES = {
     'pg_quantize_u8': [P, P, L, F, F, P],
     'pg_l2dist_u8': [P, L, P, I, L, P, P],
     'pg_topk_smallest_i64': [P, I, L, I, P, P, P],
+    # loss and per-layer weight statistics (csrc/telemetry.hip)
+    'pg_scalar_stats_push': [P, P, P, I, I, P],
+    'pg_segment_stats_plan': [P, P, I, L, P, L, P, P],
+    'pg_segment_stats_f32': [P, L, P, L, P, P],
+    'pg_segment_stats_finish': [P, L, P, I, P, P],
     # gradient exchange (RCCL bound at run time inside the library)
     'pg_rccl_version': [P],
     'pg_comm_unique_id': [P],

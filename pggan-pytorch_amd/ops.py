@@ -1239,3 +1239,83 @@ def griffin_lim(images, x0, hop, rounds, mode='abslog', drange=(-1, 1), round_ho
         if round_hook is not None:
             round_hook(i, prev, x)
     return x
+
+
+# ------------------------------------------------------------------------- loss and weight statistics (csrc/telemetry.hip)
+STATS_MAX_SOURCES, STATS_RECORD, STATS_MAX_LENGTH, SEG_CHUNK = 8, 8, 4096, 8192      # PG_STATS_* / PG_SEG_CHUNK of include/pggan_hip.h
+
+
+def scalar_stats_record(K, device):
+    """A record of ``K`` slots for ``scalar_stats_push``: float64 [K, STATS_RECORD] on ``device``, uninitialised (the first push
+    carries ``reset=True``)."""
+    if isinstance(K, bool) or int(K) != K or not 1 <= K <= STATS_MAX_SOURCES:
+        raise ValueError('scalar_stats_record: %r slots (1 .. %d)' % (K, STATS_MAX_SOURCES))
+    return torch.empty((int(K), STATS_RECORD), device=device, dtype=torch.float64)
+
+
+def scalar_stats_push(record, sources, reset=False):
+    """Fold the means of up to ``STATS_MAX_SOURCES`` small fp32 device tensors into ``record`` (``scalar_stats_record``), slot k from
+    ``sources[k]`` (None: the slot is skipped): ONE launch on the current stream, no copy, no host synchronisation
+    (pg_scalar_stats_push; the record's layout and the order of the sums are stated in include/pggan_hip.h).  ``reset``: every slot is
+    put into its empty state before the sources are folded.  A source is contiguous with 1 .. ``STATS_MAX_LENGTH`` elements of any shape."""
+    if (not torch.is_tensor(record) or not record.is_cuda or record.dtype != torch.float64 or not record.is_contiguous()
+            or record.dim() != 2 or record.shape[1] != STATS_RECORD or not 1 <= record.shape[0] <= STATS_MAX_SOURCES):
+        raise ValueError('scalar_stats_push: record must be a contiguous float64 device tensor [K <= %d, %d]' % (STATS_MAX_SOURCES, STATS_RECORD))
+    K = record.shape[0]
+    if len(sources) != K:
+        raise ValueError('scalar_stats_push: %d sources for a record of %d slots' % (len(sources), K))
+    ptrs, lens = (ctypes.c_void_p * K)(), (ctypes.c_int * K)()
+    for k, t in enumerate(sources):
+        if t is None:
+            continue
+        if (not torch.is_tensor(t) or t.device != record.device or t.dtype != torch.float32 or not t.is_contiguous()
+                or not 1 <= t.numel() <= STATS_MAX_LENGTH):
+            raise ValueError('scalar_stats_push: source %d must be a contiguous float32 tensor of 1 .. %d elements on %s'
+                             % (k, STATS_MAX_LENGTH, record.device))
+        ptrs[k], lens[k] = t.data_ptr(), t.numel()
+    require_gpu()
+    _lib.call('pg_scalar_stats_push', record.data_ptr(), ptrs, lens, K, 1 if reset else 0, _stream())
+    return record
+
+
+def segment_stats_plan(segments, n_flat):
+    """The chunk table of ``segment_stats`` for ``segments`` = [(offset, length), ...] of a flat buffer of ``n_flat`` floats, cut by the
+    library's own rule (pg_segment_stats_plan; host only, no device): ``(chunks [nchunks, 2], ranges [S, 2])`` int64 host tensors.
+    An offset that is no multiple of 4 elements is PG_E_ALIGN, a segment outside the buffer or an empty one PG_E_ARG (RuntimeError)."""
+    S = len(segments)
+    if S < 1:
+        raise ValueError('segment_stats_plan: no segments')
+    offs = (ctypes.c_int64 * S)(*[int(o) for o, _ in segments])
+    lens = (ctypes.c_int64 * S)(*[int(n) for _, n in segments])
+    count = ctypes.c_int64(0)
+    _lib.call('pg_segment_stats_plan', offs, lens, S, int(n_flat), None, 0, None, ctypes.addressof(count))
+    chunks = torch.empty((count.value, 2), dtype=torch.int64)
+    ranges = torch.empty((S, 2), dtype=torch.int64)
+    _lib.call('pg_segment_stats_plan', offs, lens, S, int(n_flat), chunks.data_ptr(), count.value, ranges.data_ptr(), ctypes.addressof(count))
+    return chunks, ranges
+
+
+def segment_stats(flat, chunks, ranges, partials=None):
+    """{sum, sumsq, maxabs, n_nonfinite} over the finite elements of every segment of the flat fp32 device buffer ``flat``: float64
+    device tensor [S, 4] (pg_segment_stats_f32 + pg_segment_stats_finish: two launches on the current stream, no atomics, the same
+    bits for the same input, a segment's numbers independent of the other segments').  ``chunks`` / ``ranges``: the tables of
+    ``segment_stats_plan(segments, flat.numel())`` as int64 tensors ON THE DEVICE (uploaded once by the caller).  ``partials``: float64
+    device scratch [nchunks, 4] to reuse."""
+    if not torch.is_tensor(flat) or not flat.is_cuda or flat.dtype != torch.float32 or not flat.is_contiguous() or flat.numel() < 1:
+        raise ValueError('segment_stats: expected a contiguous, non-empty float32 device tensor')
+    for t, what in ((chunks, 'chunks'), (ranges, 'ranges')):
+        if (not torch.is_tensor(t) or t.device != flat.device or t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 2
+                or t.shape[1] != 2 or t.shape[0] < 1):
+            raise ValueError('segment_stats: %s must be a contiguous int64 tensor [n, 2] on the device of the buffer' % what)
+    nchunks, S = chunks.shape[0], ranges.shape[0]
+    if partials is None:
+        partials = torch.empty((nchunks, 4), device=flat.device, dtype=torch.float64)
+    elif (not torch.is_tensor(partials) or partials.device != flat.device or partials.dtype != torch.float64
+          or not partials.is_contiguous() or tuple(partials.shape) != (nchunks, 4)):
+        raise ValueError('segment_stats: partials must be a contiguous float64 tensor [%d, 4] on the device of the buffer' % nchunks)
+    require_gpu()
+    out = torch.empty((S, 4), device=flat.device, dtype=torch.float64)
+    s = _stream()
+    _lib.call('pg_segment_stats_f32', flat.data_ptr(), flat.numel(), chunks.data_ptr(), nchunks, partials.data_ptr(), s)
+    _lib.call('pg_segment_stats_finish', partials.data_ptr(), nchunks, ranges.data_ptr(), S, out.data_ptr(), s)
+    return out

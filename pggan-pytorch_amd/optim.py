@@ -37,6 +37,18 @@ class FusedAdam(torch.optim.Optimizer):
         self._nets.extend(nets)
         return self
 
+    def flat_moments(self, net):
+        """Read-only access to Adam's two moments of ``net``: ``(m, v)``, flat fp32 tensors aligned element for element with
+        ``net._flat_param`` (the padding between parameters and not-yet-updated parameters hold zeros), or None before the first step
+        (or load_state_dict) on that network's current buffer.  With beta1 = 0, ``m`` is exactly the last gradient x ``grad_scale``."""
+        flat = getattr(net, '_flat_param', None)
+        if flat is None:
+            return None
+        for base, m, v in self._flat.values():
+            if base == flat.data_ptr() and m.numel() == flat.numel():
+                return m, v
+        return None
+
     def _flat_state(self, gi, group):
         params = group['params']
         probe = params[0].data_ptr()              # a re-flatten moves every parameter: the first one's address tells

@@ -5,8 +5,10 @@ from PyTorch after 0.3, so the minimal ``Plugin`` protocol is restated here: an 
 ``trigger_interval = [(n, unit), ...]``, ``register(trainer)`` and one method per unit
 (``iteration`` / ``epoch`` / ``s`` / ``end``) — exactly what ``Trainer.call_plugins`` relies on.
 All schedule arithmetic is Python int (+ one IEEE double division for alpha): bit-exact by construction."""
+import math
 import os
 import time
+import warnings
 from datetime import timedelta
 from glob import glob
 
@@ -511,6 +513,155 @@ class NNMonitor(Plugin):
                 if host is None:
                     host = batch.cpu().numpy()
                 proc(host, description)
+
+    def end(self, *args):
+        self.epoch(*args)
+
+
+class LossMonitor(Plugin):
+    """The losses of a run per tick (replaces the reference's four ``EfficientLossMonitor``s, train.py:170-171 / plugins.py:102-111, which
+    read every loss on the host every iteration).  ``iteration(i, *losses)`` makes ONE ``telemetry.ScalarStats.push`` of the tensors the
+    trainer hands over, in ``names``' order (``Trainer`` passes G_loss, D_loss, D_real, D_fake; the per-sample ``[N, 1]`` losses count
+    with their mean, as in the reference): one library call, no host synchronisation -- the host keeps running ahead of the device.
+    ``epoch`` makes one ``read`` (a copy of K x 64 bytes; the tick boundary waits for the device anyway) and writes, for every name,
+    ``stats[name]`` under the stat-dict convention of the other monitors (``log_name``, ``log_epoch_fields=['{val:.4f}']``, ``val`` = the mean
+    over the tick's iterations) plus the legacy monitor's ``last`` and ``epoch_mean`` and ``min``, ``max``, ``std``, ``count``, ``nonfinite``,
+    ``first_bad``.  The statistics start afresh with every tick; ``end`` reports what a last, unfinished tick has gathered.  A NaN or
+    infinite loss is counted, never averaged; ``HealthMonitor`` turns it into an error.
+
+    Stream order: the push runs on the stream that is current when the trainer calls its plugins -- the stream the loss
+    functions were called on.  Eagerly, the loss block is the last launch of the forward schedule on that stream; a replayed step
+    (launch plan or hipGraph) hands out copies of its reused loss buffer made on that stream after the replay.  Either way the
+    push is behind the producer, and the tensors it reads are the caller's own, so the next replay cannot overwrite them.
+    Host tensors or Python floats from a foreign loss go through the numpy twin.  Every rank keeps its own record."""
+
+    def __init__(self, names=('G_loss', 'D_loss', 'D_real', 'D_fake')):
+        super(LossMonitor, self).__init__([(1, 'iteration'), (1, 'epoch'), (1, 'end')])
+        from .telemetry import ScalarStats
+        self.scalars = ScalarStats(names)
+        self.names = self.scalars.names
+        self.last = None                 # (tick index, ScalarStats.read result) of the last report
+
+    def register(self, trainer):
+        self.trainer = trainer
+        trainer.loss_monitor = self      # HealthMonitor looks here
+        for name in self.names:
+            trainer.stats[name] = dict(log_name=name, log_epoch_fields=['{val:.4f}'], val=float('nan'), last=float('nan'),
+                                       epoch_mean=float('nan'))
+
+    def iteration(self, i, *losses):
+        if len(losses) < len(self.names):
+            raise ValueError('LossMonitor: the trainer handed over %d values for %r' % (len(losses), self.names))
+        self.scalars.push(*losses[:len(self.names)])
+
+    def epoch(self, epoch_index):
+        res = self.scalars.read(reset=True)
+        self.last = (epoch_index, res)
+        for name in self.names:
+            r = res[name]
+            self.trainer.stats[name] = dict(log_name=name, log_epoch_fields=['{val:.4f}'], val=r['mean'], last=r['last'],
+                                            epoch_mean=r['mean'], min=r['min'], max=r['max'], std=r['std'], count=r['count'],
+                                            nonfinite=r['nonfinite'], first_bad=r['first_bad'])
+
+    def end(self, *args):
+        if not self.scalars.empty:                                       # (iterations since the last tick closed)
+            self.epoch(*args)
+
+
+class HealthMonitor(Plugin):
+    """Numerical guard and per-layer norms of D and G (the reference has neither): every ``health_ticks`` ticks and at the end, after
+    ``engine.wait_pending(net)``, ONE ``telemetry.SegmentStats.measure`` of each network's flat parameters and -- when its optimizer is a
+    ``FusedAdam`` -- one of Adam's first moment (``FusedAdam.flat_moments``), segmented into the weight and the bias of every layer.  With a
+    ``torch.optim`` optimizer only the weights are measured.  Writes, under the stat-dict convention of the other monitors,
+    ``stats['G_wnorm' | 'D_wnorm']`` (the L2 norm over all segments), ``stats['G_gnorm' | 'D_gnorm']`` and ``stats['G_gmax' | 'D_gmax']`` (L2
+    norm and largest magnitude of the first moment).  The g-statistics equal those of the last gradient x ``grad_scale`` EXACTLY when
+    beta1 = 0 (the reference's Adam: train.py:148-149); with any other beta1 they are those of Adam's running gradient average.
+    ``per_layer=True`` adds one stat per layer (``'G_wnorm/blocks.3.c1.weight'`` ...); ``report()`` returns the whole table of the last
+    evaluation as a list of dicts (net, layer, offset, length, wnorm, wmax, w_nonfinite, gnorm, gmax, g_nonfinite).
+
+    On any NaN / +-Inf element in a parameter or moment segment, or any non-finite push of a registered ``LossMonitor`` in the tick,
+    ``on_nonfinite='raise'`` raises ``telemetry.TrainingDiverged`` and ``'warn'`` warns (RuntimeWarning); the message names the network,
+    every affected layer with its count, the loss with ``first_bad``, and the kimg.  Register it BEFORE ``SaverPlugin``: plugins due at the
+    same tick fire in registration order, so the guard fires first and the poisoned snapshot is never written.  Rank 0 evaluates
+    (replicas are identical)."""
+
+    def __init__(self, health_ticks=1, on_nonfinite='raise', per_layer=False):
+        super(HealthMonitor, self).__init__([(health_ticks, 'epoch'), (1, 'end')])
+        if on_nonfinite not in ('raise', 'warn'):
+            raise ValueError("on_nonfinite must be 'raise' or 'warn', got %r" % (on_nonfinite,))
+        self.on_nonfinite, self.per_layer = on_nonfinite, bool(per_layer)
+        self._seg = {}                   # net name -> (flat buffer address, SegmentStats)
+        self._table = []
+
+    def register(self, trainer):
+        self.trainer = trainer
+
+    def report(self):
+        return [dict(row) for row in self._table]
+
+    def _segments(self, which, net):
+        from .telemetry import SegmentStats
+        hit = self._seg.get(which)
+        if hit is None or hit[0] != net._flat_param.data_ptr():
+            hit = self._seg[which] = (net._flat_param.data_ptr(), SegmentStats.for_network(net))
+        return hit[1]
+
+    def epoch(self, epoch_index):
+        tr = self.trainer
+        if getattr(tr, 'parallel', None) is not None and tr.parallel.rank != 0:
+            return
+        from . import engine
+        from .telemetry import TrainingDiverged
+        fmt = ['{val:.4g}']
+        table, problems = [], []
+        for which, net, opt in (('D', tr.D, tr.optimizer_d), ('G', tr.G, tr.optimizer_g)):
+            flat = getattr(net, '_flat_param', None)
+            if flat is None:
+                continue                                                 # a foreign network: nothing to segment
+            if flat.is_cuda:
+                engine.wait_pending(net)                                 # a deferred update of this network (second stream)
+            seg = self._segments(which, net)
+            w = seg.measure(flat)
+            moments = opt.flat_moments(net) if hasattr(opt, 'flat_moments') else None
+            g = seg.measure(moments[0]) if moments is not None else None
+            w = w.cpu().numpy()
+            g = g.cpu().numpy() if g is not None else None
+            tr.stats[which + '_wnorm'] = dict(log_name=which + '_wnorm', log_epoch_fields=fmt, val=math.sqrt(float(w[:, 1].sum())))
+            if g is not None:
+                tr.stats[which + '_gnorm'] = dict(log_name=which + '_gnorm', log_epoch_fields=fmt, val=math.sqrt(float(g[:, 1].sum())))
+                tr.stats[which + '_gmax'] = dict(log_name=which + '_gmax', log_epoch_fields=fmt, val=float(g[:, 2].max()))
+            bad = []
+            for i, (name, (off, n)) in enumerate(zip(seg.names, seg.segments)):
+                row = dict(net=which, layer=name, offset=off, length=n, wnorm=math.sqrt(float(w[i, 1])), wmax=float(w[i, 2]),
+                           w_nonfinite=int(w[i, 3]), gnorm=None, gmax=None, g_nonfinite=None)
+                if g is not None:
+                    row.update(gnorm=math.sqrt(float(g[i, 1])), gmax=float(g[i, 2]), g_nonfinite=int(g[i, 3]))
+                table.append(row)
+                if self.per_layer:
+                    for key in ('wnorm', 'gnorm'):
+                        if row[key] is not None:
+                            stat = '%s_%s/%s' % (which, key, name)
+                            tr.stats[stat] = dict(log_name=stat, log_epoch_fields=fmt, val=row[key])
+                if row['w_nonfinite']:
+                    bad.append('%s: %d of %d weights' % (name, row['w_nonfinite'], n))
+                if row['g_nonfinite']:
+                    bad.append('%s: %d of %d first-moment elements' % (name, row['g_nonfinite'], n))
+            if bad:
+                problems.append('%s has non-finite values in %s' % (which, '; '.join(bad)))
+        self._table = table
+        lm = getattr(tr, 'loss_monitor', None)
+        if lm is not None:
+            # this tick's report when the loss monitor has already fired (it was registered first), else a look at its record
+            res = lm.last[1] if lm.last is not None and lm.last[0] == epoch_index and lm.scalars.empty else lm.scalars.read(reset=False)
+            for name in lm.names:
+                if res[name]['nonfinite']:
+                    problems.append('loss %s was non-finite in %d iterations of this tick, first_bad = %d (last value %r)'
+                                    % (name, res[name]['nonfinite'], res[name]['first_bad'], res[name]['last']))
+        if problems:
+            msg = 'training diverged at %.3f kimg (tick %s): %s' % (tr.cur_nimg / 1000., epoch_index, '. '.join(problems))
+            if self.on_nonfinite == 'raise':
+                raise TrainingDiverged(msg)
+            warnings.warn(msg, RuntimeWarning)
 
     def end(self, *args):
         self.epoch(*args)
