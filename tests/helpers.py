@@ -48,6 +48,33 @@ def reference_grads(net):
     return out
 
 
+# Bounds on ``trace_movement_errors`` (docs/experiments_optimizer_tests.md §5): 4 x the largest per-tensor value measured against the
+# fixture, rounded up to one significant digit -- two fp32 evaluations in different summation orders can disagree with each other by as
+# much as either disagrees with the fixture.  Host tier (tests/emu_ops.py): 3.8e-5 measured.  HIP path on an MI355X: 4.82e-5 (largest of
+# 9 runs).  A step wrong by 2 % reads 1.96e-2 at the least on either tier.
+TRACE_MOVEMENT_TOL_HOST = 2e-4
+TRACE_MOVEMENT_TOL_GPU = 2e-4
+
+
+def trace_movement_errors(data, **nets):
+    """How well the networks' weights MOVED as the trace16 fixture's did over its 14 iterations: {tensor: relative L2 error of the
+    movement, ||(w - w0) - (w1 - w0)||_2 / ||w1 - w0||_2} from the fixture's ``G0/D0`` (start) and ``G1/D1`` (end) entries, for
+    ``G=`` / ``D=`` networks after the run.  A tensor the fixture did not move must be bit-identical to its start (asserted here)."""
+    out = {}
+    for pre, net in sorted(nets.items()):
+        for k, v in net.reference_state_dict().items():
+            if not torch.is_tensor(v):
+                continue
+            w0, w1 = data['%s0/%s' % (pre, k)], data['%s1/%s' % (pre, k)]
+            w = np.ascontiguousarray(v.detach().cpu().numpy().reshape(w0.shape))
+            if np.array_equal(w0.view(np.int32), w1.view(np.int32)):
+                assert np.array_equal(w.view(np.int32), w0.view(np.int32)), '%s/%s moved, the fixture did not move it' % (pre, k)
+                continue
+            want = w1.astype(np.float64) - w0
+            out['%s/%s' % (pre, k)] = float(np.linalg.norm(((w.astype(np.float64) - w0) - want).ravel()) / np.linalg.norm(want.ravel()))
+    return out
+
+
 def synthetic(seed, n, C, res, latent):
     rs = np.random.RandomState(seed)
     real = rs.rand(n, C, res, res).astype(np.float32) * 2 - 1

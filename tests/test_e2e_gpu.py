@@ -10,8 +10,8 @@ import pytest
 import torch
 
 from conftest import fixture_params, load_fixture, rel_err
-from helpers import (assert_same_contributions, build_flag_nets, build_nets, grads_by_name, load_fixture_params, reference_grads,
-                     synthetic)
+from helpers import (TRACE_MOVEMENT_TOL_GPU, assert_same_contributions, build_flag_nets, build_nets, grads_by_name, load_fixture_params,
+                     reference_grads, synthetic, trace_movement_errors)
 
 import pggan_amd as pg
 
@@ -192,6 +192,11 @@ def test_trainer_trace_golden():
         for k, v in sd.items():
             if torch.is_tensor(v):
                 assert rel_err(v.cpu(), data['%s/%s' % (pre, k)]) < 5e-3, k
+    # the bound above is the size of the whole 14-iteration movement: the step itself is held by the movement per tensor
+    moved = trace_movement_errors(data, G=G, D=D)
+    for k in sorted(moved):
+        print('movement rel-L2 %-32s %.3e' % (k, moved[k]))
+    assert len(moved) >= 20 and max(moved.values()) < TRACE_MOVEMENT_TOL_GPU, max((v, k) for k, v in moved.items())
 
 
 @pytest.mark.parametrize('res,depth,alpha,n,fmap_base,C', [(128, 5, 1.0, 2, 4096, 3), (128, 4, 0.5, 3, 4096, 3),
