@@ -41,7 +41,9 @@ extern "C" {
 
 typedef void* pg_stream_t;
 
-/* Library / device info.  Returns the ABI version (bumped on any signature change). */
+/* Library / device info.  Returns PG_ABI_VERSION, bumped on any signature change: a binding derived from this header refuses a
+ * library built from another version of it. */
+#define PG_ABI_VERSION 27
 int pg_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------

@@ -1,14 +1,21 @@
-"""ctypes binding of libpggan_hip.so (C-ABI declared in include/pggan_hip.h).
+"""ctypes binding of libpggan_hip.so, derived at import from the C headers that declare its ABI.
 
-There is deliberately NO fallback: if the shared library is missing or a symbol is absent the
-import of the product path fails loudly (``PgganLibraryError``).  Build it with
-``python __graft_entry__.py`` (or ``__graft_entry__.build()``)."""
+include/pggan_hip.h (the product boundary) and include/pggan_hip_debug.h (thread-local diagnostic exports) are the one statement
+of the ABI: the compiler holds every definition in csrc/*.hip against them, and this module parses them once into SIGNATURES /
+DEBUG_SIGNATURES (name -> argtypes), the return types, and CONSTANTS (every ``#define PG_*`` as an integer).  A new entry point is
+declared in the header, defined in csrc/ and wrapped in ops.py; nothing is restated here.
+
+There is deliberately NO fallback: a prototype or ``#define`` the parser does not fully understand, a missing shared library or an
+absent symbol fails loudly (``PgganLibraryError``).  Build the library with ``python __graft_entry__.py`` (or
+``__graft_entry__.build()``)."""
+import ast
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PGGAN_HIP_LIB') or os.path.join(_HERE, 'libpggan_hip.so')   # env override: kernel A/B experiments
-ABI_VERSION = 27
+_INCLUDE = os.path.join(os.path.dirname(_HERE), 'include')
 
 
 class PgganLibraryError(RuntimeError):
@@ -21,122 +28,87 @@ L = ctypes.c_int64
 F = ctypes.c_float
 D = ctypes.c_double
 
-# name -> argtypes (stream is always the last void*).  Mirrors include/pggan_hip.h 1:1; the thread-local diagnostic
-# exports of include/pggan_hip_debug.h are listed in DEBUG_SIGNATURES.
-SIGNATURES = {
-    'pg_abi_version': [],
-    'pg_conv2d_nhwc': [P, P, P, P, P, I, I, I, I, I, I, I, I, F, F, F, P],
-    'pg_conv2d_pool_nhwc': [P, P, P, P, P, P, P, F, F, I, I, I, I, I, I, I, I, I, F, F, F, P],
-    'pg_conv2d_pixelnorm_nhwc': [P, P, P, P, P, I, I, I, I, I, I, I, I, F, F, F, P],
-    'pg_conv2d_pnbwd_nhwc': [P, P, P, P, P, I, I, I, I, I, I, I, F, F, P],
-    'pg_conv2d_unpool_nhwc': [P, P, P, P, P, I, I, I, I, I, I, I, I, F, F, F, P],
-    'pg_signbytes_to_mask': [P, P, L, P],
-    'pg_conv2d_unpooled_nhwc': [P, P, P, F, F, P, P, I, I, I, I, I, I, F, F, P],
-    'pg_conv2d_wgrad_unpooled_nhwc': [P, P, P, F, F, P, P, I, I, I, I, I, F, P],
-    'pg_conv2d_pixelnorm_torgb_nhwc': [P, P, P, P, P, P, P, F, P, I, I, I, I, I, I, F, F, F, P],
-    'pg_conv2d_masked_fromrgb_bwd_nhwc': [P, P, P, F, P, P, F, P, P, P, P, I, I, I, I, I, I, F, P],
-    'pg_conv2d_fromrgb_nhwc': [P, P, P, F, F, P, P, P, P, P, I, I, I, I, I, I, F, F, P],
-    'pg_wino_transform_weights': [P, P, I, I, P],
-    'pg_wino_transform_weights_batched': [P, P, I, P, P, P, P, P, P],
-    'pg_conv2d_wino_nhwc': [P, P, P, P, P, P, P, F, F, I, P, P, F, I, I, I, I, I, I, F, F, F, P],
-    'pg_conv2d_wino_pixelnorm_nhwc': [P, P, P, P, P, I, I, I, I, I, I, F, F, F, P],
-    'pg_conv2d_wino_pnbwd_nhwc': [P, P, P, P, P, I, P, F, F, I, I, I, I, I, F, F, P],
-    'pg_set_workspace': [P, P, ctypes.c_size_t],
-    'pg_workspace_bytes': [I, I, I, I, I, I, P],
-    'pg_conv2d_wgrad_wino_nhwc': [P, P, P, P, I, I, I, I, I, I, F, P],
-    'pg_conv2d_wgrad_wino2_nhwc': [P, P, I, P, P, I, P, P, I, I, I, I, I, I, F, P],
-    'pg_conv2d_wgrad_nhwc': [P, P, P, P, I, I, I, I, I, I, I, I, F, P],
-    'pg_pack_dgrad_weights': [P, P, I, I, I, P],
-    'pg_pack_dgrad_weights_batched': [P, P, I, P, P, P, P, P],
-    'pg_fromrgb_fwd': [P, P, P, P, P, I, I, I, I, I, I, F, F, F, P],
-    'pg_fromrgb_bwd_data': [P, P, P, I, I, I, I, I, I, I, F, P],
-    'pg_fromrgb_wgrad': [P, P, P, P, I, I, I, I, I, I, F, P],
-    'pg_torgb_fwd': [P, P, P, P, P, I, I, I, I, I, F, F, F, P],
-    'pg_torgb_bwd_data': [P, P, P, I, I, I, I, I, I, F, P],
-    'pg_torgb_bwd_data_pnbwd': [P, P, P, P, P, I, I, I, I, I, F, F, P],
-    'pg_torgb_wgrad': [P, P, P, P, I, I, I, I, I, I, F, F, P],
-    'pg_avgpool2_fwd': [P, P, P, I, I, I, I, F, F, P],
-    'pg_avgpool2_bwd': [P, P, P, I, I, I, I, F, F, P],
-    'pg_upsample2_bwd': [P, P, I, I, I, I, P],
-    'pg_axpby_mask': [P, P, P, P, L, F, F, F, P],
-    'pg_pixelnorm_fwd': [P, P, P, L, I, F, P],
-    'pg_pixelnorm_lrelu_bwd': [P, P, P, P, L, I, F, P],
-    'pg_pixelnorm_tangent': [P, P, P, P, P, P, L, I, P],
-    'pg_pixelnorm_lrelu_bwd_inj': [P, P, P, P, P, L, I, F, P],
-    'pg_mbstd_fwd': [P, P, P, I, I, I, I, I, P],
-    'pg_mbstd_tangent': [P, P, P, P, P, I, I, I, I, I, P],
-    'pg_mbstd_bwd': [P, P, P, P, P, P, P, I, I, I, I, I, I, F, P],
-    'pg_mbstd_stats': [P, P, I, I, I, I, P],
-    'pg_mbstd_write': [P, P, P, P, I, I, I, I, I, I, P],
-    'pg_mbstd_tangent_stats': [P, P, P, P, I, I, I, I, P],
-    'pg_mbstd_tangent_write': [P, P, P, P, P, I, I, I, I, I, I, P],
-    'pg_mbstd_gsum': [P, P, P, I, I, I, I, I, P],
-    'pg_mbstd_bwd_global': [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
-    'pg_linear1_fwd': [P, P, P, P, I, I, P],
-    'pg_linear1_bwd_data': [P, P, P, P, I, I, F, P],
-    'pg_linear1_wgrad': [P, P, P, P, I, I, P],
-    'pg_gp_mix': [P, P, P, P, I, L, P],
-    'pg_row_sumsq': [P, P, I, L, P],
-    'pg_gp_seed': [P, P, P, P, I, L, F, F, F, P],
-    'pg_d_loss': [P, P, P, P, P, P, I, F, P],
-    'pg_g_loss': [P, P, P, I, P],
-    'pg_adam': [P, P, P, P, L, F, F, F, F, F, F, F, P],
-    'pg_ema_f32': [P, P, L, F, P],
-    'pg_real_prepare_u8': [P, P, L, I, I, D, D, D, D, D, P],
-    'pg_image_grid_u8': [P, P, I, I, I, I, I, F, F, P],
-    'pg_pyramid_level_u8': [P, P, L, I, I, I, F, F, P],
-    'pg_real_batch_u8': [P, L, I, I, I, P, P, I, P, D, D, D, D, D, P],
-    'pg_zero': [P, L, P],
-    'pg_uniform_f32': [P, L, ctypes.c_uint64, ctypes.c_uint64, P],
-    'pg_stft_abslog': [P, L, I, P, I, I, I, I, P],
-    'pg_stft_image': [P, L, I, P, I, I, I, I, I, P],
-    'pg_mono_f32': [P, L, I, P, L, P],
-    'pg_minmax_f32': [P, L, P, P],
-    'pg_stretch_to_u8': [P, P, L, P, F, P],
-    # Griffin-Lim on the device (csrc/griffinlim.hip)
-    'pg_gl_spectrum_f64': [P, P, I, I, I, D, D, D, I, P],
-    'pg_gl_pieces_f64': [P, L, P, P, I, I, I, I, P],
-    'pg_overlap_add_f64': [P, P, L, I, I, I, I, P],
-    'pg_wave_normalize_f32': [P, P, L, I, I, P, P],
-    # sliced Wasserstein distance (csrc/swd.hip)
-    'pg_lap_down': [P, P, L, I, P],
-    'pg_lap_up_sub': [P, P, P, L, I, P],
-    'pg_swd_gather': [P, P, P, L, I, I, L, L, P],
-    'pg_swd_channel_stats': [P, L, P, P, P],
-    'pg_swd_normalize': [P, L, P, P],
-    'pg_swd_project': [P, P, P, L, I, P],
-    'pg_swd_sort_rows': [P, P, I, L, P],
-    'pg_swd_l1': [P, P, L, P, P, P],
-    # multi-scale SSIM between image pairs (csrc/msssim.hip)
-    'pg_msssim_scale': [P, P, P, P, P, L, I, I, F, F, P],
-    'pg_msssim_finish': [P, P, P, L, I, I, P],
-    # nearest training images (csrc/nn_search.hip)
-    'pg_quantize_u8': [P, P, L, F, F, P],
-    'pg_l2dist_u8': [P, L, P, I, L, P, P],
-    'pg_topk_smallest_i64': [P, I, L, I, P, P, P],
-    # loss and per-layer weight statistics (csrc/telemetry.hip)
-    'pg_scalar_stats_push': [P, P, P, I, I, P],
-    'pg_segment_stats_plan': [P, P, I, L, P, L, P, P],
-    'pg_segment_stats_f32': [P, L, P, L, P, P],
-    'pg_segment_stats_finish': [P, L, P, I, P, P],
-    # gradient exchange (RCCL bound at run time inside the library)
-    'pg_rccl_version': [P],
-    'pg_comm_unique_id': [P],
-    'pg_comm_init_rank': [P, I, P, I],
-    'pg_comm_info': [P, P, P],
-    'pg_comm_destroy': [P],
-    'pg_allreduce_sum_f32': [P, P, L, P],
-}
+_ARGTYPES = {'pg_stream_t': P, 'int': I, 'int64_t': L, 'float': F, 'double': D, 'size_t': ctypes.c_size_t, 'uint64_t': ctypes.c_uint64}
+_RESTYPES = {'int': I, 'const char*': ctypes.c_char_p}
 
-DEBUG_SIGNATURES = {
-    'pg_debug_last_conv_kernel': [],
-    'pg_debug_last_wino_kernel': [],
-    'pg_debug_last_wino_wgrad_kernel': [],
-    'pg_debug_set_tuning': [I, I],
-    'pg_debug_set_wino': [I],
-    'pg_debug_set_wino_ksplit': [I],
-    'pg_debug_set_wino_epi': [I],
-}
+
+def _define_value(name, text):
+    """Value of ``#define name text``: integer literals, parentheses, unary minus and <<; anything else is refused."""
+    def value(node):
+        if isinstance(node, ast.Constant) and type(node.value) is int:
+            return node.value
+        if isinstance(node, ast.UnaryOp) and isinstance(node.op, ast.USub):
+            return -value(node.operand)
+        if isinstance(node, ast.BinOp) and isinstance(node.op, ast.LShift):
+            return value(node.left) << value(node.right)
+        raise PgganLibraryError('#define %s %s: not an integer expression' % (name, text))
+    try:
+        return value(ast.parse(text.strip(), mode='eval').body)
+    except SyntaxError:
+        raise PgganLibraryError('#define %s %s: not an integer expression' % (name, text))
+
+
+def _argtype(name, param):
+    if '*' in param:
+        return P
+    words = [w for w in param.split() if w != 'const']
+    ctype = ' '.join(words[:-1])                    # the last word is the parameter's name
+    if ctype not in _ARGTYPES or not re.fullmatch(r'[A-Za-z_]\w*', words[-1]):
+        raise PgganLibraryError('%s: parameter "%s" has no ctypes mapping' % (name, ' '.join(param.split())))
+    return _ARGTYPES[ctype]
+
+
+def parse_header(text):
+    """C header text -> (argtypes by name, restype by name, {PG_* define: int}) of its pg_* prototypes."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    guards = set(re.findall(r'^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]*$', text, flags=re.M))     # include guard: #ifndef X / #define X
+    constants, body, conditionals = {}, [], []
+    for line in text.split('\n'):
+        directive = re.match(r'\s*#\s*(\w+)\s*(.*?)\s*$', line)
+        foreign = next((c for c in conditionals if c), None)
+        if foreign and re.search(r'\bpg_\w+\s*\(|#\s*define\s+PG_', line):
+            raise PgganLibraryError('declaration under the preprocessor conditional "%s": %s' % (foreign, line.strip()))
+        if not directive:
+            body.append(line)
+            continue
+        word, rest = directive.groups()
+        if word in ('if', 'ifdef', 'ifndef'):
+            known = (word, rest) == ('ifdef', '__cplusplus') or word == 'ifndef' and rest in guards
+            conditionals.append(None if known else line.strip())
+        elif word == 'endif':
+            conditionals.pop()
+        elif word == 'define' and rest.startswith('PG_'):
+            name, value = re.match(r'(\w+)(.*)', rest).groups()
+            constants[name] = _define_value(name, value)
+    body = '\n'.join(body)
+    argtypes, restypes = {}, {}
+    for m in re.finditer(r'\b(pg_\w+)\s*\(', body):
+        name = m.group(1)
+        params = re.compile(r'([^()]*)\)\s*;').match(body, m.end())
+        if not params:
+            raise PgganLibraryError('%s: cannot read the parameter list' % name)
+        ret = ' '.join(body[max(body.rfind(c, 0, m.start()) for c in ';{}') + 1:m.start()].split()).replace(' *', '*')
+        if ret not in _RESTYPES:
+            raise PgganLibraryError('%s: return type "%s" has no ctypes mapping' % (name, ret))
+        params = [p.strip() for p in params.group(1).split(',')]
+        argtypes[name] = [] if params in ([''], ['void']) else [_argtype(name, p) for p in params]
+        restypes[name] = _RESTYPES[ret]
+    return argtypes, restypes, constants
+
+
+def _read_header(name):
+    try:
+        with open(os.path.join(_INCLUDE, name)) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise PgganLibraryError('cannot read the C-ABI header %s: %s' % (name, e))
+
+
+# name -> argtypes (stream is always the last void*) of the product boundary, of the diagnostic exports; name -> restype of both
+SIGNATURES, _RESTYPE_OF, CONSTANTS = _read_header('pggan_hip.h')
+DEBUG_SIGNATURES, _debug_restypes, _ = _read_header('pggan_hip_debug.h')
+_RESTYPE_OF.update(_debug_restypes)
+ABI_VERSION = CONSTANTS['PG_ABI_VERSION']          # load() holds the library's pg_abi_version() against it: a stale .so is refused
 
 _lib = None
 
@@ -160,7 +132,7 @@ def load():
         except AttributeError:
             raise PgganLibraryError('symbol %s missing from %s' % (name, LIB_PATH))
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_char_p if name in ('pg_debug_last_conv_kernel', 'pg_debug_last_wino_kernel', 'pg_debug_last_wino_wgrad_kernel') else ctypes.c_int
+        fn.restype = _RESTYPE_OF[name]
     v = lib.pg_abi_version()
     if v != ABI_VERSION:
         raise PgganLibraryError('ABI version mismatch: library %d, binding %d' % (v, ABI_VERSION))
@@ -168,8 +140,9 @@ def load():
     return lib
 
 
-_ERR = {-1: 'PG_E_ARG (bad dimension / null pointer)', -2: 'PG_E_ALIGN (channel count / alignment)',
-        -3: 'PG_E_UNSUP (unsupported configuration)', -4: 'PG_E_NOLIB (no RCCL library could be loaded)'}
+_ERR = {CONSTANTS['PG_E_ARG']: 'PG_E_ARG (bad dimension / null pointer)', CONSTANTS['PG_E_ALIGN']: 'PG_E_ALIGN (channel count / alignment)',
+        CONSTANTS['PG_E_UNSUP']: 'PG_E_UNSUP (unsupported configuration)', CONSTANTS['PG_E_NOLIB']: 'PG_E_NOLIB (no RCCL library could be loaded)'}
+_E_UNSUP, _E_RCCL_BASE = CONSTANTS['PG_E_UNSUP'], CONSTANTS['PG_E_RCCL_BASE']
 
 
 class Unsupported(RuntimeError):
@@ -178,8 +151,8 @@ class Unsupported(RuntimeError):
 
 def check(rc, name):
     if rc != 0:
-        what = _ERR.get(rc) or ('RCCL ncclResult_t %d' % (-16 - rc) if rc <= -16 else 'hipError_t %d' % rc)
-        raise (Unsupported if rc == -3 else RuntimeError)('%s failed: %s' % (name, what))
+        what = _ERR.get(rc) or ('RCCL ncclResult_t %d' % (_E_RCCL_BASE - rc) if rc <= _E_RCCL_BASE else 'hipError_t %d' % rc)
+        raise (Unsupported if rc == _E_UNSUP else RuntimeError)('%s failed: %s' % (name, what))
 
 
 CALL_HOOK = None        # measurement aid (bench.py): ``hook(fn, args, name) -> rc`` runs every C-ABI call, eager or replayed from a launch plan

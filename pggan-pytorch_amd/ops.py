@@ -12,6 +12,8 @@ import torch
 
 from . import _lib
 
+_C = _lib.CONSTANTS          # every #define PG_* that include/pggan_hip.h carries
+
 
 def _stream():
     """Raw HIP stream handle of torch's current stream.  torch.cuda.current_stream() costs ~17 us per call (device
@@ -167,7 +169,8 @@ def _is_bytes(t):
     return t is not None and t.dtype == torch.uint8
 
 
-FLAG_UPSAMPLE, FLAG_MASK_BYTES, FLAG_Y_BYTES, FLAG_SIGNS_OUT = 1, 2, 4, 8     # PG_FLAG_* of include/pggan_hip.h
+FLAG_UPSAMPLE, FLAG_MASK_BYTES = _C['PG_FLAG_UPSAMPLE'], _C['PG_FLAG_MASK_BYTES']
+FLAG_Y_BYTES, FLAG_SIGNS_OUT = _C['PG_FLAG_Y_BYTES'], _C['PG_FLAG_SIGNS_OUT']
 Unsupported = _lib.Unsupported
 
 
@@ -542,7 +545,7 @@ def pixelnorm_tangent(t, y, r, a):
 
 
 # -------------------------------------------------------------------------------------- mbstd
-MBSTD_STATS_STRIDE = 136        # PG_MBSTD_STATS_STRIDE (include/pggan_hip.h): [mu, sigma, reduction workspace]
+MBSTD_STATS_STRIDE = _C['PG_MBSTD_STATS_STRIDE']        # [mu, sigma, reduction workspace]
 
 
 def mbstd_fwd(x, groups, cp):
@@ -727,7 +730,7 @@ def real_prepare_u8(x_u8, alpha, range_in=(0, 255), range_out=(-1, 1)):
     return out
 
 
-SOUND_MODES = {'abslog': 0, 'reallog': 1}
+SOUND_MODES = {'abslog': _C['PG_SOUND_ABSLOG'], 'reallog': _C['PG_SOUND_REALLOG']}
 
 
 def spectrogram_u8(signal, n_fft, hop_length, max_out=255.0, img_mode='abslog'):
@@ -816,12 +819,12 @@ def real_batch_u8(stack_u8, idx, flip=None, depthdiff=0, alpha=1.0, range_in=(0,
 
 
 # ------------------------------------------------------------------------- sliced Wasserstein distance (csrc/swd.hip)
-SWD_DESC = 147                     # PG_SWD_DESC: 3 channels x 7 x 7
-SWD_REDUCE_BLOCKS = 1024           # PG_SWD_REDUCE_BLOCKS
-SWD_SORT_LDS_ROW = 8192            # PG_SWD_SORT_RUN: the longest row one workgroup sorts in LDS ...
-SWD_SORT_MERGE_RUN = 8192          # ... and the run length the global merge of a longer row starts from
-SWD_SORT_MERGE_TILE = 2048         # PG_SWD_SORT_MERGE_TILE: outputs per workgroup of a merge pass
-SWD_SORT_MAX_M = 1 << 22           # PG_SWD_SORT_MAX_M
+SWD_DESC = _C['PG_SWD_DESC']                                   # 3 channels x 7 x 7
+SWD_REDUCE_BLOCKS = _C['PG_SWD_REDUCE_BLOCKS']
+SWD_SORT_LDS_ROW = _C['PG_SWD_SORT_RUN']                       # the longest row one workgroup sorts in LDS ...
+SWD_SORT_MERGE_RUN = _C['PG_SWD_SORT_RUN']                     # ... and the run length the global merge of a longer row starts from
+SWD_SORT_MERGE_TILE = _C['PG_SWD_SORT_MERGE_TILE']             # outputs per workgroup of a merge pass
+SWD_SORT_MAX_M = _C['PG_SWD_SORT_MAX_M']
 
 
 def _f32_dev(t, what, ndim=None):
@@ -941,9 +944,10 @@ def swd_l1(a, b):
 
 
 # ------------------------------------------------------------------------- multi-scale SSIM between image pairs (csrc/msssim.hip)
-MSSSIM_TILE = 32                   # PG_MSSSIM_TILE: outputs (and pixels) per workgroup side
+MSSSIM_TILE = _C['PG_MSSSIM_TILE']                             # outputs (and pixels) per workgroup side
 MSSSIM_WINDOW = 11                 # taps of the Gaussian window; a scale's side is at least 16 so that the window always fits whole
-MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli & Bovik 2003; PG_MSSSIM_MAX_SCALES of them
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli & Bovik 2003
+assert len(MSSSIM_WEIGHTS) == _C['PG_MSSSIM_MAX_SCALES']
 MSSSIM_MODES = {'as_is': 0, 'range': 1, 'quantize': 2}
 
 
@@ -1040,8 +1044,8 @@ def msssim_pairs(a, b, drange=(-1, 1), quantize=True, out=None, scratch=None):
 
 
 # ------------------------------------------------------------------------- nearest training images (csrc/nn_search.hip)
-NN_MAX_QUERIES = 64                # PG_NN_MAX_QUERIES: queries of one pass over the stack; more are split into several passes
-NN_MAX_TOPK = 16                   # PG_NN_MAX_TOPK
+NN_MAX_QUERIES = _C['PG_NN_MAX_QUERIES']                       # queries of one pass over the stack; more are split into several passes
+NN_MAX_TOPK = _C['PG_NN_MAX_TOPK']
 
 
 def _u8_images(t, what):
@@ -1242,7 +1246,8 @@ def griffin_lim(images, x0, hop, rounds, mode='abslog', drange=(-1, 1), round_ho
 
 
 # ------------------------------------------------------------------------- loss and weight statistics (csrc/telemetry.hip)
-STATS_MAX_SOURCES, STATS_RECORD, STATS_MAX_LENGTH, SEG_CHUNK = 8, 8, 4096, 8192      # PG_STATS_* / PG_SEG_CHUNK of include/pggan_hip.h
+STATS_MAX_SOURCES, STATS_RECORD = _C['PG_STATS_MAX_SOURCES'], _C['PG_STATS_RECORD']
+STATS_MAX_LENGTH, SEG_CHUNK = _C['PG_STATS_MAX_LENGTH'], _C['PG_SEG_CHUNK']
 
 
 def scalar_stats_record(K, device):

@@ -73,12 +73,13 @@ class DataParallel(object):
         """RCCL communicator of the C-ABI: rank 0 draws the id, the control plane carries it, every rank joins."""
         from . import _lib
         lib = _lib.load()
-        ident = ctypes.create_string_buffer(128)
+        id_bytes = _lib.CONSTANTS['PG_COMM_ID_BYTES']
+        ident = ctypes.create_string_buffer(id_bytes)
         if self.rank == 0:
             _lib.check(lib.pg_comm_unique_id(ident), 'pg_comm_unique_id')
         box = [ident.raw if self.rank == 0 else None]
         dist.broadcast_object_list(box, src=0)
-        ident = ctypes.create_string_buffer(box[0], 128)
+        ident = ctypes.create_string_buffer(box[0], id_bytes)
         comm = ctypes.c_void_p()
         _lib.check(lib.pg_comm_init_rank(ctypes.byref(comm), self.world_size, ident, self.rank), 'pg_comm_init_rank')
         n, r = ctypes.c_int(), ctypes.c_int()
