@@ -23,7 +23,13 @@ values are comparable within a growth stage and between runs of this project.
 
 ``NearestNeighbours``: the nearest training images of generated samples by exact squared L2 distance over the 0..255 levels of the saved
 image -- the paper's answer to "is that a new image or a copy of a training image?", which neither metric above can give (a generator
-that memorises keeps a fine SWD, and MS-SSIM only sees collapse between samples).  Integer arithmetic: exact, the same from run to run."""
+that memorises keeps a fine SWD, and MS-SSIM only sees collapse between samples).  Integer arithmetic: exact, the same from run to run.
+
+``NDB``: the number of statistically different bins and the Jensen-Shannon divergence over k-means bins of the training images (Richardson &
+Weiss 2018) -- does the generator cover the modes of the training set in the data's proportions, which none of the three above says.  Integer
+k-means on the device-resident stack: exact and reproducible; UNPINNED like the SWD and MS-SSIM."""
+import math
+
 import numpy as np
 import torch
 
@@ -311,3 +317,233 @@ class NearestNeighbours(object):
             from .dataset import batch_host
             out = torch.from_numpy(batch_host(stack.numpy(), idx.numpy(), flip.numpy(), 0, 1.0, (0, 255), self.drange))
         return out.view(tuple(result['index'].shape) + tuple(stack.shape[1:]))
+
+
+# ------------------------------------------------------------------------------------------------ NDB/k and JSD (k-means bins)
+Z_THRESHOLD_05 = 1.959963984540054                 # two-sided alpha = 0.05 of the standard normal: Phi^-1(0.975)
+
+
+def _assign_host(x, c):
+    """``cluster.assign_u8`` in numpy int64: x [M,D], c [K,D] uint8 -> (label int32 [M], sqdist int64 [M]); argmin takes the first
+    (lowest k) of equal distances."""
+    x64, c64 = x.astype(np.int64), c.astype(np.int64)
+    dist = (x64 * x64).sum(axis=1)[:, None] - 2 * (x64 @ c64.T) + (c64 * c64).sum(axis=1)[None]
+    label = dist.argmin(axis=1)
+    return label.astype(np.int32), dist[np.arange(x.shape[0]), label]
+
+
+def _update_host(x, label, c):
+    """``cluster.cluster_sums_u8`` + ``centroids_u8`` in numpy int64: label -1 is no member; an empty bin keeps its centroid."""
+    K = c.shape[0]
+    member = label >= 0
+    counts = np.bincount(label[member], minlength=K).astype(np.int64)
+    sums = np.zeros(c.shape, dtype=np.int64)
+    np.add.at(sums, label[member], x[member].astype(np.int64))
+    new = c.copy()
+    filled = counts > 0
+    n = counts[filled][:, None]
+    new[filled] = ((2 * sums[filled] + n) // (2 * n)).astype(np.uint8)
+    return new
+
+
+def ndb_statistic(ref, gen, z_threshold=Z_THRESHOLD_05):
+    """The two-sample test per bin and the JS divergence of the two histograms, in fp64 on the host: ``ref``,
+    ``gen`` integer counts [K] -> {'ndb', 'ndb_over_k', 'jsd', 'z'}.  A bin whose standard error is 0 has z = 0."""
+    ref, gen = np.asarray(ref, dtype=np.float64), np.asarray(gen, dtype=np.float64)
+    P, Q = ref.sum(), gen.sum()
+    if not (P > 0 and Q > 0):
+        raise ValueError('both histograms need at least one sample')
+    p, q, pool = ref / P, gen / Q, (ref + gen) / (P + Q)
+    se = np.sqrt(pool * (1.0 - pool) * (1.0 / P + 1.0 / Q))
+    z = np.zeros_like(p)
+    np.divide(p - q, se, out=z, where=se > 0)
+    ndb = int((np.abs(z) > z_threshold).sum())
+    m = 0.5 * (p + q)
+    # K <= 64 terms, added in ascending k on Python floats: the order is part of the definition's bits (0 log 0 = 0)
+    kl_p = sum(float(a) * math.log2(float(a) / float(b)) for a, b in zip(p, m) if a > 0)
+    kl_q = sum(float(a) * math.log2(float(a) / float(b)) for a, b in zip(q, m) if a > 0)
+    return {'ndb': ndb, 'ndb_over_k': ndb / float(len(ref)), 'jsd': 0.5 * kl_p + 0.5 * kl_q, 'z': z}
+
+
+class NDB(object):
+    """Number of statistically different bins (NDB/k) and the Jensen-Shannon divergence of the bin histograms (Richardson & Weiss 2018,
+    "On GANs and GMMs"): does the generator cover the modes of the training set in the data's proportions?  ``fit()`` clusters the
+    training images into ``k`` Voronoi cells by k-means in pixel space; ``feed`` counts generated images per cell; ``result()`` counts the
+    cells whose share of generated images differs from their share of training images by a two-sample test, and the JSD of the two
+    histograms.  Defined per image vector: one-channel networks are measured like RGB ones.
+
+    ``source``: a ``DeviceImageDataset`` (``fit()`` takes ``level_stack()`` of its current ``model_depth``; ``range_in`` must be
+    (0, 255)) or a uint8 tensor [M,C,r,r]; D = C r^2 a multiple of 16, M <= ``cluster.MAX_IMAGES``, 2 <= k <= ``ops.NN_MAX_QUERIES``.
+    ``holdout`` = h, 0 <= h < M - k + 1: the first h entries of ``torch.randperm(M)`` from a CPU generator seeded ``seed`` are held out
+    of the fit and the reference proportions are counted on THEM; h = 0 is the paper's form (reference proportions on the fitted images
+    themselves), under which a fresh sample of the SAME distribution already differs in many bins -- a centroid is nearer to its own
+    members than to new points -- so a hold-out is the form to use.  The initial centroids are copies of the first k images of a
+    second permutation, of the fit set, seeded ``seed + 1``.  An iteration assigns ALL images (``label = argmin_k`` of the exact
+    squared distance, the lower k of equal ones) and moves every centroid to the mean of its fit-set members rounded half up to
+    uint8 -- this project's choice: the next assignment stays on the exact int8-MFMA path and the whole fit is reproducible -- an
+    empty bin keeping its centroid.  The fit stops when an iteration's fit-set labels equal the previous one's (``converged``) or after
+    ``max_iter`` iterations (rounded centroids do not guarantee a monotone objective); ``iterations`` counts the assignments, and
+    after an unconverged fit the images are assigned once more, to the final centroids.  Three 1-element host reads per iteration (the
+    comparison of the labels, the label check and the bincount of ``cluster.cluster_sums_u8``); a fit happens once per growth stage.
+    UNPINNED, like the SWD and MS-SSIM: comparable between runs of this project, not with published tables.
+
+    ``feed(samples_fp32)`` rounds to the 0..255 levels of the saved image (``ops.quantize_u8`` with ``drange``); ``feed_u8`` takes
+    levels.  Batches of any size >= 1.  ``device``: None = where the source is; 'cpu' = the numpy twin in int64, equal bit for bit."""
+
+    def __init__(self, source, k=50, holdout=0, seed=0, max_iter=30, z_threshold=Z_THRESHOLD_05, drange=(-1, 1), device=None):
+        if torch.is_tensor(source):
+            if source.dtype != torch.uint8 or source.dim() != 4 or source.shape[0] < 1:
+                raise ValueError('source: expected a DeviceImageDataset or a uint8 tensor [M,C,r,r]')
+            M, src_device = source.shape[0], source.device
+        elif hasattr(source, 'level_stack'):
+            if tuple(source.range_in) != (0, 255):
+                raise ValueError('source: the data set holds range_in = %r; the bins are fitted on 0..255 levels' % (tuple(source.range_in),))
+            M, src_device = len(source), source.device
+        else:
+            raise ValueError('source: expected a DeviceImageDataset or a uint8 tensor [M,C,r,r], got %s' % type(source))
+        from . import cluster
+        if not 1 <= M <= cluster.MAX_IMAGES:
+            raise ValueError('%d images (1 <= M <= %d: the per-bin sums are int32)' % (M, cluster.MAX_IMAGES))
+        if isinstance(k, bool) or int(k) != k or not 2 <= k <= ops.NN_MAX_QUERIES:
+            raise ValueError('k = %r (2 <= k <= %d)' % (k, ops.NN_MAX_QUERIES))
+        if isinstance(holdout, bool) or int(holdout) != holdout or not 0 <= holdout < M - int(k) + 1:
+            raise ValueError('holdout = %r for %d images and k = %d (0 <= holdout < M - k + 1)' % (holdout, M, k))
+        if isinstance(max_iter, bool) or int(max_iter) != max_iter or max_iter < 1:
+            raise ValueError('max_iter must be a positive integer, got %r' % (max_iter,))
+        if not float(z_threshold) > 0:
+            raise ValueError('z_threshold must be positive, got %r' % (z_threshold,))
+        if not float(drange[1]) > float(drange[0]):
+            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
+        self.source, self.k, self.holdout, self.seed, self.max_iter = source, int(k), int(holdout), int(seed), int(max_iter)
+        self.z_threshold, self.drange = float(z_threshold), (float(drange[0]), float(drange[1]))
+        self.device = torch.device(src_device if device is None else device)
+        self.num_images = M
+        self.centroids = self.labels = self.ref = self.iterations = self.converged = self.resolution = self.shape = None
+        self.reset()
+
+    def split(self):
+        """(held-out indices [h], fit-set indices [M - h]) as int64 CPU tensors: disjoint, together 0 .. M-1."""
+        perm = torch.randperm(self.num_images, generator=torch.Generator().manual_seed(self.seed))
+        return perm[:self.holdout], perm[self.holdout:]
+
+    def stack(self):
+        """The uint8 stack [M,C,r,r] a fit made now would cluster, on ``device``."""
+        s = self.source if torch.is_tensor(self.source) else self.source.level_stack()
+        return s if s.device == self.device else s.to(self.device)
+
+    def fit(self):
+        """Cluster the stack of the current stage; stores ``centroids`` uint8 [k,C,r,r] and ``labels`` int32 [M] (on ``device``), ``ref``
+        (int64 [k], host), ``iterations``, ``converged``, ``resolution``; forgets what was fed.  Returns self."""
+        stack = self.stack().contiguous()
+        M, K = stack.shape[0], self.k
+        if M != self.num_images:
+            raise ValueError('the source holds %d images now, %d at construction' % (M, self.num_images))
+        D = stack.numel() // M
+        if D % 16:
+            raise ValueError('an image of %d bytes (a multiple of 16 is required)' % D)
+        held, fit = self.split()
+        init = fit[torch.randperm(fit.numel(), generator=torch.Generator().manual_seed(self.seed + 1))[:K]]
+        if self.device.type == 'cuda':
+            from . import cluster
+            is_fit = torch.zeros(M, dtype=torch.bool)
+            is_fit[fit] = True
+            is_fit = is_fit.to(self.device)
+            outside = torch.full((M,), -1, dtype=torch.int32, device=self.device)
+            c = stack.index_select(0, init.to(self.device)).contiguous()
+            prev, iterations, converged = None, 0, False
+            while iterations < self.max_iter:
+                label, _ = cluster.assign_u8(stack, c)
+                iterations += 1
+                members = torch.where(is_fit, label, outside)
+                if prev is not None and bool(torch.equal(members, prev)):
+                    converged = True
+                    break
+                sums, counts = cluster.cluster_sums_u8(stack, members, K)
+                c = cluster.centroids_u8(sums, counts, c)
+                prev = members
+            if not converged:
+                label, _ = cluster.assign_u8(stack, c)
+            counted = label.index_select(0, (held if self.holdout else fit).to(self.device)).to(torch.int64)
+            ref = torch.bincount(counted, minlength=K).cpu().numpy().astype(np.int64)
+            self.centroids, self.labels = c, label
+        else:
+            x = stack.numpy().reshape(M, D)
+            is_fit = np.zeros(M, dtype=bool)
+            is_fit[fit.numpy()] = True
+            c = x[init.numpy()].copy()
+            prev, iterations, converged = None, 0, False
+            while iterations < self.max_iter:
+                label, _ = _assign_host(x, c)
+                iterations += 1
+                members = np.where(is_fit, label, np.int32(-1)).astype(np.int32)
+                if prev is not None and np.array_equal(members, prev):
+                    converged = True
+                    break
+                c = _update_host(x, members, c)
+                prev = members
+            if not converged:
+                label, _ = _assign_host(x, c)
+            ref = np.bincount(label[(held if self.holdout else fit).numpy()], minlength=K).astype(np.int64)
+            self.centroids, self.labels = torch.from_numpy(c.reshape((K,) + tuple(stack.shape[1:]))), torch.from_numpy(label)
+        self.ref, self.iterations, self.converged = ref, iterations, converged
+        self.shape, self.resolution = tuple(stack.shape[1:]), int(stack.shape[-1])
+        self.reset()
+        return self
+
+    def reset(self):
+        """Forget what was fed; the fit is kept."""
+        self.gen = np.zeros(self.k, dtype=np.int64)
+        self._counts = None                                             # device: the running histogram, read once in result()
+        self._fed = 0
+        self._result = None
+
+    def _fitted(self, images, dtype, what):
+        if self.centroids is None:
+            raise RuntimeError('fit() first')
+        if not torch.is_tensor(images) or images.dtype != dtype or images.dim() != 4 or images.shape[0] < 1 \
+                or tuple(images.shape[1:]) != self.shape:
+            raise ValueError('%s: expected %s images [n,%d,%d,%d] (the fitted resolution), got %s'
+                             % ((what, str(dtype).replace('torch.', '')) + self.shape
+                                + (tuple(images.shape) if torch.is_tensor(images) else type(images),)))
+        if self._result is not None:
+            raise RuntimeError('result() was taken: reset() before feeding again')
+
+    def feed(self, samples):
+        """Generated fp32 images [n,C,r,r] in ``drange``, n >= 1."""
+        self._fitted(samples, torch.float32, 'feed')
+        if self.device.type == 'cuda':
+            self.feed_u8(ops.quantize_u8(samples.to(self.device).contiguous(), self.drange))
+        else:
+            self.feed_u8(torch.from_numpy(_quantise_host(samples.cpu().numpy(), self.drange)))
+
+    def feed_u8(self, images):
+        """Generated images as 0..255 levels, uint8 [n,C,r,r], n >= 1."""
+        self._fitted(images, torch.uint8, 'feed_u8')
+        n = images.shape[0]
+        if self.device.type == 'cuda':
+            from . import cluster
+            images = images.to(self.device).contiguous()
+            for a in range(0, n, ops.NN_MAX_QUERIES * 64):              # (any size: the distances of a chunk are [k, chunk] int64)
+                label, _ = cluster.assign_u8(images[a:a + ops.NN_MAX_QUERIES * 64], self.centroids)
+                counts = torch.bincount(label.to(torch.int64), minlength=self.k)
+                self._counts = counts if self._counts is None else self._counts + counts
+        else:
+            label, _ = _assign_host(images.cpu().numpy().reshape(n, -1), self.centroids.numpy().reshape(self.k, -1))
+            self.gen = self.gen + np.bincount(label, minlength=self.k).astype(np.int64)
+        self._fed += n
+
+    def result(self):
+        """{'ndb', 'ndb_over_k', 'jsd', 'z' (float64 [k]), 'ref', 'gen' (int64 [k]), 'k', 'num_samples', 'iterations', 'converged'}
+        in fp64 on the host (``ndb_statistic``).  One device synchronisation."""
+        if self._result is None:
+            if self.centroids is None:
+                raise RuntimeError('fit() first')
+            if self._fed < 1:
+                raise RuntimeError('nothing was fed')
+            if self._counts is not None:
+                self.gen = self._counts.cpu().numpy().astype(np.int64)
+            res = ndb_statistic(self.ref, self.gen, self.z_threshold)
+            res.update(ref=self.ref.copy(), gen=self.gen.copy(), k=self.k, num_samples=self._fed, iterations=self.iterations,
+                       converged=self.converged)
+            self._result = res
+        return self._result

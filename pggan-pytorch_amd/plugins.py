@@ -518,6 +518,77 @@ class NNMonitor(Plugin):
         self.epoch(*args)
 
 
+class NDBMonitor(Plugin):
+    """Mode-coverage metric per tick (``metrics.NDB``: NDB/k and the JS divergence over k-means bins of the training images; the
+    reference reports none): every ``ndb_ticks`` ticks and at the end, ``num_samples`` images of ``G.forward(sample_fn(n).cuda())``,
+    ``minibatch`` at a time -- of the smoothed generator when the trainer keeps one (``smoothed`` as in ``OutputGenerator``) -- are counted
+    per bin and compared with the proportions of held-out training images.  ``dataset``: a ``DeviceImageDataset``; the bins are
+    fitted on ``level_stack()`` of the current growth stage and REFITTED when the stage's resolution differs from the fitted one (a
+    fit happens once per stage, not per evaluation).  ``holdout=None`` holds out ``min(M // 5, num_samples)`` training images for the
+    reference proportions (``metrics.NDB`` says why a hold-out is the form to use); ``k`` bins, at most ``ops.NN_MAX_QUERIES``.
+    Writes ``stats['ndb']`` (the number of bins whose two proportions differ at the 5 % level), ``stats['ndb_over_k']`` and
+    ``stats['jsd']`` under the stat-dict convention of the other monitors.  Defined per image vector: one-channel networks are measured
+    like RGB ones.  Rank 0 evaluates (replicas are identical; the bins are rank 0's shard).  Opt-in: a run that does not register it
+    pays nothing.  ``metric_kwargs`` go to ``NDB`` (seed, max_iter, z_threshold, drange).
+
+    The default period follows docs/experiments_ndb.md: the metric's own part of an evaluation of 8192 samples measured 0.07 s at 3x1024^2
+    (512 batches of 16 against 50 centroids), the fit 0.70 ms per GB of stack and iteration, i.e. at most 30 x 66 ms = 2.0 s for 30 000
+    images of 3x1024^2 by proportion (that size itself was not run), once per stage; the 8192 generator passes are bounded by 8192 images
+    at the 296 img/s of a whole measured train step, 27.7 s.  An evaluation is under 27.8 s, and under 1 % of a 3.3 s tick of 1 kimg (the
+    rule of docs/experiments_swd.md) needs ticks >= 100 x 27.8 / 3.3 = 842: 850.  ``num_samples=2048, ndb_ticks=200`` costs the same
+    share with a noisier histogram."""
+
+    def __init__(self, dataset, sample_fn, num_samples=8192, minibatch=16, k=50, holdout=None, ndb_ticks=850, smoothed=None,
+                 **metric_kwargs):
+        super(NDBMonitor, self).__init__([(ndb_ticks, 'epoch'), (1, 'end')])
+        if int(num_samples) < 1 or int(minibatch) < 1:
+            raise ValueError('num_samples and minibatch must be positive')
+        self.dataset, self.sample_fn = dataset, sample_fn
+        self.num_samples, self.minibatch, self.k = int(num_samples), int(minibatch), k
+        self.holdout = min(len(dataset) // 5, self.num_samples) if holdout is None else holdout
+        self.smoothed = smoothed
+        self.metric_kwargs = metric_kwargs
+        self._metric_obj = None
+
+    def register(self, trainer):
+        _check_smoothed(trainer, self.smoothed, 'NDBMonitor')
+        self.trainer = trainer
+
+    def _stage_resolution(self):
+        stage = getattr(self.dataset, '_stage', None)
+        if stage is None:
+            return int(self.dataset.level_stack().shape[-1])
+        stack, depthdiff = stage()                                           # (no level is made for the answer)
+        return int(stack.shape[-1]) >> depthdiff
+
+    def _metric(self):
+        """The metric, fitted on the data set's current stage."""
+        if self._metric_obj is None:
+            from .metrics import NDB
+            self._metric_obj = NDB(self.dataset, k=self.k, holdout=self.holdout, **self.metric_kwargs)
+        m = self._metric_obj
+        if m.resolution != self._stage_resolution():
+            m.fit()
+        return m
+
+    def epoch(self, epoch_index):
+        tr = self.trainer
+        if tr.parallel is not None and tr.parallel.rank != 0:
+            return
+        metric = self._metric()
+        metric.reset()
+        gen = _output_generator(tr, self.smoothed)
+        for start in range(0, self.num_samples, self.minibatch):
+            metric.feed(gen.forward(self.sample_fn(min(self.minibatch, self.num_samples - start)).cuda()))
+        res = metric.result()
+        tr.stats['ndb'] = dict(log_name='ndb', log_epoch_fields=['{val:d}'], val=res['ndb'])
+        tr.stats['ndb_over_k'] = dict(log_name='ndb_over_k', log_epoch_fields=['{val:.3f}'], val=res['ndb_over_k'])
+        tr.stats['jsd'] = dict(log_name='jsd', log_epoch_fields=['{val:.4f}'], val=res['jsd'])
+
+    def end(self, *args):
+        self.epoch(*args)
+
+
 class LossMonitor(Plugin):
     """The losses of a run per tick (replaces the reference's four ``EfficientLossMonitor``s, train.py:170-171 / plugins.py:102-111, which
     read every loss on the host every iteration).  ``iteration(i, *losses)`` makes ONE ``telemetry.ScalarStats.push`` of the tensors the
