@@ -4,7 +4,9 @@ Every pass below is a hand-ordered sequence of the C-ABI kernels (``ops``):
 
   generator_forward / generator_backward            reference network.py:118-139 + its autograd
   discriminator forward (batched [real|fake|mixed])  reference network.py:225-240
-  d_backward            first-order adjoint sweep (data-only or data+weights)
+  d_backward            first-order adjoint sweep (data-only or data+weights): the driver of
+                        _consume | _pn_adjoints (seed: _pn_head_seed) -> _hand_over (+ _fade_in) ... -> _entry, which pass saved.PoolAdjoint between blocks
+  _bytes_first          the one rule for LeakyReLU' masks kept as sign bytes (saved.Sign): bytes first, fp32 when a launch refuses
   d_tangent_wgrad       forward-mode (tangent) sweep of the gradient-penalty second-order term
 
 The WGAN-GP double backward (wgan_gp_loss.py:25-31 + trainer.py:98) is NOT done with a generic
@@ -250,80 +252,84 @@ def _wino(layer, N, H, cout, transposed=False):
     return layer._wtu if transposed else layer._wu
 
 
+def _f32(sign):
+    """fp32 view of a LeakyReLU' mask that may be stored as sign bytes only (paths without a byte-aware kernel)."""
+    return sign.f32 if sign.f32 is not None or sign.bytes is None else ops.signbytes_to_mask(sign.bytes)
+
+
+def _bytes_first(run, sign, tag, bytes_out=False, count=True, redo=None):
+    """THE rule for a launch that may be handed sign bytes.
+
+    First attempt: ``run(mask, bytes_out)`` with the bytes of ``sign`` (a saved.Sign or None) as the mask.  ``bytes_out`` asks for a
+    byte OUTPUT (signs_out / y_bytes) as well.
+    If that answers ``ops.Unsupported``, the launch is counted under ``FALLBACKS[tag]`` and redone as ``run(fp32 mask, False)``.
+    The fp32 copy is used as given; the bytes are expanded only when there is none.
+    With no byte in play there is nothing to redo: ``Unsupported`` is the caller's.
+
+    tag   : the key, or a callable that formats it (only a counted fallback pays for the string).
+    count : False redoes silently.
+    redo  : called in place of the second ``run``, by a launch that has to expand the bytes itself, behind what its other arguments
+            issue."""
+    mb = sign.bytes if sign is not None else None
+    if mb is None and not bytes_out:
+        return run(sign.f32 if sign is not None else None, False)
+    try:
+        return run(mb if mb is not None else sign.f32 if sign is not None else None, bytes_out)
+    except ops.Unsupported:
+        if count:
+            FALLBACKS[tag() if callable(tag) else tag] += 1
+    return redo() if redo is not None else run(None if sign is None else _f32(sign), False)
+
+
 def _conv(x, layer, N, H, act=True, mask=None, bias=True, ups=False, out=None, signs_out=False):
-    """Forward conv (+bias+act) or, with ``mask``, the masked linear map of the tangent pass.  ``signs_out``: returns
-    (y, sign bytes of y) -- (y, None) when the launch cannot produce them."""
-    def run(mask, signs_out):
+    """Forward conv (+bias+act) or, with ``mask`` (the saved.Sign of the layer's own output), the masked linear map of the tangent
+    pass.  ``signs_out``: returns (y, sign bytes of y) -- (y, None) when the launch cannot produce them."""
+    def run(m, so):
         u = _wino(layer, N, H, layer.conv.weight.shape[2])
         if u is not None:
-            return ops.conv2d_wino(x, u, layer.conv.bias.data if bias else None, N, H, H, layer.c,
-                                   layer.slope if act else 1.0, mask=mask, mask_slope=layer.slope, ups=ups, out=out,
-                                   signs_out=signs_out)
-        return ops.conv2d(x, layer.conv.weight.data, layer.conv.bias.data if bias else None, N, H, H,
-                          layer.ksize, layer.pad, layer.c, layer.slope if act else 1.0,
-                          mask=mask, mask_slope=layer.slope, ups=ups, out=out, signs_out=signs_out)
-    if signs_out:
-        try:
-            return run(mask, True)
-        except ops.Unsupported:
-            FALLBACKS['conv signs_out %dx%d %s' % (H, H, tuple(layer.conv.weight.shape))] += 1
-            return run(mask, False), None
-    if isinstance(mask, tuple):                    # (fp32 activation, its sign bytes or None): bytes first, fp32 as the fallback
-        m32, mb = mask
-        if mb is not None:
-            try:
-                return run(mb, False)
-            except ops.Unsupported:
-                FALLBACKS['conv masked %dx%d %s' % (H, H, tuple(layer.conv.weight.shape))] += 1
-        return run(m32, False)
-    return run(mask, False)
-
-
-def _mask32(m):
-    """fp32 view of a LeakyReLU' mask that may be stored as sign bytes (paths without a byte-aware kernel)."""
-    return ops.signbytes_to_mask(m) if m is not None and m.dtype == torch.uint8 else m
+            y = ops.conv2d_wino(x, u, layer.conv.bias.data if bias else None, N, H, H, layer.c,
+                                layer.slope if act else 1.0, mask=m, mask_slope=layer.slope, ups=ups, out=out, signs_out=so)
+        else:
+            y = ops.conv2d(x, layer.conv.weight.data, layer.conv.bias.data if bias else None, N, H, H,
+                           layer.ksize, layer.pad, layer.c, layer.slope if act else 1.0,
+                           mask=m, mask_slope=layer.slope, ups=ups, out=out, signs_out=so)
+        return (y, None) if signs_out and not so else y
+    if not signs_out and (mask is None or mask.bytes is None):         # (no byte in play: nothing for the rule, one call less on the host)
+        return run(mask and mask.f32, False)
+    return _bytes_first(run, mask, lambda: 'conv %s %dx%d %s' % ('signs_out' if signs_out else 'masked', H, H, tuple(layer.conv.weight.shape)),
+                        bytes_out=signs_out)
 
 
 def _conv_pool(x, layer, N, H, bias=True, mask=None, other=None, a=1.0, b=0.0, pool_only=False, y_bytes=False):
-    """conv (+bias+act | mask) followed by the 2x2 average pool / fade-in blend, one launch.  ``y_bytes``: the
+    """conv (+bias+act | mask: as in ``_conv``) followed by the 2x2 average pool / fade-in blend, one launch.  ``y_bytes``: the
     full-resolution output is returned as sign bytes (falls back to fp32 when the launch cannot fuse)."""
-    def run(mask, y_bytes):
+    def run(m, yb):
         u = _wino(layer, N, H, layer.conv.weight.shape[2])
         if u is not None:
             return ops.conv2d_wino(x, u, layer.conv.bias.data if bias else None, N, H, H, layer.c,
-                                   layer.slope if mask is None else 1.0, mask=mask, mask_slope=layer.slope,
-                                   pool=True, other=other, a=a, b=b, pool_only=pool_only, y_bytes=y_bytes)
+                                   layer.slope if m is None else 1.0, mask=m, mask_slope=layer.slope,
+                                   pool=True, other=other, a=a, b=b, pool_only=pool_only, y_bytes=yb)
         return ops.conv2d_pool(x, layer.conv.weight.data, layer.conv.bias.data if bias else None, N, H, H, layer.ksize, layer.pad,
-                               layer.c, layer.slope if mask is None else 1.0, mask=mask, mask_slope=layer.slope,
-                               other=other, a=a, b=b, pool_only=pool_only, y_bytes=y_bytes)
-    if y_bytes or (mask is not None and mask.dtype == torch.uint8):
-        try:
-            return run(mask, y_bytes)
-        except ops.Unsupported:
-            FALLBACKS['conv_pool %dx%d %s' % (H, H, tuple(layer.conv.weight.shape))] += 1
-            return run(_mask32(mask), False)
-    return run(mask, False)
+                               layer.c, layer.slope if m is None else 1.0, mask=m, mask_slope=layer.slope,
+                               other=other, a=a, b=b, pool_only=pool_only, y_bytes=yb)
+    if not y_bytes and (mask is None or mask.bytes is None):
+        return run(mask and mask.f32, False)
+    return _bytes_first(run, mask, lambda: 'conv_pool %dx%d %s' % (H, H, tuple(layer.conv.weight.shape)), bytes_out=y_bytes)
 
 
-def _dgrad(net, gz, layer, N, Hout, mask=None, mask_slope=0.2):
-    """Adjoint of the conv wrt its input: gz [N,Hout,Hout,Cout] -> [N,Hin,Hin,Cin_store] (* mask)."""
-    def run(mask):
+def _dgrad(net, gz, layer, N, Hout, mask=None):
+    """Adjoint of the conv wrt its input: gz [N,Hout,Hout,Cout] -> [N,Hin,Hin,Cin_store] (* LeakyReLU' of ``mask``, a saved.Sign)."""
+    slope = mask.slope if mask is not None else 0.2
+
+    def run(m, _):
         u = _wino(layer, N, Hout, layer.conv.weight.shape[3], transposed=True) if layer.ksize == 3 and layer.pad == 1 else None
         if u is not None:
-            return ops.conv2d_wino(gz, u, None, N, Hout, Hout, layer.c, 1.0, mask=mask, mask_slope=mask_slope)
+            return ops.conv2d_wino(gz, u, None, N, Hout, Hout, layer.c, 1.0, mask=m, mask_slope=slope)
         return ops.conv2d(gz, _wt(net, layer), None, N, Hout, Hout, layer.ksize, layer.ksize - 1 - layer.pad,
-                          layer.c, 1.0, mask=mask, mask_slope=mask_slope)
-    if isinstance(mask, tuple):                    # (fp32 activation, its sign bytes or None)
-        m32, mb = mask
-        if mb is not None:
-            try:
-                return run(mb)
-            except ops.Unsupported:
-                FALLBACKS['dgrad masked %dx%d %s' % (Hout, Hout, tuple(layer.conv.weight.shape))] += 1
-                if m32 is None:                    # (d_forward(keep_input=False) kept the sign bytes only: expand them)
-                    m32 = _mask32(mb)
-        return run(m32)
-    return run(mask)
+                          layer.c, 1.0, mask=m, mask_slope=slope)
+    if mask is None or mask.bytes is None:
+        return run(mask and mask.f32, False)
+    return _bytes_first(run, mask, lambda: 'dgrad masked %dx%d %s' % (Hout, Hout, tuple(layer.conv.weight.shape)))
 
 
 def _dgrad_pool(net, gz, layer, N, H, other=None, a=1.0, b=0.0, pnb=None):
@@ -341,20 +347,18 @@ def _dgrad_pool(net, gz, layer, N, H, other=None, a=1.0, b=0.0, pnb=None):
                            other=other, a=a, b=b, pool_only=True)[1]
 
 
-def _dgrad_unpool(net, gz, layer, N, H, upmask, mul, mask_slope):
-    """Backward-data conv + pool adjoint + LeakyReLU' mask of the finer activation, one launch."""
+def _dgrad_unpool(net, gz, layer, N, H, up, mul):
+    """Backward-data conv + pool adjoint + LeakyReLU' of the finer activation (``up``, a saved.Sign), one launch."""
     u = _wino(layer, N, H, layer.conv.weight.shape[3], transposed=True)
-    if u is not None:
-        return ops.conv2d_wino(gz, u, None, N, H, H, layer.c, 1.0, mask_slope=mask_slope, unpool=True, upmask=upmask, up_mul=mul)
-    try:
+    if u is not None:                              # (outside the rule: this launch takes either form, a refusal is the caller's)
+        return ops.conv2d_wino(gz, u, None, N, H, H, layer.c, 1.0, mask_slope=up.slope, unpool=True,
+                               upmask=up.bytes if up.bytes is not None else up.f32, up_mul=mul)
+
+    def launch(mask):                              # mask(): read behind the wait for the weights, where the redo expands the bytes
         return ops.conv2d_unpool(gz, _wt(net, layer), N, H, H, layer.ksize, layer.ksize - 1 - layer.pad, layer.c,
-                                 upmask=upmask, mul=mul, mask_slope=mask_slope)
-    except ops.Unsupported:
-        if upmask is None or upmask.dtype != torch.uint8:
-            raise
-        FALLBACKS['dgrad unpool %dx%d %s' % (H, H, tuple(layer.conv.weight.shape))] += 1
-        return ops.conv2d_unpool(gz, _wt(net, layer), N, H, H, layer.ksize, layer.ksize - 1 - layer.pad, layer.c,
-                                 upmask=_mask32(upmask), mul=mul, mask_slope=mask_slope)
+                                 upmask=mask(), mul=mul, mask_slope=up.slope)
+    return _bytes_first(lambda m, _: launch(lambda: m), up, lambda: 'dgrad unpool %dx%d %s' % (H, H, tuple(layer.conv.weight.shape)),
+                        redo=lambda: launch(lambda: _f32(up)))
 
 
 def _dgrad_pnbwd(net, gz, layer, N, H, ysaved, r, slope):
@@ -802,12 +806,10 @@ def d_forward(D, x, groups=1, keep_input=True):
                 fused, cur = (a1, a1b), None
             except ops.Unsupported:
                 FALLBACKS['fromRGB in the gather %dx%d' % (r, r)] += 1
-    if fused is not None:
-        pass
-    elif sb and r >= SIGN_BYTES_MIN_H:
-        cur, curb = ops.fromrgb_fwd(x, fr.conv.weight.data, fr.conv.bias.data, NB, C, r, r, fr.c, fr.slope, signs_out=True)
-    else:
-        cur = ops.fromrgb_fwd(x, fr.conv.weight.data, fr.conv.bias.data, NB, C, r, r, fr.c, fr.slope)
+    if fused is None:
+        cur = ops.fromrgb_fwd(x, fr.conv.weight.data, fr.conv.bias.data, NB, C, r, r, fr.c, fr.slope, signs_out=sb and r >= SIGN_BYTES_MIN_H)
+        if sb and r >= SIGN_BYTES_MIN_H:
+            cur, curb = cur
     H = r
     a2 = None
     for k, j in enumerate(range(e, nb)):
@@ -882,176 +884,40 @@ def _arena_free(st):
 def _lazy_unpool_ok(rec, save_adjoints):
     """May the pool adjoint behind block ``rec`` stay un-evaluated, for the consumers of the block's c2 gradient to apply in their gathers
     (ops.conv2d_unpooled / conv2d_wgrad_unpooled)?  Needs c2's output as sign bytes and the 8-channel 3x3 layers those kernels are built for."""
+    if not (USE_LAZY_UNPOOL and not save_adjoints and rec.H % 32 == 0 and rec.a2.dtype == torch.uint8):     # (the cheap tests first)
+        return False
     c2 = rec.blk.c2
     w = c2.conv.weight.shape
-    return (USE_LAZY_UNPOOL and not save_adjoints and rec.a2.dtype == torch.uint8 and w[3] == 8 and w[2] in (8, 16)
-            and c2.ksize == 3 and rec.H % 32 == 0)
+    return w[3] == 8 and w[2] in (8, 16) and c2.ksize == 3
 
 
-def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
-    """First-order adjoint sweep through D for the batch in ``ctx``.
+# ---- the adjoint sweep: d_backward drives it; one step per thing that happens to a block ---------------------------------------------
+#   _consume | _pn_adjoints   hand-over of the coarser block (saved.PoolAdjoint) -> gz2, gz1 (+ c2's weight gradient)
+#   _hand_over                c1's backward-data conv + the pool adjoint -> the hand-over to the finer block (+ _fade_in at the boundary)
+#   _entry                    c1's backward-data conv of the entry block, fromRGB's gradients, the image gradient
+def _consume(D, hand, rec, n, full):
+    """c2 of block ``rec`` over ``n`` images: (gz2, gz1) and c2's weight gradient from what the coarser block handed over.  A lazy
+    hand-over is unpooled in the gathers of its two consumers (gz2 is never written: None); when they answer ``ops.Unsupported`` it is
+    evaluated after all."""
+    c2, H = rec.blk.c2, rec.H
+    a1 = saved.Sign.a1(rec, n if rec.last else None)
 
-    gscore [NB] : d loss / d score.   full: also accumulate weight/bias gradients.
-    want_gimg   : return d loss / d input image (NCHW).
-    hvp         : saved.Hvp — the last ``NB-n_head`` images form one extra group
-                  whose score gradient is zero and which only receives the minibatch-stddev
-                  Hessian-vector injection; ``gscore`` then has n_head entries."""
-    wait_pending(D)
-    if getattr(D, 'pixelnorm', False):
-        return _d_backward_pn(D, ctx, gscore, full, want_gimg, save_adjoints, hvp)
-    D._ensure_buffers()
-    NB, alpha = ctx.NB, ctx.alpha
-    x = ctx.x
-    C = D.num_channels
-    recs = ctx.recs
-    adj = [saved.DAdjoint() for _ in recs] if save_adjoints else None
-    lastrec = recs[-1]
-    nh = NB if hvp is None else hvp.n_head
-    a2 = lastrec.a2
-    lc2 = lastrec.blk.c2
-    tail = _tail_wgrad_on_main(recs[0].H) if (full and ASYNC_WGRAD and D._rt.grad_hook is None and len(recs) > 1) else 0
-    if full:
-        ops.linear1_wgrad(gscore, a2[:nh], D._lin_gw, D._lin_gb)
-    g = ops.linear1_bwd_data(gscore, D.linear.weight.data, a2[:nh], (nh,) + tuple(a2.shape[1:]), lc2.slope)
-    gimg = None
-    gimg_fused = fw_fused = False                # the entry block's backward-data conv wrote the image gradient / accumulated fromRGB's weight gradient itself
-    pending_prev = None
-    carry = None
-    for idx in range(len(recs) - 1, -1, -1):
-        rec = recs[idx]
-        blk, H = rec.blk, rec.H
-        c1, c2 = blk.c1, blk.c2
-        fr_slope = blk.fromRGB.slope
-        if rec.last:
-            gz2 = g                                                           # [nh,1,1,C]
-            a1, mb, inp = rec.a1, rec.mb, rec.inp
-            if full:
-                _wgrad(a1[:nh], gz2, c2, nh, H)
-            gz1 = _dgrad(D, gz2, c2, nh, 1, mask=a1[:nh], mask_slope=c1.slope)
-            if full:
-                _wgrad(mb[:nh], gz1, c1, nh, H)
-            gmb = _dgrad(D, gz1, c1, nh, H)                                   # [nh,4,4,CP]
-            cp = c1.cin_store
-            if hvp is None:
-                gin = _mbstd_bwd(D, gmb, inp, rec.stats, cp, rec.first, fr_slope)
-            else:
-                gin = _mbstd_bwd_hvp(D, gmb, None, rec, hvp, fr_slope)
-            if save_adjoints:
-                adj[idx].gz2, adj[idx].gz1, adj[idx].gmb = gz2, gz1, gmb
-        else:
-            gz2 = g
-            if carry is not None:                  # gz2 = pool adjoint of the coarser gradient, evaluated inside the two consumers
-                gc, gb, gmul, gsl = carry
-                carry = None
-                try:
-                    gz1 = ops.conv2d_unpooled(gc, _wt(D, c2), gb, gmul, gsl, NB, H, H, c2.c,
-                                              mask=rec.a1b if rec.a1b is not None else rec.a1, mask_slope=c1.slope)
-                    if full:
-                        _flush_wgrad(c2)           # (this launch does not go through _wgrad: a deferred tangent term rides nowhere)
-                        with _on_side(rec.a1, gc, gb):
-                            ops.conv2d_wgrad_unpooled(rec.a1, gc, gb, gmul, gsl, c2._gw, c2._gb, NB, H, H, c2.c)
-                except ops.Unsupported:                    # (shape checks are identical for both entry points: nothing was accumulated)
-                    FALLBACKS['lazy unpool %dx%d' % (H, H)] += 1
-                    gz2 = ops.avgpool2_bwd(gc, _mask32(gb), 4.0 * gmul, gsl)
-                    if full:
-                        _wgrad(rec.a1, gz2, c2, NB, H)
-                    gz1 = _dgrad(D, gz2, c2, NB, H, mask=(rec.a1, rec.a1b), mask_slope=c1.slope)
-            else:
-                if full:
-                    _wgrad(rec.a1, gz2, c2, NB, H)
-                gz1 = _dgrad(D, gz2, c2, NB, H, mask=(rec.a1, rec.a1b), mask_slope=c1.slope)
-            if full:
-                _wgrad(rec.inp, gz1, c1, NB, H, on_main=rec.first and tail >= 2)
-            g_fused = None
-            if not rec.first and not (recs[idx - 1].first and alpha < 1.0):
-                pv = recs[idx - 1]
-                if _lazy_unpool_ok(pv, save_adjoints):
-                    # plain coarse gradient; the finer block's c2 consumers apply the pool adjoint in their gathers
-                    carry = (_dgrad(D, gz1, c1, NB, H), pv.a2, 0.25, pv.blk.c2.slope)
-                else:
-                    # backward-data conv + pool adjoint + LeakyReLU' of the finer block's output in one kernel
-                    g_fused = _dgrad_unpool(D, gz1, c1, NB, H, pv.a2, 1.0, pv.blk.c2.slope)
-                gin = None
-            else:
-                gin = None
-                # fromRGB's weight gradient rides in the same epilogue when the sweep asks for weight gradients -- not under a bucketed
-                # gradient exchange, whose flushes wait for the weight-gradient stream only (as the tail launches on the main stream)
-                fw = full and D._rt.grad_hook is None
-                if (rec.first and (want_gimg or fw) and rec.inpb is not None and x.is_cuda and c1.ksize == 3 and c1.pad == 1
-                        and _wino(c1, NB, H, c1.conv.weight.shape[3], transposed=True) is None):
-                    # the entry block's backward-data conv hands the IMAGE gradient on as well (fromRGB's backward-data in its epilogue); the
-                    # 8-channel gradient itself is written only when somebody reads it afterwards (the tangent term of the gradient penalty)
-                    fr0 = blk.fromRGB
-                    try:
-                        gin, gi = ops.conv2d_masked_fromrgb_bwd(gz1, _wt(D, c1), rec.inpb, fr_slope, fr0.conv.weight.data, fr0.c, NB, C, H, H, c1.c,
-                                                                keep_gf=save_adjoints or (full and not fw), want_gimg=want_gimg,
-                                                                img=x if fw else None, rgb_dw=fr0._gw if fw else None, rgb_db=fr0._gb if fw else None)
-                        if want_gimg:
-                            gimg = gi
-                        gimg_fused, fw_fused = True, fw
-                    except ops.Unsupported:
-                        FALLBACKS['fromRGB adjoint in the epilogue %dx%d' % (H, H)] += 1
-                if not gimg_fused:
-                    gin = _dgrad(D, gz1, c1, NB, H, mask=(rec.inp, rec.inpb) if rec.first else None, mask_slope=fr_slope)
-            if save_adjoints:
-                adj[idx].gz2, adj[idx].gz1 = gz2, gz1
-        if rec.first:
-            gf = gin                                                          # adjoint of fromRGB pre-activation
-            fr = blk.fromRGB
-            if save_adjoints:
-                adj[idx].gf = gf
-            if full and not fw_fused:
-                with (_on_main if tail >= 1 else _on_side)(gf, x):
-                    ops.fromrgb_wgrad(gf, x, fr._gw, fr._gb, NB, C, H, H, fr.c)
-            if want_gimg:
-                if not gimg_fused:
-                    gimg = torch.empty_like(x)
-                    ops.fromrgb_bwd_data(gf, fr.conv.weight.data, gimg, NB, C, H, H, fr.c)
-                if pending_prev is not None:
-                    gpf, pfr = pending_prev
-                    ops.fromrgb_bwd_data(gpf, pfr.conv.weight.data, gimg, NB, C, H // 2, H // 2, pfr.c,
-                                         pool=True, accumulate=True)
-        else:
-            prev = recs[idx - 1]
-            pc2 = prev.blk.c2
-            if prev.first and alpha < 1.0:
-                if _lazy_unpool_ok(prev, save_adjoints):
-                    # fade-in at the 1024^2 stage: the same lazy pool adjoint as in the fully grown stage (x alpha); the entry block's c2
-                    # consumers evaluate it in their gathers instead of reading a 604 MB fine-resolution gradient (round 4)
-                    carry = (gin, prev.a2, 0.25 * alpha, pc2.slope)
-                    g = None
-                else:
-                    g = ops.avgpool2_bwd(gin, _mask32(prev.a2), alpha, pc2.slope)
-                pfr = blk.fromRGB                                             # the block whose fromRGB fed the fade-in
-                gpf = ops.axpby_mask(gin, mask=prev.pf, a=1.0 - alpha, mask_slope=pfr.slope)
-                if save_adjoints:
-                    adj[idx - 1].gpf = gpf
-                if full:
-                    with _on_side(gpf, x):
-                        ops.fromrgb_wgrad(gpf, x, pfr._gw, pfr._gb, NB, C, H, H, pfr.c, pool=True)
-                pending_prev = (gpf, pfr)
-            elif not rec.last and g_fused is not None:
-                g = g_fused
-            elif carry is not None:
-                g = None                            # consumed through ``carry`` by the next (finer) block
-            else:
-                g = ops.avgpool2_bwd(gin, _mask32(prev.a2), 1.0, pc2.slope)
+    def lazy(up, _):
+        if up is not hand.up.bytes:                # the redo: the pool adjoint as a launch of its own, c2's own launches below
+            return ops.avgpool2_bwd(hand.coarse, up, 4.0 * hand.mul, hand.up.slope), None
+        gz1 = ops.conv2d_unpooled(hand.coarse, _wt(D, c2), up, hand.mul, hand.up.slope, n, H, H, c2.c,
+                                  mask=a1.bytes if a1.bytes is not None else a1.f32, mask_slope=a1.slope)
         if full:
-            _grads_ready(D, _d_block_done(D, recs, idx, alpha))
-    return gimg, adj
-
-
-def _d_block_done(D, recs, idx, alpha):
-    """Layers whose weight gradients are complete once block ``idx`` of the batched backward sweep has been processed
-    (the tangent pass ran before the sweep, so nothing else accumulates into them)."""
-    rec = recs[idx]
-    blk = rec.blk
-    done = [blk.c1, blk.c2]
-    if rec.last:
-        done.append(D._lin_layer)
-    if rec.first or (recs[idx - 1].first and alpha < 1.0):
-        done.append(blk.fromRGB)                 # the entry block's fromRGB / the fade-in branch's fromRGB
-    return done
+            _flush_wgrad(c2)                       # (this launch does not go through _wgrad: a deferred tangent term rides nowhere)
+            with _on_side(a1.f32, hand.coarse, up):
+                ops.conv2d_wgrad_unpooled(a1.f32, hand.coarse, up, hand.mul, hand.up.slope, c2._gw, c2._gb, n, H, H, c2.c)
+        return None, gz1                           # (shape checks are identical for both entry points: nothing was accumulated on failure)
+    gz2, gz1 = (hand.g, None) if hand.g is not None else _bytes_first(lazy, hand.up, lambda: 'lazy unpool %dx%d' % (H, H))
+    if gz1 is None:
+        if full:
+            _wgrad(a1.f32, gz2, c2, n, H)
+        gz1 = _dgrad(D, gz2, c2, n, 1 if rec.last else H, a1)
+    return gz2, gz1
 
 
 _NO_INJECTION = saved.PNInjection()
@@ -1069,98 +935,179 @@ def _pn_bwd(gy, y, r, slope, nh, inj):
     return gy
 
 
-def _d_backward_pn(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
-    """``d_backward`` for Discriminator(pixelnorm=True): every c1/c2 is conv -> LeakyReLU -> PixelNorm
-    (network.py:32-41), so the masks can no longer be fused into the backward-data convs; the adjoint of each
-    (LeakyReLU, PixelNorm) pair is one ``pixelnorm_lrelu_bwd`` launch.  With ``hvp`` the mixed images [nh:]
-    take the minibatch-stddev AND the per-layer PixelNorm Hessian-vector injections (``hvp.injs``)."""
-    D._ensure_buffers()
-    NB, alpha = ctx.NB, ctx.alpha
-    x = ctx.x
-    C = D.num_channels
-    recs = ctx.recs
-    adj = [saved.DAdjoint() for _ in recs] if save_adjoints else None
-    lastrec = recs[-1]
-    nh = NB if hvp is None else hvp.n_head
-    injs = None if hvp is None else hvp.injs
-    a2 = lastrec.a2
-    gtop = ops.linear1_bwd_data(gscore, D.linear.weight.data, None, (nh,) + tuple(a2.shape[1:]))
-    if nh < NB:                                      # mixed images: zero score gradient, injections only
-        g = torch.empty_like(a2)                     # (C-ABI launches, not ATen ops: a launch plan replays only those)
+def _pn_head_seed(D, gscore, a2, nh):
+    """The head of the PixelNorm discriminator's sweep: the adjoint wrt the NORMALISED ``a2`` (no mask), the mixed images [nh:] with
+    a zero score gradient (they take injections only)."""
+    g = ops.linear1_bwd_data(gscore, D.linear.weight.data, None, (nh,) + tuple(a2.shape[1:]))
+    if nh < a2.shape[0]:
+        gtop, g = g, torch.empty_like(a2)            # (C-ABI launches, not ATen ops: a launch plan replays only those)
         ops.zero_(g[nh:])
         ops.axpby_mask(gtop, a=1.0, out=g[:nh])
-    else:
-        g = gtop
+    return g
+
+
+def _pn_adjoints(D, hand, rec, n, nh, full, adj, inj):
+    """``_consume`` for Discriminator(pixelnorm=True): every c1/c2 is conv -> LeakyReLU -> PixelNorm (network.py:32-41), so the masks
+    can no longer be fused into the backward-data convs; the adjoint of each (LeakyReLU, PixelNorm) pair is one ``pixelnorm_lrelu_bwd``
+    launch, which on the mixed images [nh:] adds the PixelNorm Hessian-vector injections ``inj``.  ``adj`` takes copies of gy2 / gy1."""
+    c1, c2, H = rec.blk.c1, rec.blk.c2, rec.H
+    if adj is not None:
+        adj.gy2 = ops.axpby_mask(hand.g, a=1.0)              # device copy through the C-ABI (recorded by a launch plan)
+    gz2 = _pn_bwd(hand.g, rec.a2, rec.r2, c2.slope, nh, inj.inj2)
     if full:
-        ops.linear1_wgrad(gscore, a2[:nh], D._lin_gw, D._lin_gb)
+        _wgrad(rec.a1, gz2, c2, n, H)
+    gy1 = _dgrad(D, gz2, c2, n, 1 if rec.last else H)
+    if adj is not None:
+        adj.gy1 = ops.axpby_mask(gy1, a=1.0)
+    return gz2, _pn_bwd(gy1, rec.a1, rec.r1, c1.slope, nh, inj.inj1)
+
+
+def _fade_in(D, ctx, rec, prev, gin, full, adj):
+    """The fade-in branch behind the entry block (network.py:230-233): the adjoint of ``rec``'s fromRGB of the pooled image from the coarse
+    gradient ``gin`` (x (1 - alpha), x LeakyReLU' of the entry block ``prev``'s pf), and that layer's weight gradient.  Returns (gpf, the layer) for ``_entry`` to add to the image gradient."""
+    pfr = rec.blk.fromRGB                                   # the block whose fromRGB fed the fade-in
+    x, H = ctx.x, rec.H
+    gpf = ops.axpby_mask(gin, mask=prev.pf, a=1.0 - ctx.alpha, mask_slope=pfr.slope)
+    if adj is not None:
+        adj.gpf = gpf
+    if full:
+        with _on_side(gpf, x):
+            ops.fromrgb_wgrad(gpf, x, pfr._gw, pfr._gb, ctx.NB, D.num_channels, H, H, pfr.c, pool=True)
+    return gpf, pfr
+
+
+def _hand_over(D, ctx, rec, prev, gz1, gin, full, adj, pn):
+    """What block ``rec`` hands to the finer block ``prev``: c1's backward-data conv (``gin`` None; the 4x4 block comes with its input
+    adjoint) and the pool adjoint -- in one launch, left lazy for prev's c2 consumers, or as two launches; at the fade-in boundary
+    x alpha, with the fade-in branch beside it.  Returns (saved.PoolAdjoint, ``_fade_in``'s result or None).  ``adj``: prev's DAdjoint."""
+    c1, H, NB = rec.blk.c1, rec.H, ctx.NB
+    fade = prev.first and ctx.alpha < 1.0
+    mul = ctx.alpha if fade else 1.0
+    up = None if pn else saved.Sign.a2(prev)                # (PixelNorm: the adjoint wrt the NORMALISED a2, no mask)
+    lazy = not pn and (gin is None or fade) and _lazy_unpool_ok(prev, adj is not None)    # (the 4x4 block's own hand-over is never lazy)
+    if gin is None and not (fade or lazy or pn):
+        # backward-data conv + pool adjoint + LeakyReLU' of the finer block's output in one kernel
+        return saved.PoolAdjoint(g=_dgrad_unpool(D, gz1, c1, NB, H, up, 1.0)), None
+    if gin is None:
+        gin = _dgrad(D, gz1, c1, NB, H)
+    if lazy:
+        # plain coarse gradient; the finer block's c2 consumers apply the pool adjoint in their gathers instead of reading a fine-resolution
+        # gradient (604 MB at the 1024^2 stage) -- across the fade-in boundary too (x alpha, round 4)
+        hand = saved.PoolAdjoint(coarse=gin, up=up, mul=0.25 * mul)
+    elif pn:
+        hand = saved.PoolAdjoint(g=ops.avgpool2_bwd(gin, None, mul))
+    else:
+        hand = saved.PoolAdjoint(g=ops.avgpool2_bwd(gin, _f32(up), mul, up.slope))
+    return hand, (_fade_in(D, ctx, rec, prev, gin, full, adj) if fade else None)
+
+
+def _entry(D, ctx, rec, gz1, gin, full, want_gimg, adj, faded, tail, pn):
+    """The entry block's end of the sweep: gf, the adjoint of fromRGB's pre-activation (``gin`` None: c1's backward-data conv is still to
+    run; at depth 0 the minibatch-stddev adjoint came with it), fromRGB's weight gradient and, with ``want_gimg``, the image gradient
+    (returned) including the fade-in branch's (``faded``).  Where the shape allows -- never under PixelNorm (``pn``), whose adjoints are
+    not masked convs -- fromRGB's backward-data and its weight gradient ride in the epilogue of c1's backward-data conv."""
+    blk, H, NB, x, C = rec.blk, rec.H, ctx.NB, ctx.x, D.num_channels
+    c1, fr = blk.c1, blk.fromRGB
     gimg = None
-    pending_prev = None
+    fused = fw_fused = False           # the backward-data conv wrote the image gradient / accumulated fromRGB's weight gradient itself
+    # fromRGB's weight gradient rides in the same epilogue when the sweep asks for weight gradients -- not under a bucketed
+    # gradient exchange, whose flushes wait for the weight-gradient stream only (as the tail launches on the main stream)
+    fw = full and D._rt.grad_hook is None
+    if (not pn and gin is None and (want_gimg or fw) and rec.inpb is not None and x.is_cuda and c1.ksize == 3 and c1.pad == 1
+            and _wino(c1, NB, H, c1.conv.weight.shape[3], transposed=True) is None):
+        # the 8-channel gradient itself is written only when somebody reads it afterwards (the tangent term of the gradient penalty)
+        try:
+            gin, gimg = ops.conv2d_masked_fromrgb_bwd(gz1, _wt(D, c1), rec.inpb, fr.slope, fr.conv.weight.data, fr.c, NB, C, H, H, c1.c,
+                                                      keep_gf=adj is not None or (full and not fw), want_gimg=want_gimg,
+                                                      img=x if fw else None, rgb_dw=fr._gw if fw else None, rgb_db=fr._gb if fw else None)
+            fused, fw_fused = True, fw
+        except ops.Unsupported:
+            FALLBACKS['fromRGB adjoint in the epilogue %dx%d' % (H, H)] += 1
+    if gin is None and not fused:
+        gin = _dgrad(D, gz1, c1, NB, H, saved.Sign.inp(rec))
+    if adj is not None:
+        adj.gf = gin
+    if full and not fw_fused:
+        with (_on_main if tail >= 1 else _on_side)(gin, x):
+            ops.fromrgb_wgrad(gin, x, fr._gw, fr._gb, NB, C, H, H, fr.c)
+    if not want_gimg:
+        return None
+    if not fused:
+        gimg = torch.empty_like(x)
+        ops.fromrgb_bwd_data(gin, fr.conv.weight.data, gimg, NB, C, H, H, fr.c)
+    if faded is not None:
+        gpf, pfr = faded
+        ops.fromrgb_bwd_data(gpf, pfr.conv.weight.data, gimg, NB, C, H // 2, H // 2, pfr.c, pool=True, accumulate=True)
+    return gimg
+
+
+def d_backward(D, ctx, gscore, full, want_gimg, save_adjoints=False, hvp=None):
+    """First-order adjoint sweep through D for the batch in ``ctx``.
+
+    gscore [NB] : d loss / d score.   full: also accumulate weight/bias gradients.
+    want_gimg   : return d loss / d input image (NCHW).
+    hvp         : saved.Hvp — the last ``NB-n_head`` images form one extra group
+                  whose score gradient is zero and which only receives the minibatch-stddev
+                  Hessian-vector injection (and, in a PixelNorm discriminator, the per-layer
+                  injections ``hvp.injs``); ``gscore`` then has n_head entries."""
+    wait_pending(D)
+    D._ensure_buffers()
+    pn = bool(getattr(D, 'pixelnorm', False))
+    NB, alpha, recs = ctx.NB, ctx.alpha, ctx.recs
+    adj = [saved.DAdjoint() for _ in recs] if save_adjoints else [None] * len(recs)
+    nh = NB if hvp is None else hvp.n_head
+    injs = hvp.injs if pn and hvp is not None else None
+    n4 = NB if pn else nh                                    # images the 4x4 block's convs run over (PixelNorm: the mixed ones take injections there)
+    a2 = recs[-1].a2
+    tail = _tail_wgrad_on_main(recs[0].H) if (full and not pn and ASYNC_WGRAD and D._rt.grad_hook is None and len(recs) > 1) else 0
+    if full and not pn:
+        ops.linear1_wgrad(gscore, a2[:nh], D._lin_gw, D._lin_gb)
+    hand = saved.PoolAdjoint(g=_pn_head_seed(D, gscore, a2, nh) if pn else ops.linear1_bwd_data(
+        gscore, D.linear.weight.data, a2[:nh], (nh,) + tuple(a2.shape[1:]), recs[-1].blk.c2.slope))
+    if full and pn:                                  # (behind the seed: the order this sweep has always issued them in)
+        ops.linear1_wgrad(gscore, a2[:nh], D._lin_gw, D._lin_gb)
+    gimg = faded = None
     for idx in range(len(recs) - 1, -1, -1):
         rec = recs[idx]
-        blk, H = rec.blk, rec.H
-        c1, c2 = blk.c1, blk.c2
-        fr_slope = blk.fromRGB.slope
-        inj = injs[idx] if injs is not None else _NO_INJECTION
-        if save_adjoints:
-            adj[idx].gy2 = ops.axpby_mask(g, a=1.0)          # device copy through the C-ABI (recorded by a launch plan)
-        gz2 = _pn_bwd(g, rec.a2, rec.r2, c2.slope, nh, inj.inj2)
-        Hc2 = 1 if rec.last else H
+        c1, H = rec.blk.c1, rec.H
+        n = n4 if rec.last else NB
+        if pn:
+            gz2, gz1 = _pn_adjoints(D, hand, rec, n, nh, full, adj[idx], injs[idx] if injs is not None else _NO_INJECTION)
+        else:
+            gz2, gz1 = _consume(D, hand, rec, n, full)
         if full:
-            _wgrad(rec.a1, gz2, c2, NB, H)
-        gy1 = _dgrad(D, gz2, c2, NB, Hc2)
-        if save_adjoints:
-            adj[idx].gy1 = ops.axpby_mask(gy1, a=1.0)
-        gz1 = _pn_bwd(gy1, rec.a1, rec.r1, c1.slope, nh, inj.inj1)
+            _wgrad(rec.mb[:n] if rec.last else rec.inp, gz1, c1, n, H, on_main=rec.first and not rec.last and tail >= 2)
+        gin = None
         if rec.last:
-            mb, inp = rec.mb, rec.inp
-            if full:
-                _wgrad(mb, gz1, c1, NB, H)
-            gmb = _dgrad(D, gz1, c1, NB, H)                                   # [NB,4,4,CP]
-            cp = c1.cin_store
+            gmb = _dgrad(D, gz1, c1, n, H)                                    # [n,4,4,CP]
             if hvp is None:
-                gin = _mbstd_bwd(D, gmb, inp, rec.stats, cp, rec.first, fr_slope)
+                gin = _mbstd_bwd(D, gmb, rec.inp, rec.stats, c1.cin_store, rec.first, rec.blk.fromRGB.slope)
             else:
-                gin = _mbstd_bwd_hvp(D, gmb[:nh], gmb[nh:], rec, hvp, fr_slope)
-            if save_adjoints:
-                adj[idx].gz2, adj[idx].gz1, adj[idx].gmb = gz2, gz1, gmb
-        else:
-            if full:
-                _wgrad(rec.inp, gz1, c1, NB, H)
-            gin = _dgrad(D, gz1, c1, NB, H, mask=rec.inp if rec.first else None, mask_slope=fr_slope)
-            if save_adjoints:
-                adj[idx].gz2, adj[idx].gz1 = gz2, gz1
+                gin = _mbstd_bwd_hvp(D, gmb[:nh], gmb[nh:] if pn else None, rec, hvp, rec.blk.fromRGB.slope)
+        if save_adjoints:
+            adj[idx].gz2, adj[idx].gz1 = gz2, gz1
+            if rec.last:
+                adj[idx].gmb = gmb
         if rec.first:
-            gf = gin
-            fr = blk.fromRGB
-            if save_adjoints:
-                adj[idx].gf = gf
-            if full:
-                with _on_side(gf, x):
-                    ops.fromrgb_wgrad(gf, x, fr._gw, fr._gb, NB, C, H, H, fr.c)
-            if want_gimg:
-                gimg = torch.empty_like(x)
-                ops.fromrgb_bwd_data(gf, fr.conv.weight.data, gimg, NB, C, H, H, fr.c)
-                if pending_prev is not None:
-                    gpf, pfr = pending_prev
-                    ops.fromrgb_bwd_data(gpf, pfr.conv.weight.data, gimg, NB, C, H // 2, H // 2, pfr.c,
-                                         pool=True, accumulate=True)
+            gimg = _entry(D, ctx, rec, gz1, gin, full, want_gimg, adj[idx], faded, tail, pn)
         else:
-            prev = recs[idx - 1]
-            if prev.first and alpha < 1.0:
-                g = ops.avgpool2_bwd(gin, None, alpha)                        # adjoint wrt the NORMALISED a2
-                pfr = blk.fromRGB
-                gpf = ops.axpby_mask(gin, mask=prev.pf, a=1.0 - alpha, mask_slope=pfr.slope)
-                if save_adjoints:
-                    adj[idx - 1].gpf = gpf
-                if full:
-                    with _on_side(gpf, x):
-                        ops.fromrgb_wgrad(gpf, x, pfr._gw, pfr._gb, NB, C, H, H, pfr.c, pool=True)
-                pending_prev = (gpf, pfr)
-            else:
-                g = ops.avgpool2_bwd(gin, None, 1.0)
+            hand, faded = _hand_over(D, ctx, rec, recs[idx - 1], gz1, gin, full, adj[idx - 1], pn)
         if full:
             _grads_ready(D, _d_block_done(D, recs, idx, alpha))
-    return gimg, adj
+    return gimg, (adj if save_adjoints else None)
+
+
+def _d_block_done(D, recs, idx, alpha):
+    """Layers whose weight gradients are complete once block ``idx`` of the batched backward sweep has been processed
+    (the tangent pass ran before the sweep, so nothing else accumulates into them)."""
+    rec = recs[idx]
+    blk = rec.blk
+    done = [blk.c1, blk.c2]
+    if rec.last:
+        done.append(D._lin_layer)
+    if rec.first or (recs[idx - 1].first and alpha < 1.0):
+        done.append(blk.fromRGB)                 # the entry block's fromRGB / the fade-in branch's fromRGB
+    return done
 
 
 def d_tangent_wgrad(D, sub, adj, u):
@@ -1178,14 +1125,8 @@ def d_tangent_wgrad(D, sub, adj, u):
     H = rec0.H
     with _on_side(adj[0].gf, u):
         ops.fromrgb_wgrad(adj[0].gf, u, fr._gw, None, N, C, H, H, fr.c)
-    cur = None
-    if rec0.inpb is not None:
-        try:
-            cur = ops.fromrgb_fwd(u, fr.conv.weight.data, None, N, C, H, H, fr.c, 1.0, mask=rec0.inpb, mask_slope=fr.slope)
-        except ops.Unsupported:
-            cur = None
-    if cur is None:
-        cur = ops.fromrgb_fwd(u, fr.conv.weight.data, None, N, C, H, H, fr.c, 1.0, mask=rec0.inp, mask_slope=fr.slope)
+    cur = _bytes_first(lambda m, _: ops.fromrgb_fwd(u, fr.conv.weight.data, None, N, C, H, H, fr.c, 1.0, mask=m, mask_slope=fr.slope),
+                       saved.Sign.inp(rec0), None, count=False)
     hvp = None
     t2 = None
     pn = bool(getattr(D, 'pixelnorm', False))
@@ -1197,16 +1138,16 @@ def d_tangent_wgrad(D, sub, adj, u):
             tmb, tstats = _mbstd_tangent(D, rec.inp, cur, rec.stats, c1.cin_store)
             hvp = saved.Hvp(tx=cur, tstats=tstats, gy_first=adj[idx].gmb, injs=injs)
             _wgrad(tmb, adj[idx].gz1, c1, N, H, bias=False, defer=True)
-            t1 = _conv(tmb, c1, N, H, mask=rec.a1, bias=False)
+            t1 = _conv(tmb, c1, N, H, mask=saved.Sign.a1(rec), bias=False)
             if pn:
                 t1, injs[idx].inj1 = ops.pixelnorm_tangent(t1, rec.a1, rec.r1, adj[idx].gy1)
             _wgrad(t1, adj[idx].gz2, c2, N, H, bias=False, defer=True)
-            t2 = _conv(t1, c2, N, H, mask=rec.a2, bias=False)
+            t2 = _conv(t1, c2, N, H, mask=saved.Sign.a2(rec), bias=False)
             if pn:
                 t2, injs[idx].inj2 = ops.pixelnorm_tangent(t2, rec.a2, rec.r2, adj[idx].gy2)
         else:
             _wgrad(cur, adj[idx].gz1, c1, N, H, bias=False, defer=True)
-            t1 = _conv(cur, c1, N, H, mask=(rec.a1, rec.a1b), bias=False)
+            t1 = _conv(cur, c1, N, H, mask=saved.Sign.a1(rec), bias=False)
             if pn:
                 t1, injs[idx].inj1 = ops.pixelnorm_tangent(t1, rec.a1, rec.r1, adj[idx].gy1)
             _wgrad(t1, adj[idx].gz2, c2, N, H, bias=False, defer=True)
@@ -1219,11 +1160,11 @@ def d_tangent_wgrad(D, sub, adj, u):
                                       pool=True, mask=rec.pf, mask_slope=nfr.slope)
             pa, pb = (alpha, 1.0 - alpha) if tpf is not None else (1.0, 0.0)
             if pn:
-                t2 = _conv(t1, c2, N, H, mask=rec.a2, bias=False)
+                t2 = _conv(t1, c2, N, H, mask=saved.Sign.a2(rec), bias=False)
                 t2, injs[idx].inj2 = ops.pixelnorm_tangent(t2, rec.a2, rec.r2, adj[idx].gy2)
                 cur = ops.avgpool2_fwd(t2, tpf, pa, pb)
             else:                                                 # only the pooled tangent is needed downstream
-                t2, cur = _conv_pool(t1, c2, N, H, bias=False, mask=rec.a2, other=tpf, a=pa, b=pb, pool_only=True)
+                t2, cur = _conv_pool(t1, c2, N, H, bias=False, mask=saved.Sign.a2(rec), other=tpf, a=pa, b=pb, pool_only=True)
     # Linear: d/dw <ones, w . t2> = sum_n t2[n]
     ops.linear1_wgrad(_ones(N, u.device), t2, D._lin_gw, None)
     return hvp

@@ -3,7 +3,12 @@ Hessian-vector terms the gradient-penalty sweeps pass on, and the two loss state
 feature that saves something new declares it here, ONCE, in the class's ``LAYOUT`` table together with the layout of its leading extent --
 ``slice_rows`` / ``merge_rows`` / ``tensors`` below are driven by those tables, so a declared tensor cannot be forgotten by the
 gradient-penalty slice, the three-pass merge or the cross-stream hand-over.  A field a path does not produce is None.
-Imports nothing from the package."""
+``Sign`` and ``PoolAdjoint`` at the end are what the D sweeps build from these records at the point of use (closed too, but never
+saved, sliced or merged: no table).  Imports nothing from the package."""
+
+import collections
+
+import torch
 
 # layout of a field's leading extent
 IMG = 'image-major'       # rows = images: [n, ...]
@@ -62,8 +67,8 @@ class GContext(_Record):
 
 
 class DBlock(_Record):
-    """One block of a discriminator pass.  Writer: engine.d_forward; readers: d_backward / _d_backward_pn, d_tangent_wgrad,
-    _mbstd_bwd_hvp."""
+    """One block of a discriminator pass.  Writer: engine.d_forward; readers: d_backward and its steps (through ``Sign.a1`` / ``a2`` /
+    ``inp`` wherever only the sign of an activation is read), d_tangent_wgrad, _mbstd_bwd_hvp."""
     LAYOUT = {
         'blk': None,      # the DBlock module
         'H': None,        # input resolution of the block
@@ -85,7 +90,7 @@ class DBlock(_Record):
 
 class DContext(_Record):
     """A discriminator pass over ``groups`` stacked minibatches.  Writer: engine.d_forward, ``merge`` (three passes -> one batch),
-    ``slice`` (the mixed third for the gradient penalty); readers: d_backward / _d_backward_pn, d_tangent_wgrad, d_loss_backward."""
+    ``slice`` (the mixed third for the gradient penalty); readers: d_backward, d_tangent_wgrad, d_loss_backward."""
     LAYOUT = {
         'NB': None,       # images
         'groups': None,   # minibatch-stddev groups
@@ -111,7 +116,7 @@ class DContext(_Record):
 
 
 class DAdjoint(_Record):
-    """First-backward adjoints of one block under the gradient penalty.  Writer: d_backward / _d_backward_pn(save_adjoints=True);
+    """First-backward adjoints of one block under the gradient penalty.  Writer: d_backward(save_adjoints=True) (gy1 / gy2: _pn_adjoints);
     reader: d_tangent_wgrad (the other factor of every tangent weight gradient)."""
     LAYOUT = {
         'gz2': IMG,       # adjoint of c2's pre-activation
@@ -126,7 +131,7 @@ class DAdjoint(_Record):
 
 
 class PNInjection(_Record):
-    """PixelNorm Hessian-vector injections of one block.  Writer: d_tangent_wgrad (ops.pixelnorm_tangent); reader: _d_backward_pn."""
+    """PixelNorm Hessian-vector injections of one block.  Writer: d_tangent_wgrad (ops.pixelnorm_tangent); reader: _pn_adjoints."""
     LAYOUT = {
         'inj1': IMG,      # added to the adjoint of a1's (LeakyReLU -> PixelNorm) on the mixed images
         'inj2': IMG,      # ... of a2's
@@ -137,7 +142,7 @@ class PNInjection(_Record):
 class Hvp(_Record):
     """Hessian-vector bundle of the gradient penalty: the last ``NB - n_head`` images of the batched sweep form one extra group whose
     score gradient is zero and which receives these injections.  Writer: d_tangent_wgrad (d_loss_backward adds n_head); readers:
-    d_backward / _d_backward_pn, _mbstd_bwd_hvp."""
+    d_backward, _mbstd_bwd_hvp."""
     LAYOUT = {
         'n_head': None,   # images in front of the mixed ones ([real | fake]: 2N)
         'tx': IMG,        # tangent of the minibatch-stddev input
@@ -242,3 +247,42 @@ def tensors(rec, seen=None):
         elif id(v) not in seen:
             seen.add(id(v))
             yield v
+
+
+class Sign(collections.namedtuple('Sign', 'f32 bytes slope', defaults=(None, None, 0.2))):
+    """The sign of an activation, i.e. its LeakyReLU' mask: the fp32 activation, its sign bytes (1 byte per 4 channels), or both.  Built
+    from a DBlock where a mask is needed (an immutable triple: one is made per mask per sweep, on the eager path's host time);
+    engine._bytes_first is the one place that chooses between the two forms."""
+    __slots__ = ()
+
+    @classmethod
+    def a1(cls, rec, n=None):
+        """c1's output (its first ``n`` images: the 4x4 block under the gradient penalty)."""
+        if n is None:
+            return cls(rec.a1, rec.a1b, rec.blk.c1.slope)
+        return cls(rec.a1[:n], None if rec.a1b is None else rec.a1b[:n], rec.blk.c1.slope)
+
+    @classmethod
+    def a2(cls, rec):
+        """c2's output, kept in ONE of the two forms (DBlock.a2)."""
+        b = rec.a2.dtype == torch.uint8
+        return cls(None if b else rec.a2, rec.a2 if b else None, rec.blk.c2.slope)
+
+    @classmethod
+    def inp(cls, rec):
+        """The entry block's input (fromRGB's output)."""
+        return cls(rec.inp, rec.inpb, rec.blk.fromRGB.slope)
+
+
+class PoolAdjoint(object):
+    """What a block of the D adjoint sweep hands to the next finer block's c2.  Producer: engine._hand_over (and d_backward's head);
+    consumers: engine._consume / _pn_adjoints.  Either evaluated -- ``g``, the adjoint of c2's pre-activation (of its normalised output
+    under PixelNorm) -- or lazy: the gradient ``coarse`` of the pooled map, for c2's consumers to unpool in their gathers as
+    4 * ``mul`` * LeakyReLU'(``up``) * nearest-upsample(coarse), ``up`` being the Sign (bytes) of the finer c2's output."""
+    __slots__ = ('g', 'coarse', 'up', 'mul')
+
+    def __init__(self, g=None, coarse=None, up=None, mul=None):
+        if not ((coarse is None and up is None and mul is None) if g is not None else
+                (coarse is not None and mul is not None and up is not None and up.bytes is not None)):
+            raise ValueError('a pool adjoint is either evaluated (g) or lazy (coarse, up with sign bytes, mul)')
+        self.g, self.coarse, self.up, self.mul = g, coarse, up, mul

@@ -1,6 +1,6 @@
 """Discriminator(pixelnorm=True) (reference network.py:191-198 flag): PixelNorm after every
 c1/c2 makes D non-piecewise-linear, so the WGAN-GP double backward needs a per-layer Hessian-vector term
-(engine._d_backward_pn / pg_pixelnorm_tangent).  Checked against the CPU oracle (which differentiates the
+(engine.d_backward through _pn_adjoints / pg_pixelnorm_tangent).  Checked against the CPU oracle (which differentiates the
 reference's op sequence with torch autograd, create_graph=True) — host emulation on CPU, HIP kernels on the GPU."""
 import importlib
 import os

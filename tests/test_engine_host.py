@@ -644,3 +644,84 @@ def test_g_context_slice_is_the_row_range_of_every_declared_tensor(emu):
     # enumeration for the cross-stream hand-over: each distinct tensor object once (a block's inp IS the coarser output)
     ts = list(pg.saved.tensors(ctx))
     assert len(ts) == len(set(id(t) for t in ts)) == 5 + 4 * 2 and ctx.recs[0].inp is ctx.y2 and ctx.recs[1].inp is ctx.recs[0].a2
+
+
+# ---- the sign-byte fallback rule (engine._bytes_first) and the hand-over between D's blocks (saved.PoolAdjoint) --------------------------
+def test_bytes_first_rule(emu, monkeypatch):
+    eng, S = pg.engine, pg.saved
+    monkeypatch.setattr(eng, 'FALLBACKS', type(eng.FALLBACKS)())
+    y = torch.tensor([[1.0, -2.0, 3.0, -4.0]])
+    f32, by = y.clone(), emu_ops.signbytes_of(y)
+    calls = []
+
+    def refusing(mask, bytes_out):                                           # a launch without a byte-aware kernel
+        calls.append((mask, bytes_out))
+        if bytes_out or (torch.is_tensor(mask) and mask.dtype == torch.uint8):
+            raise emu_ops.Unsupported('bytes')
+        return 'redone'
+
+    def taking(mask, bytes_out):
+        calls.append((mask, bytes_out))
+        return 'bytes'
+
+    # refused bytes: counted once under the tag, redone with the fp32 copy AS GIVEN
+    assert eng._bytes_first(refusing, S.Sign(f32, by, 0.2), 'tag A') == 'redone'
+    assert dict(eng.FALLBACKS) == {'tag A': 1}
+    assert [c[0] is m for c, m in zip(calls, (by, f32))] == [True, True] and [c[1] for c in calls] == [False, False]
+    # ... bytes only: expanded for the second attempt, and only then
+    del calls[:]
+    expanded = []
+    monkeypatch.setattr(emu_ops, 'signbytes_to_mask', lambda b, _orig=emu_ops.signbytes_to_mask: expanded.append(b) or _orig(b))
+    assert eng._bytes_first(refusing, S.Sign(bytes=by), 'tag B') == 'redone'
+    assert eng.FALLBACKS['tag B'] == 1 and len(expanded) == 1 and expanded[0] is by
+    assert calls[1][0].dtype == torch.float32 and torch.equal(torch.sign(calls[1][0]), torch.sign(y))
+    # ... a byte OUTPUT (signs_out / y_bytes) is a request of the same kind: redone without it, the mask unchanged
+    del calls[:]
+    assert eng._bytes_first(refusing, S.Sign(f32), 'tag C', bytes_out=True) == 'redone'
+    assert eng._bytes_first(refusing, None, 'tag C', bytes_out=True) == 'redone'
+    assert eng.FALLBACKS['tag C'] == 2 and [(c[0] is f32, c[1]) for c in calls[:2]] == [(True, True), (True, False)]
+    assert [c for c in calls[2:]] == [(None, True), (None, False)]
+    assert len(expanded) == 1
+    # "do not count" (the tangent pass's fromRGB retry)
+    n = sum(eng.FALLBACKS.values())
+    assert eng._bytes_first(refusing, S.Sign(f32, by), 'tag D', count=False) == 'redone'
+    assert sum(eng.FALLBACKS.values()) == n and 'tag D' not in eng.FALLBACKS
+    # "redo": called in place of the second attempt (the launch expands the bytes itself), counted all the same; nothing is expanded for it
+    del calls[:]
+    assert eng._bytes_first(refusing, S.Sign(bytes=by), 'tag D2', redo=lambda: 'own redo') == 'own redo'
+    assert len(calls) == 1 and calls[0][0] is by and len(expanded) == 1 and eng.FALLBACKS['tag D2'] == 1
+    assert eng._bytes_first(taking, S.Sign(bytes=by), 'tag D2', redo=lambda: 'own redo') == 'bytes' and eng.FALLBACKS['tag D2'] == 1
+    # no byte in play: nothing to redo, Unsupported is the caller's -- and nothing is counted
+    def unsupported(mask, bytes_out):
+        calls.append((mask, bytes_out))
+        raise emu_ops.Unsupported('shape')
+    for sign in (S.Sign(f32), None):
+        del calls[:]
+        with pytest.raises(emu_ops.Unsupported):
+            eng._bytes_first(unsupported, sign, 'tag E')
+        assert len(calls) == 1
+    # ... nor when the second attempt is refused as well
+    with pytest.raises(emu_ops.Unsupported):
+        eng._bytes_first(unsupported, S.Sign(f32, by), 'tag F')
+    assert 'tag E' not in eng.FALLBACKS and eng.FALLBACKS['tag F'] == 1
+    # the byte call succeeds: one call, nothing counted, nothing expanded
+    del calls[:]
+    n = sum(eng.FALLBACKS.values())
+    assert eng._bytes_first(taking, S.Sign(f32, by), 'tag G') == 'bytes'
+    assert len(calls) == 1 and calls[0][0] is by and sum(eng.FALLBACKS.values()) == n and len(expanded) == 1
+
+
+def test_pool_adjoint_is_evaluated_or_lazy():
+    S = pg.saved
+    g, by = torch.zeros(1, 2, 2, 4), torch.zeros(1, 4, 4, 1, dtype=torch.uint8)
+    assert S.PoolAdjoint(g=g).coarse is None
+    lazy = S.PoolAdjoint(coarse=g, up=S.Sign(bytes=by, slope=0.2), mul=0.25)
+    assert lazy.g is None and lazy.up.bytes is by
+    for bad in (dict(), dict(g=g, coarse=g, up=S.Sign(bytes=by), mul=0.25), dict(g=g, mul=0.25), dict(coarse=g, mul=0.25),
+                dict(coarse=g, up=S.Sign(f32=g), mul=0.25), dict(coarse=g, up=S.Sign(bytes=by))):
+        with pytest.raises(ValueError):
+            S.PoolAdjoint(**bad)
+    for rec in (lazy, S.Sign()):
+        assert not hasattr(rec, '__dict__')
+        with pytest.raises(AttributeError):
+            rec.undeclared = 1

@@ -1,6 +1,7 @@
 """Winograd F(2x2,3x3) path (csrc/conv_wino.hip): kernel vs the direct-conv emulation, and the engine with the path forced
 on for every eligible layer vs the CPU oracle (host emulation on CPU, HIP on the GPU)."""
 import importlib
+import inspect
 import os
 import sys
 
@@ -35,30 +36,42 @@ def emu(monkeypatch):
     yield
 
 
-def _engine_vs_oracle(dev, monkeypatch, res, depth, alpha, n, kw=None):
-    monkeypatch.setattr(pg.engine, 'WINO_MIN_WORKGROUPS', 0)          # every eligible layer takes the Winograd path
+def _seeded_nets(res, kw):
     torch.manual_seed(21)
     shape = (1, 3, res, res)
+    return pg.Generator(shape, latent_size=64, **kw), pg.Discriminator(shape, **kw)
+
+
+def _oracle_case(res, depth, alpha, n, kw=None):
+    """Batch and the oracle's losses / gradients of one D step + one G step of the ``_seeded_nets``."""
     kw = kw or dict(fmap_base=256, fmap_max=64)
-    G = pg.Generator(shape, latent_size=64, **kw)
-    D = pg.Discriminator(shape, **kw)
+    G, D = _seeded_nets(res, kw)
     gp, dp = G.reference_state_dict(), D.reference_state_dict()
-    G.to(dev); D.to(dev)
     cfg = oracle.NetCfg(res, 3, latent_size=64, **kw)
+    real, z_d, z_g, mix = oracle.synthetic_batch(300 + depth, n, 3, 4 * 2 ** depth, 64)
+    return dict(kw=kw, batch=(real, z_d, z_g, mix), ref=oracle.d_loss_and_grads(dp, gp, cfg, real, z_d, mix, depth, alpha),
+                refg=oracle.g_loss_and_grads(gp, dp, cfg, z_g, depth, alpha))
+
+
+def _engine_vs_oracle(dev, monkeypatch, res, depth, alpha, n, kw=None, case=None):
+    """``case``: the ``_oracle_case`` of the same arguments where a module computes it once for several tests."""
+    monkeypatch.setattr(pg.engine, 'WINO_MIN_WORKGROUPS', 0)          # every eligible layer takes the Winograd path
+    case = case or _oracle_case(res, depth, alpha, n, kw)
+    G, D = _seeded_nets(res, case['kw'])
+    ref, refg = case['ref'], case['refg']
+    real, z_d, z_g, mix = case['batch']
+    G.to(dev); D.to(dev)
     G.depth = D.depth = depth
     G.alpha = D.alpha = alpha
-    real, z_d, z_g, mix = oracle.synthetic_batch(300 + depth, n, 3, 4 * 2 ** depth, 64)
     pg.wgan_gp_loss.set_mixing_factors(mix)
     d_cost, rl, fl = pg.wgan_gp_D_loss(D, G, real.to(dev), z_d.to(dev))
     d_cost.backward()
-    ref = oracle.d_loss_and_grads(dp, gp, cfg, real, z_d, mix, depth, alpha)
     assert rel_err(d_cost, ref['D_cost']) < 2e-4
     mine = reference_grads(D)
     for k, v in ref['grads'].items():
         assert rel_err(mine[k], v) < 2e-2, (k, rel_err(mine[k], v))
     g_cost = pg.wgan_gp_G_loss(G, D, z_g.to(dev))
     g_cost.backward()
-    refg = oracle.g_loss_and_grads(gp, dp, cfg, z_g, depth, alpha)
     assert rel_err(g_cost, refg['G_cost']) < 2e-4
     assert rel_err(G(z_g.to(dev)).cpu(), refg['fake']) < 2e-4
     gm = reference_grads(G)
@@ -402,6 +415,59 @@ def test_engine_with_sign_bytes_host(emu, monkeypatch, depth, alpha, n):
     _engine_vs_oracle('cpu', monkeypatch, 32, depth, alpha, n)
 
 
+def _is_bytes(t):
+    return torch.is_tensor(t) and t.dtype == torch.uint8
+
+
+# FALLBACKS tag -> (the entry points of ``ops`` behind it, which of their calls are sign-byte requests -- by bound argument).
+# 'conv masked' and 'dgrad masked' are the same launches with a byte mask (a forward and a backward-data conv differ in their weights
+# only), so either case forces both redos; ``_assert_fell_back`` tells them apart by the key that was counted.  The Winograd unpool launch
+# is not behind 'dgrad unpool': the engine passes its refusal on.
+_BYTE_REQUESTS = {
+    'conv signs_out': ('conv2d conv2d_wino', lambda a: a['signs_out']),
+    'conv masked': ('conv2d conv2d_wino', lambda a: _is_bytes(a['mask']) and not a.get('pool')),
+    'conv_pool': ('conv2d_pool conv2d_wino', lambda a: a.get('pool', True) and (a['y_bytes'] or _is_bytes(a['mask']))),
+    'dgrad masked': ('conv2d conv2d_wino', lambda a: _is_bytes(a['mask']) and not a.get('pool')),
+    'dgrad unpool': ('conv2d_unpool', lambda a: _is_bytes(a['upmask'])),
+    'lazy unpool': ('conv2d_unpooled', lambda a: _is_bytes(a['gbytes'])),
+    'fromRGB in the gather': ('conv2d_fromrgb', lambda a: a['signs_out']),
+    'fromRGB adjoint in the epilogue': ('conv2d_masked_fromrgb_bwd', lambda a: _is_bytes(a['mask_bytes'])),
+}
+
+
+def _refuse_byte_requests(monkeypatch, mod, tag):
+    """The entry points behind ``tag`` answer ``Unsupported`` to every sign-byte request, BEFORE the library is called (what PG_E_UNSUP
+    does: nothing is launched); every other call goes through."""
+    names, is_request = _BYTE_REQUESTS[tag]
+    for name in names.split():
+        def refusing(*a, _orig=getattr(mod, name), **k):
+            bound = inspect.signature(_orig).bind(*a, **k)
+            bound.apply_defaults()
+            if is_request(bound.arguments):
+                raise mod.Unsupported('refused by the test: ' + tag)
+            return _orig(*a, **k)
+        monkeypatch.setattr(mod, name, refusing)
+
+
+def _assert_fell_back(tag, before):
+    gained = [k for k, v in pg.engine.FALLBACKS.items() if k.startswith(tag) and v > before.get(k, 0)]
+    assert gained, 'no launch fell back under %r: the branch was not exercised (%r)' % (tag, dict(pg.engine.FALLBACKS))
+
+
+@pytest.mark.parametrize('tag', ['conv signs_out', 'conv masked', 'conv_pool', 'dgrad masked', 'dgrad unpool', 'lazy unpool'])
+def test_engine_redoes_refused_sign_byte_launches_host(emu, monkeypatch, tag):
+    """Every "bytes first, fp32 as the fallback" branch of the engine (engine._bytes_first), forced: same bounds against the oracle."""
+    monkeypatch.setattr(pg.engine, 'SIGN_BYTES_MIN_H', 8)
+    monkeypatch.setattr(pg.engine, 'USE_SIGN_BYTES', True)
+    if tag == 'dgrad unpool':                          # (direct kernels: only their unpool launch is behind the rule)
+        monkeypatch.setattr(pg.engine, 'USE_WINOGRAD', False)
+    _refuse_byte_requests(monkeypatch, E, tag)
+    before = dict(pg.engine.FALLBACKS)
+    # (the lazy pool adjoint needs an 8 -> 8/16-channel c2 at a multiple of 32 rows: fmap_base 128 gives 8 -> 16 at 32x32)
+    _engine_vs_oracle('cpu', monkeypatch, 32, 3, 1.0, 2, kw=dict(fmap_base=128, fmap_max=64) if tag == 'lazy unpool' else None)
+    _assert_fell_back(tag, before)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('depth,alpha,n,wino', [(3, 1.0, 3, True), (4, 0.6, 2, True), (4, 1.0, 2, False)])
 def test_engine_with_sign_bytes_gpu(monkeypatch, depth, alpha, n, wino):
@@ -423,6 +489,27 @@ def test_engine_with_lazy_pool_adjoint_gpu(monkeypatch, alpha):
     monkeypatch.setattr(pg.ops, 'conv2d_unpooled', lambda *a, **k: (calls.append(1), orig(*a, **k))[1])
     _engine_vs_oracle('cuda', monkeypatch, 128, 5, alpha, 2, kw=dict(fmap_base=512, fmap_max=64))
     assert len(calls) > 0                             # ... also across the fade-in boundary (x alpha) since round 4
+
+
+@pytest.fixture(scope='module')
+def lazy128_oracle():
+    """The oracle's side of the 128x128 case, once for all forced-fallback cases."""
+    return _oracle_case(128, 5, 1.0, 2, dict(fmap_base=512, fmap_max=64))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('tag,wino', [('conv signs_out', True), ('conv masked', True), ('conv_pool', True), ('dgrad masked', True),
+                                      ('lazy unpool', True), ('fromRGB in the gather', True), ('fromRGB adjoint in the epilogue', True),
+                                      ('conv masked', False), ('dgrad unpool', False)])
+def test_engine_redoes_refused_sign_byte_launches_gpu(monkeypatch, lazy128_oracle, tag, wino):
+    """The same on the GPU at the default byte threshold (64x64 up), with both fromRGB fusions: the HIP path against the oracle when the
+    entry points behind one FALLBACKS tag refuse their sign-byte requests (Winograd wherever eligible; ``wino`` False: direct kernels)."""
+    if not wino:
+        monkeypatch.setattr(pg.engine, 'USE_WINOGRAD', False)
+    _refuse_byte_requests(monkeypatch, pg.ops, tag)
+    before = dict(pg.engine.FALLBACKS)
+    _engine_vs_oracle('cuda', monkeypatch, 128, 5, 1.0, 2, case=lazy128_oracle)
+    _assert_fell_back(tag, before)
 
 
 @pytest.mark.gpu
