@@ -18,8 +18,8 @@ const char* pg_debug_last_conv_kernel(void);
 const char* pg_debug_last_wino_kernel(void);
 const char* pg_debug_last_wino_wgrad_kernel(void);
 
-/* Tuning aids (tools/sweeps/): force a configuration of the direct conv / weight-gradient kernels (csrc/conv_igemm.hip) for the
- * calling thread's next launches.  Value -1 restores the built-in choice of a key.  Callers pass the integers. */
+/* Tuning aids (tools/sweeps/): force a configuration of the direct conv / weight-gradient kernels (csrc/conv_igemm.hip, conv_thin.hip,
+ * conv_k4.hip, conv_wgrad.hip; the switches themselves live in conv_api.hip) for the calling thread's next launches.  Value -1 restores the built-in choice of a key.  Callers pass the integers. */
 enum pg_tune_key {
     PG_TUNE_CONV_TILE = 0,      /* value: index of the tile candidate (conv_igemm.hip, dispatch_conv) */
     PG_TUNE_WGRAD = 1,          /* value: enum pg_wgrad_cfg */

@@ -1,7 +1,7 @@
 // Row-streaming 3x3 convolution for the 8-cout layers of the 1024^2 stage (gfx950 / CDNA4).
 //
 // Replaces F.conv2d + bias + LeakyReLU of reference network.py:33-36 (and its backward-data / gradient-penalty tangent forms)
-// for the layers 8->8 and 16->8 — the shapes conv_thin_kernel (conv_igemm.hip) serves with one 8 x 32 pixel tile per workgroup.
+// for the layers 8->8 and 16->8 — the shapes conv_thin_kernel (conv_thin.hip) serves with one 8 x 32 pixel tile per workgroup.
 // Those layers sit at the HBM ridge (18-24 FLOP/B); a tile kernel loses there to (a) the halo re-read of a small tile (1.33x on
 // the input), (b) 1 KB row pieces scattered over ten DRAM pages per workgroup, (c) a load -> barrier -> compute -> store life
 // cycle whose overlap depends on other workgroups being in a different phase, and (d) ~700 scalar / vector instructions of
@@ -28,15 +28,7 @@
 // Fused epilogues (same set as the tile kernel): x scale, + bias, LeakyReLU | x LeakyReLU'(saved activation, fp32 or sign bytes),
 // sign bytes out, 2x2 average pool + fade-in blend, PixelNorm, adjoint of the previous (LeakyReLU -> PixelNorm); nearest x2
 // upsample fused into the row gather (the DMA source address).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <cstdio>
-#include <type_traits>
-#include "pggan_hip.h"
-#include "bufload.h"
 #include "convp.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef PG_STRIP_ABL            // ablation build of tools/sweeps/bench_strip.py: 1 no DMA after the prologue, 2 no stores, 4 one tap only
 #define PG_STRIP_ABL 0
@@ -47,6 +39,7 @@ namespace {
 using pgk::ConvP;
 using pgk::pg_sign_byte;
 using pgk::pg_sign_factors;
+using pgk::g_last_kernel; using pgk::set_smem; using pgk::SMEM_ANY;
 
 constexpr int SW = 64;            // output columns of a strip
 constexpr int RP = SW + 2;        // slots of one plane row (left / right halo column included)
@@ -616,47 +609,38 @@ __global__ __launch_bounds__(256, 2) void conv_strip_rgb_kernel(SArgs p)
     conv_strip_body<8, 8, EPI, false, 2>(p);
 }
 
-// Dynamic LDS above 48 KB needs the function attribute; it is a per-device property of the loaded code object, so it is set on
-// every launch that needs it (an idempotent host-side call: no per-process flag that a second GPU or a second thread could miss).
-inline int strip_set_smem(const void* fn, size_t smem)
-{
-    if (smem <= 48 * 1024) return 0;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    return e == hipSuccess ? 0 : (int)e;
-}
-
 template <int COUT, int CIN, int EPI, bool WREG, bool GATH = false>
-int launch_strip(const SArgs& a, int N, hipStream_t s, char* name, size_t name_len)
+int launch_strip(const SArgs& a, int N, hipStream_t s)
 {
     using B = Blk<CIN>;
     const size_t smem = (size_t)NBLK * B::SLOTS * 16 + (WREG ? 0 : (size_t)9 * COUT * (CIN == 16 ? CIN + 4 : CIN) * 4);
     auto kern = conv_strip_kernel<COUT, CIN, EPI, WREG, GATH>;
-    if (int rc = strip_set_smem(reinterpret_cast<const void*>(kern), smem); rc) return rc;
-    snprintf(name, name_len, "conv_strip_kernel<%d, %d, %d, %s, %s>", COUT, CIN, EPI, WREG ? "true" : "false", GATH ? "true" : "false");
+    if (int rc = set_smem(kern, smem, SMEM_ANY)) return rc;
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "conv_strip_kernel<%d, %d, %d, %s, %s>", COUT, CIN, EPI, WREG ? "true" : "false", GATH ? "true" : "false");
     hipLaunchKernelGGL(kern, dim3((unsigned)(N * a.strips * a.segs)), dim3(256), smem, s, a);
     return (int)hipGetLastError();
 }
 
 template <int EPI, bool WREG, int XM>
-int launch_strip_x(const SArgs& a, int N, hipStream_t s, char* name, size_t name_len)
+int launch_strip_x(const SArgs& a, int N, hipStream_t s)
 {
     const size_t smem = (size_t)NBLK * Blk<8>::SLOTS * 16 + (WREG ? 0 : (size_t)9 * 8 * 8 * 4);
     auto kern = conv_strip_x_kernel<EPI, WREG, XM>;
-    if (int rc = strip_set_smem(reinterpret_cast<const void*>(kern), smem); rc) return rc;
-    snprintf(name, name_len, "conv_strip_x_kernel<%d, %s, %d>", EPI, WREG ? "true" : "false", XM);
+    if (int rc = set_smem(kern, smem, SMEM_ANY)) return rc;
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "conv_strip_x_kernel<%d, %s, %d>", EPI, WREG ? "true" : "false", XM);
     hipLaunchKernelGGL(kern, dim3((unsigned)(N * a.strips * a.segs)), dim3(256), smem, s, a);
     return (int)hipGetLastError();
 }
 
 template <int COUT, int CIN, bool WREG>
-int launch_strip_epi(const SArgs& a, int epi, int N, hipStream_t s, char* name, size_t name_len)
+int launch_strip_epi(const SArgs& a, int epi, int N, hipStream_t s)
 {
     switch (epi) {
-        case EPI_FWD: return launch_strip<COUT, CIN, EPI_FWD, WREG>(a, N, s, name, name_len);
-        case EPI_MASK: return launch_strip<COUT, CIN, EPI_MASK, WREG>(a, N, s, name, name_len);
-        case EPI_PN: return launch_strip<COUT, CIN, EPI_PN, WREG>(a, N, s, name, name_len);
-        case EPI_PNB: return launch_strip<COUT, CIN, EPI_PNB, WREG>(a, N, s, name, name_len);
-        default: return launch_strip<COUT, CIN, EPI_GENERIC, WREG>(a, N, s, name, name_len);
+        case EPI_FWD: return launch_strip<COUT, CIN, EPI_FWD, WREG>(a, N, s);
+        case EPI_MASK: return launch_strip<COUT, CIN, EPI_MASK, WREG>(a, N, s);
+        case EPI_PN: return launch_strip<COUT, CIN, EPI_PN, WREG>(a, N, s);
+        case EPI_PNB: return launch_strip<COUT, CIN, EPI_PNB, WREG>(a, N, s);
+        default: return launch_strip<COUT, CIN, EPI_GENERIC, WREG>(a, N, s);
     }
 }
 
@@ -868,13 +852,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_strip_kernel(WArgs p)
 }
 
 template <int CO, int CI, bool GATH = false>
-int launch_wgrad_strip_t(const WArgs& a, int N, hipStream_t s, char* name, size_t name_len)
+int launch_wgrad_strip_t(const WArgs& a, int N, hipStream_t s)
 {
     constexpr int QO = CO / 4, QI = CI / 4;
     const size_t smem = ((size_t)QI * (3 * 320 + 2) + (size_t)QO * (2 * RB * SW + 2)) * 16;
     auto kern = wgrad_strip_kernel<CO, CI, GATH>;
-    if (int rc = strip_set_smem(reinterpret_cast<const void*>(kern), smem); rc) return rc;
-    snprintf(name, name_len, "wgrad_strip_kernel<%d, %d, %s>", CO, CI, GATH ? "true" : "false");
+    if (int rc = set_smem(kern, smem, SMEM_ANY)) return rc;
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "wgrad_strip_kernel<%d, %d, %s>", CO, CI, GATH ? "true" : "false");
     hipLaunchKernelGGL(kern, dim3((unsigned)(N * a.strips * a.segs)), dim3(256), smem, s, a);
     return (int)hipGetLastError();
 }
@@ -895,7 +879,7 @@ constexpr bool STRIP_WREG = true;
 
 }  // namespace
 
-int pgk::launch_conv_strip(ConvP& p, hipStream_t s, char* name, size_t name_len)
+int pgk::launch_conv_strip(ConvP& p, hipStream_t s)
 {
     if (p.KS != 3 || p.pad != 1 || p.yup || p.ksplit != 1) return PG_E_UNSUP;
     if ((p.Wout % SW) || (p.Hout % 16) || p.Hout != p.Hin || p.Wout != p.Win) return PG_E_UNSUP;
@@ -912,10 +896,10 @@ int pgk::launch_conv_strip(ConvP& p, hipStream_t s, char* name, size_t name_len)
     a.gbytes = p.gbytes; a.gmul = p.gmul; a.gslope = p.gslope;
     if (p.gbytes) {                              // pool adjoint in the gather (backward-data conv of a DBlock's c2): masked or plain
         if (!p.ups || p.bias || p.ypool || p.y_bytes || p.pnb_y || p.pn_r || p.ysigns) return PG_E_UNSUP;
-        if (p.Cin == 8) return p.mask ? launch_strip<8, 8, EPI_MASK, false, true>(a, p.N, s, name, name_len)
-                                      : launch_strip<8, 8, EPI_FWD, false, true>(a, p.N, s, name, name_len);
-        return p.mask ? launch_strip<8, 16, EPI_MASK, false, true>(a, p.N, s, name, name_len)
-                      : launch_strip<8, 16, EPI_FWD, false, true>(a, p.N, s, name, name_len);
+        if (p.Cin == 8) return p.mask ? launch_strip<8, 8, EPI_MASK, false, true>(a, p.N, s)
+                                      : launch_strip<8, 8, EPI_FWD, false, true>(a, p.N, s);
+        return p.mask ? launch_strip<8, 16, EPI_MASK, false, true>(a, p.N, s)
+                      : launch_strip<8, 16, EPI_FWD, false, true>(a, p.N, s);
     }
     int epi = EPI_GENERIC;
     if (!p.ypool && !p.y_bytes) {
@@ -924,14 +908,14 @@ int pgk::launch_conv_strip(ConvP& p, hipStream_t s, char* name, size_t name_len)
         else if (p.mask && !p.pnb_y && !p.pn_r) epi = EPI_MASK;
         else if (!p.mask && !p.pnb_y && !p.pn_r) epi = EPI_FWD;
     }
-    if (p.Cin == 8) return launch_strip_epi<8, 8, STRIP_WREG>(a, epi, p.N, s, name, name_len);
-    return launch_strip_epi<8, 16, false>(a, epi, p.N, s, name, name_len);
+    if (p.Cin == 8) return launch_strip_epi<8, 8, STRIP_WREG>(a, epi, p.N, s);
+    return launch_strip_epi<8, 16, false>(a, epi, p.N, s);
 }
 
 int pgk::launch_conv_strip_fromrgb(const float* img, const float* rgb_w, const float* rgb_b, float rgb_scale, float rgb_slope,
                                    unsigned char* x_signs, const float* w, const float* bias, float* y, unsigned char* y_signs,
                                    int N, int C, int H, int W, int Cmid, int Cout, float scale, float slope,
-                                   hipStream_t s, char* name, size_t name_len)
+                                   hipStream_t s)
 {
     if (C > RGB_MAXC || Cmid != 8 || Cout != 8 || (W % SW) || (H % 16)) return PG_E_UNSUP;
     if ((long long)H * W * 16 * 4 >= (1ll << 31)) return PG_E_UNSUP;            // 32-bit byte offsets inside an image
@@ -944,8 +928,8 @@ int pgk::launch_conv_strip_fromrgb(const float* img, const float* rgb_w, const f
     a.rgb_w = rgb_w; a.rgb_b = rgb_b; a.rgb_scale = rgb_scale; a.rgb_slope = rgb_slope; a.rgbC = C; a.xsigns = x_signs;
     const size_t smem = (size_t)NBLK * Blk<8>::SLOTS * 16 + (size_t)9 * 8 * 8 * 4;
     auto kern = conv_strip_rgb_kernel<EPI_FWD>;
-    if (int rc = strip_set_smem(reinterpret_cast<const void*>(kern), smem); rc) return rc;
-    snprintf(name, name_len, "conv_strip_rgb_kernel<%d>", (int)EPI_FWD);
+    if (int rc = set_smem(kern, smem, SMEM_ANY)) return rc;
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "conv_strip_rgb_kernel<%d>", (int)EPI_FWD);
     hipLaunchKernelGGL(kern, dim3((unsigned)(N * a.strips * a.segs)), dim3(256), smem, s, a);
     return (int)hipGetLastError();
 }
@@ -953,7 +937,7 @@ int pgk::launch_conv_strip_fromrgb(const float* img, const float* rgb_w, const f
 int pgk::launch_conv_strip_pn_torgb(const float* x, const float* w, const float* bias, float* y, float* r,
                                     const float* t_w, const float* t_b, float t_scale, float* img,
                                     int N, int C, int H, int W, int Cin, int Cout, float scale, float slope, float eps,
-                                    hipStream_t s, char* name, size_t name_len)
+                                    hipStream_t s)
 {
     if (C < 1 || C > RGB_MAXC || Cin != 8 || Cout != 8 || (W % SW) || (H % 16)) return PG_E_UNSUP;
     if ((long long)H * W * 16 * 4 >= (1ll << 31)) return PG_E_UNSUP;
@@ -964,14 +948,14 @@ int pgk::launch_conv_strip_pn_torgb(const float* x, const float* w, const float*
     a.scale = scale; a.slope = slope; a.mask_slope = 1.f; a.pool_a = 1.f;
     a.H = H; a.W = W; a.strips = W / SW; a.segs = H / seg; a.seg_rows = seg;
     a.t_out = img; a.t_w = t_w; a.t_b = t_b; a.t_scale = t_scale; a.tC = C; a.t_sc = Cout; a.t_sco = 1;
-    return launch_strip_x<EPI_PN, STRIP_WREG, 1>(a, N, s, name, name_len);
+    return launch_strip_x<EPI_PN, STRIP_WREG, 1>(a, N, s);
 }
 
 int pgk::launch_conv_strip_masked_rgb_bwd(const float* gz, const float* wt, const unsigned char* mask_bytes, float mask_slope, float* y,
                                           const float* rgb_w, float rgb_scale, float* gimg,
                                           const float* img, float* rgb_dw, float* rgb_db,
                                           int N, int C, int H, int W, int Cin, int Cout, float scale,
-                                          hipStream_t s, char* name, size_t name_len)
+                                          hipStream_t s)
 {
     if (C < 1 || C > RGB_MAXC || Cin != 8 || Cout != 8 || (W % SW) || (H % 16)) return PG_E_UNSUP;
     if ((long long)H * W * 16 * 4 >= (1ll << 31)) return PG_E_UNSUP;
@@ -985,11 +969,11 @@ int pgk::launch_conv_strip_masked_rgb_bwd(const float* gz, const float* wt, cons
     a.fw_img = img; a.fw_dw = rgb_dw; a.fw_db = rgb_db; a.fw_scale = rgb_scale;
     // weights in LDS, both forms: with the weight gradient's 16 accumulators the register-weights form would drop to two waves per SIMD,
     // and without them it sits at the 168-VGPR cap of three waves per SIMD and spills
-    if (rgb_dw) return launch_strip_x<EPI_MASK, false, 3>(a, N, s, name, name_len);
-    return launch_strip_x<EPI_MASK, false, 1>(a, N, s, name, name_len);
+    if (rgb_dw) return launch_strip_x<EPI_MASK, false, 3>(a, N, s);
+    return launch_strip_x<EPI_MASK, false, 1>(a, N, s);
 }
 
-int pgk::launch_wgrad_strip(WgP& p, hipStream_t s, char* name, size_t name_len)
+int pgk::launch_wgrad_strip(WgP& p, hipStream_t s)
 {
     if (p.pad != 1 || p.Hout != p.Hin || p.Wout != p.Win || (p.gbytes && p.ups)) return PG_E_UNSUP;
     if ((p.Wout % SW) || (p.Hout % 16)) return PG_E_UNSUP;
@@ -1007,11 +991,11 @@ int pgk::launch_wgrad_strip(WgP& p, hipStream_t s, char* name, size_t name_len)
     a.H = p.Hout; a.W = p.Wout; a.ups = p.ups; a.strips = p.Wout / SW; a.segs = p.Hout / seg; a.seg_rows = seg;
     a.gbytes = p.gbytes; a.gmul = p.gmul; a.gslope = p.gslope;
     if (p.gbytes) {
-        if (p.Cout == 8 && p.Cin == 8) return launch_wgrad_strip_t<8, 8, true>(a, p.N, s, name, name_len);
-        if (p.Cout == 16 && p.Cin == 8) return launch_wgrad_strip_t<16, 8, true>(a, p.N, s, name, name_len);
-        return launch_wgrad_strip_t<8, 16, true>(a, p.N, s, name, name_len);
+        if (p.Cout == 8 && p.Cin == 8) return launch_wgrad_strip_t<8, 8, true>(a, p.N, s);
+        if (p.Cout == 16 && p.Cin == 8) return launch_wgrad_strip_t<16, 8, true>(a, p.N, s);
+        return launch_wgrad_strip_t<8, 16, true>(a, p.N, s);
     }
-    if (p.Cout == 8 && p.Cin == 8) return launch_wgrad_strip_t<8, 8>(a, p.N, s, name, name_len);
-    if (p.Cout == 16 && p.Cin == 8) return launch_wgrad_strip_t<16, 8>(a, p.N, s, name, name_len);
-    return launch_wgrad_strip_t<8, 16>(a, p.N, s, name, name_len);
+    if (p.Cout == 8 && p.Cin == 8) return launch_wgrad_strip_t<8, 8>(a, p.N, s);
+    if (p.Cout == 16 && p.Cin == 8) return launch_wgrad_strip_t<16, 8>(a, p.N, s);
+    return launch_wgrad_strip_t<8, 16>(a, p.N, s);
 }

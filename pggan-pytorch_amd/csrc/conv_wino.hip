@@ -12,16 +12,8 @@
 // LDS, each lane loads ITS tile's 4x4 patch, transforms it in registers and feeds the MFMAs; the output transform is
 // lane-local because a lane holds all 16 products of its (tile, 4 couts).  (conv_wino2_kernel: the second generation.  The first,
 // conv_wino_kernel<VEC> with register-staged 16-channel chunks, lost on every layer and is gone: docs/experiments_*.md.)
-#include <hip/hip_runtime.h>
-#include <type_traits>
 #include <mutex>
 #include <vector>
-#include <stdint.h>
-#include <stdio.h>
-#include "pggan_hip.h"
-#include "bufload.h"
-#include "convp.h"
-
 #include "wino_epi.h"
 
 namespace {
@@ -678,10 +670,7 @@ int wino_conv(const float* x, const float* u, const float* bias, const float* ma
     else fn = xs == 3 ? PG_W2(3, false) : PG_W2(4, false);
 #undef PG_W2
     snprintf(g_wino_last, sizeof(g_wino_last), "conv_wino2_kernel<%d, 1, %d, %s, %d>", ncb, xs, ks > 1 ? "true" : "false", epi);   // (as the profiler demangles it)
-    if (smem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (int rc = pgk::set_smem(fn, smem, pgk::SMEM_ANY)) return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)(nblk * ks)), dim3(256), smem, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }

@@ -20,13 +20,6 @@
 //     agree with the tile kernel to the last bit (same sums in the same order).
 // Bounds per 64-tile step (8->16: 1024 MFMA cycles per wave against ~1200 VALU cycles of output transform + pooled / sign-byte
 // epilogue; 16->16 and wider: MFMA / HBM), see DESIGN.md.
-#include <hip/hip_runtime.h>
-#include <type_traits>
-#include <stdint.h>
-#include <stdio.h>
-#include "pggan_hip.h"
-#include "bufload.h"
-#include "convp.h"
 #include "wino_epi.h"
 
 namespace {
@@ -446,10 +439,7 @@ int launch_ws(const WinoP& p, WinoStripGeo g, hipStream_t s, char* name, size_t 
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return (int)e;
     if (dev < 0 || dev >= 16) return PG_E_UNSUP;
     if (!slots[dev]) {
-        if (smem > 48 * 1024) {
-            if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); e != hipSuccess)
-                return (int)e;
-        }
+        if (int rc = pgk::set_smem(kern, smem, pgk::SMEM_ANY)) return rc;
         int nb = 0, cus = 0;
         if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 256, smem); e != hipSuccess) return (int)e;
         if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return (int)e;

@@ -11,15 +11,7 @@
 // stages a region of 32 tiles (16x8 pixels: gz rows + x halo rows) in LDS, every lane transforms ITS (tile, channel)
 // values in registers: Z from the 2x2 gz values (A operand: row = cout, k = tile), V from the 4x4 x patch (B operand:
 // col = cin, k = tile).  M stays in 16 accumulators; G^T M G is lane-local at the end and commits 9 taps with atomics.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include "pggan_hip.h"
-#include "bufload.h"
 #include "convp.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 #ifndef PG_WW_SCHED
 #define PG_WW_SCHED 2            // 3: both cout halves' transforms first, then one stream of 32 MFMAs (A/B builds)

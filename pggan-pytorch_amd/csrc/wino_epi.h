@@ -2,14 +2,9 @@
 // Winograd F(2x2,3x3) convs, the lane-local output transform and the fused epilogues on the 2x2 outputs of a tile.  A lane
 // (li = lane & 15, kk = lane >> 4) of either kernel holds the 16 Winograd-domain products of tile li for couts 4 kk .. 4 kk + 3.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "pggan_hip.h"
-#include "bufload.h"
+#include "convp.h"          // f32x4, MFMA16, set_smem, the per-stream Workspace; the runtime, ABI and bufload.h headers
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 namespace pgw {
 

@@ -1170,10 +1170,10 @@ def test_sound_entry_points(rz, mode, n_fft, hop, stereo):
 
 
 # ------------------------------------------------------------------------------------------------------- coverage
-# From a reading of the dispatchers: every __global__ conv kernel of csrc/conv_igemm.hip (dispatch_conv / launch_conv, launch_ksplit,
-# dispatch_thin, launch_k4_conv, launch_k4_wgrad, the weight-gradient launchers), conv_strip.hip (launch_conv_strip, launch_wgrad_strip
-# and the two RGB-fused launchers), conv_wino.hip, conv_wino_strip.hip and conv_wino_wgrad.hip whose symbol the pg_debug_last_* calls
-# report.  (conv_epilogue_kernel is the deferred epilogue of a split-K conv_igemm_kernel launch and has no symbol of its own there;
+# From a reading of the dispatchers: every __global__ conv kernel of csrc/conv_igemm.hip (dispatch_conv / launch_conv, launch_ksplit),
+# conv_thin.hip (dispatch_thin), conv_k4.hip (launch_k4_conv, launch_k4_wgrad), conv_wgrad.hip (the weight-gradient launchers),
+# conv_strip.hip (launch_conv_strip, launch_wgrad_strip and the two RGB-fused launchers), conv_wino.hip, conv_wino_strip.hip and
+# conv_wino_wgrad.hip whose symbol the pg_debug_last_* calls report.  (conv_epilogue_kernel is the deferred epilogue of a split-K conv_igemm_kernel launch and has no symbol of its own there;
 # the weight-transform and pack kernels are covered by test_weight_transforms_batched_in_flat_buffers.)
 CONV_FAMILIES = {
     'conv_igemm_kernel', 'conv_ksplit_kernel', 'conv_thin_kernel', 'conv_k4_expand_kernel', 'conv_k4_reduce_kernel',
