@@ -7,6 +7,7 @@ the C-ABI of ``libpggan_hip.so`` (``include/pggan_hip.h``).  Import as
 from . import _lib, runtime, ops, engine, network, wgan_gp_loss, trainer, plugins, optim, parallel, utils, graphs, plans, sound, metrics, ema, dataset, telemetry, cluster  # noqa: F401
 from .network import Generator, Discriminator, PGConv2d  # noqa: F401
 from .wgan_gp_loss import wgan_gp_D_loss, wgan_gp_G_loss  # noqa: F401
+from .gan_losses import gan_losses  # noqa: F401  (the function takes the module's place as the package attribute)
 from .trainer import Trainer  # noqa: F401
 from .plugins import (Plugin, DepthManager, LRScheduler, RampupLR, TimeMonitor, AbsoluteTimeMonitor, SaverPlugin, OutputGenerator,  # noqa: F401
                       SWDMonitor, MSSSIMMonitor, NNMonitor, NDBMonitor, LossMonitor, HealthMonitor, load_models, load_smoothed_generator, load_trainer_state)
@@ -19,7 +20,7 @@ from .metrics import NearestNeighbours, NDB  # noqa: F401
 from .telemetry import ScalarStats, SegmentStats, TrainingDiverged  # noqa: F401
 from ._lib import PgganLibraryError, LIB_PATH  # noqa: F401
 
-__all__ = ['Generator', 'Discriminator', 'PGConv2d', 'wgan_gp_D_loss', 'wgan_gp_G_loss', 'Trainer', 'Plugin',
+__all__ = ['Generator', 'Discriminator', 'PGConv2d', 'wgan_gp_D_loss', 'wgan_gp_G_loss', 'gan_losses', 'Trainer', 'Plugin',
            'DepthManager', 'LRScheduler', 'RampupLR', 'TimeMonitor', 'AbsoluteTimeMonitor', 'SaverPlugin', 'OutputGenerator', 'SWDMonitor', 'MSSSIMMonitor', 'NNMonitor', 'load_models',
            'load_smoothed_generator', 'load_trainer_state', 'FusedAdam', 'GeneratorEMA', 'DataParallel', 'SoundSaver', 'DeviceSoundSaver',
            'spectrogram_u8', 'DeviceImageDataset', 'NearestNeighbours', 'NDB', 'NDBMonitor', 'LossMonitor', 'HealthMonitor', 'ScalarStats', 'SegmentStats',

@@ -1227,9 +1227,24 @@ def _assign_grads(net, layers, linear=False):
 REAL_THIRD_IN_STEP = True      # False: reference half of tests/test_e2e_gpu.py::test_three_pass_d_forward_matches_whole_batch_forward
 
 
-def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_target):
+class Objective(_collections.namedtuple('Objective', 'kind drift penalty weight target')):
+    """What the loss block of a step computes: ``kind`` a key of ``ops.GAN_KINDS``, ``drift`` the weight of the
+    s_r^2 term, ``penalty`` 'gp' | 'r1' | None with its ``weight`` (lambda / gamma) and, for 'gp', the ``target`` norm.  Immutable and
+    hashable: it is part of the key of a launch plan.  ``objective=None`` everywhere below is WGAN-GP on the original kernels."""
+    __slots__ = ()
+
+
+def _penalty_seed(obj, gimg, ss, N):
+    if obj.penalty == 'r1':
+        return ops.r1_seed(gimg, ss, obj.weight, 1.0 / N)
+    return ops.gp_seed(gimg, ss, obj.weight, obj.target, 1.0 / N)
+
+
+def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_target, objective=None):
     """Forward half of wgan_gp_D_loss (wgan_gp_loss.py:36-65): three D passes batched as
-    [real | fake | mixed], G without graph, and the first backward of the gradient penalty."""
+    [real | fake | mixed], G without graph, and the first backward of the gradient penalty.
+    With an ``Objective`` (penalty 'gp' or 'r1') the same schedule with that objective's loss block and penalty seed; its fields stand in
+    for the three iwass arguments, which are not read.  R1 is the penalty at ``mix`` == 0, i.e. at the real images."""
     ops.require_gpu()
     real = _check_dev(real, 'real images')
     latents = _check_dev(latents, 'latents')
@@ -1288,11 +1303,17 @@ def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_
     sub = ctx.slice(2 * N, 3 * N, 2, 3)
     gimg, adj = d_backward(D, sub, _ones(N, real.device), full=False, want_gimg=True, save_adjoints=True)  # :25-28
     ss = ops.row_sumsq(gimg)
-    gp, u = ops.gp_seed(gimg, ss, iwass_lambda, iwass_target, 1.0 / N)        # :29-31
+    if objective is None:
+        gp, u = ops.gp_seed(gimg, ss, iwass_lambda, iwass_target, 1.0 / N)    # :29-31
+    else:
+        gp, u = _penalty_seed(objective, gimg, ss, N)
     probe('D.gp_bwd_end')
     if fake_done is not None:
         _wait_event(torch.cuda.current_stream(torch._C._cuda_getDevice()), fake_done)
-    d_cost, d_real_loss, d_fake_loss, gscore = ops.d_loss(s, gp, N, iwass_epsilon)   # :48,55,62
+    if objective is None:
+        d_cost, d_real_loss, d_fake_loss, gscore = ops.d_loss(s, gp, N, iwass_epsilon)   # :48,55,62
+    else:
+        d_cost, d_real_loss, d_fake_loss, gscore = ops.gan_d_loss(s, gp, N, objective.kind, objective.drift)
     probe('D.loss_end')
     state = saved.DLossState(D=D, ctx=ctx, sub=sub, adj=adj, u=u, gscore=gscore, N=N, scores=s, gp=gp)
     if arena_st is not None:
@@ -1457,8 +1478,43 @@ def d_loss_backward(state, scale=1.0):
     _assign_grads(D, d_active_params(D, ctx.depth, ctx.alpha), linear=True)
 
 
-def g_loss_forward(G, D, latents):
-    """wgan_gp_G_loss (wgan_gp_loss.py:68-74)."""
+def d_plain_loss_forward(D, G, real, latents, objective):
+    """The D step of an objective without a penalty: ONE whole-batch pass over [real | fake], then the loss block.  No mixed third, no
+    first backward, no tangent pass."""
+    ops.require_gpu()
+    real = _check_dev(real, 'real images')
+    latents = _check_dev(latents, 'latents')
+    N = real.shape[0]
+    D._sync_version()
+    x2 = torch.empty((2 * N,) + tuple(real.shape[1:]), device=real.device, dtype=torch.float32)
+    ops.axpby_mask(real, a=1.0, out=x2[:N])
+    d_step_generator(D, G, latents, x2[N:])
+    s, ctx = d_forward(D, x2, groups=2)
+    d_cost, d_real_loss, d_fake_loss, gscore = ops.gan_d_loss(s, None, N, objective.kind, objective.drift)
+    return d_cost, d_real_loss, d_fake_loss, saved.DLossState(D=D, ctx=ctx, gscore=gscore, N=N, scores=s)
+
+
+def d_plain_loss_backward(state, scale=1.0):
+    """``d_cost.backward()`` of ``d_plain_loss_forward``: the adjoint sweep over [real | fake] alone, then ``d_loss_backward``'s tail."""
+    D, ctx = state.D, state.ctx
+    D._ensure_buffers()
+    ops.zero_(D._flat_grad)
+    if scale != 1.0:
+        D._rt.grad_hook = None
+    for lay in _live_conv_layers(D):
+        lay._pending_wgrad = None
+    d_backward(D, ctx, state.gscore, full=True, want_gimg=False)
+    for lay in _live_conv_layers(D):
+        _flush_wgrad(lay)
+    if not (D._rt.skip_join and scale == 1.0):
+        _join_side()
+    if scale != 1.0:
+        ops.axpby_mask(D._flat_grad, a=scale, out=D._flat_grad)
+    _assign_grads(D, d_active_params(D, ctx.depth, ctx.alpha), linear=True)
+
+
+def g_loss_forward(G, D, latents, objective=None):
+    """wgan_gp_G_loss (wgan_gp_loss.py:68-74); with an ``Objective`` its generator term in place of -s."""
     ops.require_gpu()
     latents = _check_dev(latents, 'latents')
     D._sync_version()
@@ -1471,7 +1527,7 @@ def g_loss_forward(G, D, latents):
         fake, gctx = generator_forward(G, latents, save=True)
     probe('G.g_fwd_end')
     s, dctx = d_forward(D, fake, 1, keep_input=False)
-    g_cost, gscore = ops.g_loss(s)
+    g_cost, gscore = ops.g_loss(s) if objective is None else ops.gan_g_loss(s, objective.kind)
     probe('G.d_fwd_end')
     return g_cost, saved.GLossState(G=G, D=D, gctx=gctx, dctx=dctx, gscore=gscore)
 

@@ -694,6 +694,42 @@ def g_loss(scores):
     return g_cost, gscore
 
 
+# ------------------------------------------------------------------- selectable objectives (include/pggan_hip_gan.h)
+# every #define PG_GAN_<KIND> of include/pggan_hip_gan.h, in the header's order: 'wgan', 'logistic', 'hinge', 'lsgan' -> the kernels' number
+GAN_KINDS = {name[len('PG_GAN_'):].lower(): value for name, value in _lib.GAN_CONSTANTS.items() if name.startswith('PG_GAN_')}
+
+
+def gan_d_loss(scores, pen, N, kind, drift):
+    """``d_loss`` for any objective: ``scores`` [2N] or [3N] = [real | fake | (mixed)], ``pen`` [N] or None, ``kind`` a key of
+    ``GAN_KINDS`` -> (d_cost, R [N,1], F [N,1], gscore of the length of ``scores``); the first three are views of one buffer."""
+    dev = scores.device
+    groups = scores.numel() // N
+    out = torch.empty((1 + 2 * N,), device=dev, dtype=torch.float32)     # one buffer, as ``d_loss`` hands them out
+    d_cost, d_real_loss, d_fake_loss = out[0], out[1:1 + N].view(N, 1), out[1 + N:].view(N, 1)
+    gscore = torch.empty((groups * N,), device=dev, dtype=torch.float32)
+    _lib.call('pg_gan_d_loss', _p(scores), _p(pen), _p(d_cost), _p(d_real_loss), _p(d_fake_loss), _p(gscore), N, groups,
+              GAN_KINDS[kind], drift, _stream())
+    return d_cost, d_real_loss, d_fake_loss, gscore
+
+
+def gan_g_loss(scores, kind):
+    N = scores.shape[0]
+    g_cost = torch.empty((), device=scores.device, dtype=torch.float32)
+    gscore = torch.empty((N,), device=scores.device, dtype=torch.float32)
+    _lib.call('pg_gan_g_loss', _p(scores), _p(g_cost), _p(gscore), N, GAN_KINDS[kind], _stream())
+    return g_cost, gscore
+
+
+def r1_seed(g, ss, gamma, inv_n):
+    """The R1 penalty per sample ``(gamma / 2) ss`` and its tangent seed ``(inv_n gamma) g`` (``gp_seed``'s place in the D step)."""
+    N = g.shape[0]
+    E = g.numel() // N
+    pen = torch.empty((N,), device=g.device, dtype=torch.float32)
+    u = torch.empty_like(g)
+    _lib.call('pg_r1_seed', _p(g), _p(ss), _p(pen), _p(u), N, E, gamma, inv_n, _stream())
+    return pen, u
+
+
 # --------------------------------------------------------------------------------------- misc
 def adam(p, g, m, v, lr, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale=1.0):
     _lib.call('pg_adam', _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, _stream())

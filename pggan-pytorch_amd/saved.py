@@ -154,7 +154,8 @@ class Hvp(_Record):
 
 
 class DLossState(_Record):
-    """Writer: engine.d_loss_forward; reader: d_loss_backward (and diagnostics: tools/, tests/test_fp64_adjudicator.py)."""
+    """Writer: engine.d_loss_forward; reader: d_loss_backward (and diagnostics: tools/, tests/test_fp64_adjudicator.py).
+    engine.d_plain_loss_forward (an objective without a penalty) writes D, N, ctx over [real | fake], gscore and scores only."""
     LAYOUT = {
         'D': None,          # the discriminator
         'N': None,          # minibatch size
