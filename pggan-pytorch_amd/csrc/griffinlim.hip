@@ -10,7 +10,8 @@
 // the whole iteration to 1e-9.  No atomics: every output element has one writer and a fixed summation order, so results are
 // bit-identical from run to run.
 //
-// The transform (gl_pieces_kernel): one workgroup per (frame, sample), the frame as split re[] / im[] arrays of doubles in LDS, a
+// The transform (gl_pieces_kernel; its radix-2 stages, twiddle table and window are csrc/fft_r2.h, shared with csrc/phase.hip): one
+// workgroup per (frame, sample), the frame as split re[] / im[] arrays of doubles in LDS, a
 // complex radix-2 FFT of n_fft points in place.  Forward: decimation in frequency, natural order in -> bit-reversed order out.  The
 // phase projection works on the bit-reversed image (bin k lives at brev(k)) and stores the CONJUGATE of the Hermitian-extended
 // spectrum; the inverse is then the same forward-twiddle butterfly network as decimation in time, bit-reversed in -> natural order
@@ -28,42 +29,15 @@
 
 #pragma clang fp contract(off)
 
+#include "fft_r2.h"
+
 namespace {
 
-constexpr int GL_MIN_N = 8;
-constexpr int GL_MAX_N = 2048;                                             // STFT_MAX_N of sound.hip: image heights 4 .. 1024
-constexpr int GL_THREADS = 256;
+using namespace fft_r2;                                                    // fft_stage, hann, the twiddle table: shared with phase.hip
 
-__device__ __forceinline__ double hann(const double* twc, int n, int half)
-{
-    const double cs = n < half ? twc[n] : -twc[n - half];                  // cos(2 pi n / N)
-    return 0.5 - 0.5 * cs;                                                 // periodic Hann: scipy.signal.hann(n_fft, sym=False)
-}
-
-// one radix-2 stage over the n_fft/2 butterflies of half-span m = 1 << s; w = e^{-2 pi i pos / (2 m)}.
-// DIF: (a, b) -> (a + b, (a - b) w); DIT: (a, b) -> (a + w b, a - w b)
-template <bool DIF>
-__device__ __forceinline__ void fft_stage(double* re, double* im, const double* twc, const double* tws, int s, int logn, int half)
-{
-    const int m = 1 << s;
-    for (int j = threadIdx.x; j < half; j += GL_THREADS) {
-        const int pos = j & (m - 1);
-        const int i0 = ((j >> s) << (s + 1)) | pos, i1 = i0 + m;
-        const int q = pos << (logn - 1 - s);                               // pos * N / (2 m) < N / 2
-        const double wr = twc[q], wi = -tws[q];
-        const double ar = re[i0], ai = im[i0], br = re[i1], bi = im[i1];
-        if (DIF) {
-            const double dr = ar - br, di = ai - bi;
-            re[i0] = ar + br; im[i0] = ai + bi;
-            re[i1] = dr * wr - di * wi; im[i1] = dr * wi + di * wr;
-        } else {
-            const double tr = br * wr - bi * wi, ti = br * wi + bi * wr;
-            re[i0] = ar + tr; im[i0] = ai + ti;
-            re[i1] = ar - tr; im[i1] = ai - ti;
-        }
-    }
-    __syncthreads();
-}
+constexpr int GL_MIN_N = FFT_MIN_N;
+constexpr int GL_MAX_N = FFT_MAX_N;                                        // STFT_MAX_N of sound.hip: image heights 4 .. 1024
+constexpr int GL_THREADS = FFT_THREADS;
 
 // x [batch][nsamp] (NULL: the spectrum is spec itself, taken as real), spec [batch][frames][n_fft/2 + 1], pieces [batch][frames][n_fft]
 template <int MAXN>
@@ -74,12 +48,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_pieces_kernel(const double* __r
     __shared__ double twc[MAXN / 2], tws[MAXN / 2];
     const int t = blockIdx.x, b = blockIdx.y;
     const int half = n_fft >> 1;
-    for (int q = threadIdx.x; q < half; q += GL_THREADS) {
-        double sn, cs;
-        sincospi(2.0 * (double)q / (double)n_fft, &sn, &cs);
-        twc[q] = cs; tws[q] = sn;
-    }
-    __syncthreads();
+    fill_twiddles(twc, tws, n_fft, half);
     if (x) {
         const double* xb = x + (size_t)b * nsamp;
         for (int n = threadIdx.x; n < n_fft; n += GL_THREADS) {
@@ -187,8 +156,6 @@ __global__ __launch_bounds__(256) void spectrum_kernel(const float* __restrict__
         spec[i] = v;
     }
 }
-
-bool bad_n(int n_fft) { return n_fft < GL_MIN_N || n_fft > GL_MAX_N || (n_fft & (n_fft - 1)); }
 
 unsigned blocks_for(int64_t n)
 {

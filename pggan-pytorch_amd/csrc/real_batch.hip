@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pggan_hip.h"
+#include "pggan_hip_phase.h"
 
 // numpy never fuses a multiply with the following add (see io_steps.hip): for the whole translation unit
 #pragma clang fp contract(off)
@@ -119,13 +120,10 @@ inline int grid_for(long long total, int block = 256, int cap = 4096)
     return (int)g;
 }
 
-}  // namespace
-
-extern "C" int pg_real_batch_u8(const uint8_t* src, int64_t M, int C, int S, int depthdiff, const int64_t* idx, const uint8_t* flip,
-                                int n, float* out, double alpha, double min_in, double max_in, double min_out, double max_out,
-                                pg_stream_t stream)
+// src [M][C][S][S]; the kernels take any C (a plane is a plane), the entry points state which they accept
+int launch_real_batch(const uint8_t* src, int C, int S, int depthdiff, const int64_t* idx, const uint8_t* flip, int n, float* out,
+                      double alpha, double min_in, double max_in, double min_out, double max_out, pg_stream_t stream)
 {
-    if (!src || !idx || !out || M <= 0 || n <= 0 || S <= 0 || depthdiff < 0 || depthdiff > 30 || (C != 1 && C != 3)) return PG_E_ARG;
     if (S & (S - 1)) return PG_E_ALIGN;
     const int r = S >> depthdiff;
     if (r < 2) return PG_E_ALIGN;
@@ -149,4 +147,23 @@ extern "C" int pg_real_batch_u8(const uint8_t* src, int64_t M, int C, int S, int
                            src, idx, flip, out, total, C, S, depthdiff, lr, (float)min_in, (float)max_in, p);
     }
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int pg_real_batch_u8(const uint8_t* src, int64_t M, int C, int S, int depthdiff, const int64_t* idx, const uint8_t* flip,
+                                int n, float* out, double alpha, double min_in, double max_in, double min_out, double max_out,
+                                pg_stream_t stream)
+{
+    if (!src || !idx || !out || M <= 0 || n <= 0 || S <= 0 || depthdiff < 0 || depthdiff > 30 || (C != 1 && C != 3)) return PG_E_ARG;
+    return launch_real_batch(src, C, S, depthdiff, idx, flip, n, out, alpha, min_in, max_in, min_out, max_out, stream);
+}
+
+// the (log-magnitude, instantaneous frequency) stacks of include/pggan_hip_phase.h
+extern "C" int pg_real_batch_2ch_u8(const uint8_t* src, int64_t M, int S, int depthdiff, const int64_t* idx, const uint8_t* flip, int n,
+                                    float* out, double alpha, double min_in, double max_in, double min_out, double max_out,
+                                    pg_stream_t stream)
+{
+    if (!src || !idx || !out || M <= 0 || n <= 0 || S <= 0 || depthdiff < 0 || depthdiff > 30) return PG_E_ARG;
+    return launch_real_batch(src, 2, S, depthdiff, idx, flip, n, out, alpha, min_in, max_in, min_out, max_out, stream);
 }

@@ -114,7 +114,9 @@ def _log2(v):
 
 class DeviceImageDataset(object):
     """``images``: uint8 numpy array or torch tensor [M,C,R,R], C in {1, 3}, R a power of two >= 4 (ValueError otherwise); at most
-    ``max_images`` of them are used.  The stack is uploaded once (in chunks) and stays on ``device``.
+    ``max_images`` of them are used.  The stack is uploaded once (in chunks) and stays on ``device``.  ``two_channel=True`` announces
+    C = 2, the 'magif' images of ``sound.spectrogram_stack_u8`` (log-magnitude and instantaneous frequency); unannounced, a
+    two-channel stack stays the error it has always been (a sliced RGB stack).
 
     The stage is dataset depth ``model_depth + model_dataset_depth_offset`` (side 2^depth, so the default offset 2 starts at 4x4).
     ``pyramid`` picks which of the reference's two behaviours supplies a stage below the source resolution:
@@ -142,7 +144,7 @@ class DeviceImageDataset(object):
     ``device='cpu'``: host mode, the same definition in numpy (fp64)."""
 
     def __init__(self, images, model_dataset_depth_offset=2, model_initial_depth=0, alpha=1.0, range_in=(0, 255), range_out=(-1, 1),
-                 pyramid='chain', mirror_augment=False, shuffle=True, seed=0, max_images=None, rank=0, world=1, device='cuda'):
+                 pyramid='chain', mirror_augment=False, shuffle=True, seed=0, max_images=None, rank=0, world=1, device='cuda', two_channel=False):
         if torch.is_tensor(images):
             ok = images.dtype == torch.uint8
         else:
@@ -152,8 +154,8 @@ class DeviceImageDataset(object):
         if images.ndim != 4 or images.shape[0] < 1:
             raise ValueError('images: expected [M,C,R,R] with M >= 1, got shape %s' % (tuple(images.shape),))
         M, C, R, R2 = (int(v) for v in images.shape)
-        if C not in (1, 3):
-            raise ValueError('images: %d channels (1 or 3 are supported)' % C)
+        if C not in ((1, 2, 3) if two_channel else (1, 3)):
+            raise ValueError('images: %d channels (1 or 3 are supported, 2 with two_channel=True)' % C)
         if R != R2 or R < 4 or R & (R - 1):
             raise ValueError('images: %dx%d (the side must be a power of two >= 4)' % (R, R2))
         if max_images is not None:

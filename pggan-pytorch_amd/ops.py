@@ -828,7 +828,8 @@ def pyramid_level_u8(batch_u8, depthdiff, range_in=(0, 255)):
 def real_batch_u8(stack_u8, idx, flip=None, depthdiff=0, alpha=1.0, range_in=(0, 255), range_out=(-1, 1), check=False):
     """uint8 device stack [M,C,S,S] -> fp32 batch [n,C,r,r], r = S >> depthdiff, in one launch (pg_real_batch_u8, csrc/real_batch.hip):
     image ``idx[j]`` (int64 device tensor [n]), its pyramid level (``pyramid_level_u8``), mirrored where ``flip[j] != 0`` (uint8 device
-    tensor [n] or None), faded and range-adjusted (``real_prepare_u8``).  The device does not check ``idx``: ``check=True`` reads its
+    tensor [n] or None), faded and range-adjusted (``real_prepare_u8``).  C = 2 (the 'magif' stacks) goes through pg_real_batch_2ch_u8 of
+    include/pggan_hip_phase.h: the same kernels.  The device does not check ``idx``: ``check=True`` reads its
     minimum and maximum back (a host synchronisation) and raises IndexError for a value outside [0, M)."""
     require_gpu()
     if not torch.is_tensor(stack_u8) or not stack_u8.is_cuda or stack_u8.dtype != torch.uint8 or not stack_u8.is_contiguous() or stack_u8.dim() != 4:
@@ -847,6 +848,9 @@ def real_batch_u8(stack_u8, idx, flip=None, depthdiff=0, alpha=1.0, range_in=(0,
         if lo < 0 or hi >= M:
             raise IndexError('idx holds values in [%d, %d] for a stack of %d images' % (lo, hi, M))
     depthdiff = int(depthdiff)
+    if C == 2:                                                   # pg_real_batch_u8 takes C in {1, 3}; two channels are an addition
+        from . import phase
+        return phase.real_batch_2ch_u8(stack_u8, idx, flip, depthdiff, alpha, range_in, range_out)
     r = S >> depthdiff if 0 <= depthdiff < 31 else 0
     out = torch.empty((n, C, r, r), device=stack_u8.device, dtype=torch.float32)
     _lib.call('pg_real_batch_u8', stack_u8.data_ptr(), M, C, S, depthdiff, idx.data_ptr(), None if flip is None else flip.data_ptr(), n,

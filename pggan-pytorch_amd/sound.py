@@ -7,6 +7,9 @@ post-processor with the reference's hook signature.
     ``[n, 1, H, W]`` samples of G; 'abslog' images go through Griffin-Lim (``griffin_lim_iter`` rounds of STFT / inverse
     STFT), 'raw' images are the waveform itself; one 32-bit float WAV per sample, names as in the reference.  It runs on the
     host with numpy, as the reference does and as SURVEY.md §8f allows (6 samples every 3 ticks).
+  * ``img_mode='magif'`` / ``mode='magif'`` — log-magnitude plus instantaneous frequency as a two-channel image (after Engel et al.
+    2019, GANSynth): ``spectrogram_u8`` / ``spectrogram_stack_u8`` make the images (csrc/phase.hip), both savers
+    turn them back into a waveform with one inverse STFT; the ``magif_*`` functions below are the definitions in numpy fp64.
   * ``DeviceSoundSaver`` — the same files from the device: the spectrum, every Griffin-Lim round and the normalisation are the fp64
     HIP kernels of csrc/griffinlim.hip; only the float32 waveforms are copied back.  Opt-in: ``SoundSaver`` stays the default.
 
@@ -22,20 +25,88 @@ import numpy as np
 from .utils import adjust_dynamic_range
 
 
-def spectrogram_u8(signal, n_fft=1024, hop_length=128, img_mode='abslog', range_in=(0, 255)):
+def spectrogram_u8(signal, n_fft=1024, hop_length=128, img_mode='abslog', range_in=(0, 255), mag_range=None):
     """Waveform (numpy array or tensor, ``[nsamp]`` or ``[nsamp, channels]``) -> uint8 device image: ``[1, n_fft/2, n_fft/2]``
     for the spectrogram modes 'abslog' (log(1 + |s|), dataset.py:296) and 'reallog' (log(1 + |Re s|) * sign(s), dataset.py:298,
     with numpy 1.13's complex sign = the sign of the real part), ``[1, 2^k, 2^k]`` for 'raw' (the waveform itself, dataset.py:289-291).
-    Defaults as SoundImageDataset.__init__ (dataset.py:259-274)."""
+    Defaults as SoundImageDataset.__init__ (dataset.py:259-274).
+
+    'magif' (this project's own): ``[2, n_fft/2, n_fft/2]``, log-magnitude stretched from the FIXED ``mag_range``
+    (default (0, log1p(n_fft/2))) and the instantaneous frequency on a circle of 256 levels; ``range_in`` is not used."""
     import torch
     from . import ops
-    if img_mode not in ('abslog', 'reallog', 'raw'):
-        raise ValueError("img_mode must be one of 'abslog', 'reallog', 'raw' (got %r)" % (img_mode,))
+    if img_mode not in ('abslog', 'reallog', 'raw', 'magif'):
+        raise ValueError("img_mode must be one of 'abslog', 'reallog', 'raw', 'magif' (got %r)" % (img_mode,))
+    if img_mode != 'magif' and mag_range is not None:
+        raise ValueError("mag_range belongs to img_mode='magif' (got img_mode %r)" % (img_mode,))
     if range_in[0] != 0:
         raise NotImplementedError('range_in must start at 0 (uint8 images)')
     t = signal if torch.is_tensor(signal) else torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32))
+    if img_mode == 'magif':
+        if t.dim() not in (1, 2) or t.shape[0] < 1:
+            raise ValueError('expected a waveform [nsamp] or [nsamp, channels], got shape %s' % (tuple(t.shape),))
+        t = t.to(dtype=torch.float32)
+        if t.dim() == 2:
+            t = t.sum(dim=1) / 2                                              # dataset.py:287-288: s.sum(axis=1) / 2 in float32
+        return spectrogram_stack_u8(t[None], n_fft, hop_length, mag_range)[0]
     t = t.to(device='cuda', dtype=torch.float32).contiguous()
     return ops.spectrogram_u8(t, int(n_fft), int(hop_length), float(range_in[1]), img_mode=img_mode)
+
+
+def spectrogram_stack_u8(signals, n_fft=1024, hop_length=128, mag_range=None):
+    """Mono waveforms ``[batch, nsamp]`` (numpy array or tensor) -> uint8 device images ``[batch, 2, n_fft/2, n_fft/2]`` of
+    ``img_mode='magif'``, for filling a ``DeviceImageDataset`` stack: the analysis of the whole batch and the quantiser, no host
+    synchronisation (phase.spectrogram_stack_u8)."""
+    import torch
+    from . import phase
+    t = signals if torch.is_tensor(signals) else torch.from_numpy(np.ascontiguousarray(signals, dtype=np.float32))
+    if t.dim() != 2 or t.shape[0] < 1:
+        raise ValueError('signals: expected [batch, nsamp], got shape %s' % (tuple(t.shape),))
+    if isinstance(n_fft, bool) or int(n_fft) != n_fft or isinstance(hop_length, bool) or int(hop_length) != hop_length:
+        raise ValueError('n_fft and hop_length must be integers, got %r and %r' % (n_fft, hop_length))
+    return phase.spectrogram_stack_u8(t.to(device='cuda', dtype=torch.float32).contiguous(), int(n_fft), int(hop_length), mag_range)
+
+
+# ---------------------------------------------------------------------- 'magif' in numpy fp64: the host twin of csrc/phase.hip
+def _mag_range(mag_range, n_fft):
+    if mag_range is None:
+        return (0.0, float(np.log1p(n_fft // 2)))
+    try:
+        lo, hi = (float(v) for v in mag_range)
+    except (TypeError, ValueError):
+        raise ValueError('mag_range must be None or (lo, hi), got %r' % (mag_range,))
+    if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo):
+        raise ValueError('mag_range must be finite with hi > lo, got %r' % (mag_range,))
+    return (lo, hi)
+
+
+def magif_analyse(y, n_fft, hop_length):
+    """Mono waveform -> ``(logmag, ifreq)`` float64 ``[n_fft/2 + 1, frames]``: log1p(|S|) and the wrapped difference of the phase of
+    neighbouring frames in units of pi, in [-1, 1); the first column is the phase itself (phi[-1] = 0, phi = 0 where S == 0)."""
+    S = stft(np.asarray(y, dtype=np.float32), n_fft, hop_length)
+    phi = np.where(np.abs(S) == 0, 0.0, np.arctan2(S.imag, S.real) / np.pi)   # (arctan2(-0.0, -0.0) is -pi)
+    d = np.diff(phi, axis=1, prepend=0.0)
+    return np.log1p(np.abs(S)), d - 2.0 * np.floor(d / 2.0 + 0.5)
+
+
+def magif_image(logmag, ifreq, mag_range):
+    """Both planes -> uint8 ``[2, ...]``: clip(rint((logmag - lo) / (hi - lo) * 255), 0, 255) and rint((ifreq + 1) * 128) mod 256."""
+    lo, hi = mag_range
+    m = np.clip(np.rint((np.asarray(logmag, dtype=np.float64) - lo) / (hi - lo) * 255.0), 0, 255)
+    f = np.mod(np.rint((np.asarray(ifreq, dtype=np.float64) + 1.0) * 128.0), 256.0)
+    return np.stack([m, f]).astype(np.uint8)
+
+
+def magif_spectrum(image, drange, mag_range):
+    """fp32 image ``[2, H, W]`` -> complex spectrum ``[H + 1, W]``: magnitude expm1(max(v, 0)) from channel 0, the running sum of the
+    instantaneous frequency of channel 1 as the phase in units of pi; the bin H (Nyquist) is 0."""
+    img = np.asarray(image, dtype=np.float64)
+    mag = np.expm1(np.maximum(adjust_dynamic_range(img[0], tuple(drange), tuple(mag_range)), 0.0))
+    c = np.cumsum(adjust_dynamic_range(img[1], tuple(drange), (0, 255)) / 128.0 - 1.0, axis=1)
+    spec = np.zeros((img.shape[1] + 1, img.shape[2]), dtype=np.complex128)
+    c = c - 2.0 * np.floor(c / 2.0 + 0.5)                                     # into [-1, 1], exactly: cos / sin see small arguments
+    spec[:-1] = mag * (np.cos(np.pi * c) + 1.0j * np.sin(np.pi * c))
+    return spec
 
 
 def _frames(y, n_fft, hop):
@@ -64,13 +135,20 @@ def istft(spec, hop_length):
 
 
 class SoundSaver(object):
-    """Post-processor writing generated spectrograms / raw waveforms as WAV files (output_postprocess.py:75-153)."""
+    """Post-processor writing generated spectrograms / raw waveforms as WAV files (output_postprocess.py:75-153).  ``mode='magif'``
+    (this project's own): channels 0 and 1 are log-magnitude over ``mag_range`` (default (0, log1p(H))) and instantaneous frequency;
+    the waveform is ONE inverse STFT of magnitude x e^{i pi cumsum(IF)}, no Griffin-Lim and no random start."""
 
     output_file_format = 'fakes_sound_{}_{}.wav'
 
     def __init__(self, samples_path='.', drange=(-1, 1), resolution=512, mode='abslog', sample_rate=16000,
-                 hop_length=128, create_subdirs=True, verbose=False, griffin_lim_iter=100, seed=None):
+                 hop_length=128, create_subdirs=True, verbose=False, griffin_lim_iter=100, seed=None, mag_range=None):
         self.samples_path = samples_path
+        if mag_range is not None:
+            if mode != 'magif':
+                raise ValueError("mag_range belongs to mode='magif' (got mode %r)" % (mode,))
+            mag_range = _mag_range(mag_range, 0)
+        self.mag_range = mag_range
         if create_subdirs:
             os.makedirs(self.samples_path, exist_ok=True)
         self.drange, self.mode, self.sample_rate, self.hop_length = drange, mode, sample_rate, hop_length
@@ -101,8 +179,12 @@ class SoundSaver(object):
             signal = istft((np.exp(np.abs(signed)) - 1) * np.sign(signed), self.hop_length)
         elif self.mode == 'raw':
             signal = image.ravel()
+        elif self.mode == 'magif':                                            # image [2, H, W]: one inverse STFT, no random start
+            if image.ndim != 3 or image.shape[0] != 2:
+                raise ValueError("SoundSaver mode 'magif' takes two-channel images, got shape %s" % (tuple(image.shape),))
+            signal = istft(magif_spectrum(image, self.drange, _mag_range(self.mag_range, 2 * image.shape[1])), self.hop_length)
         else:
-            raise ValueError('SoundSaver mode %r is not one of abslog / reallog / raw' % (self.mode,))
+            raise ValueError('SoundSaver mode %r is not one of abslog / reallog / raw / magif' % (self.mode,))
         return signal / np.abs(signal).max()
 
     def output_wav(self, signal, samples_description, ith):
@@ -123,7 +205,7 @@ class SoundSaver(object):
         if self.mode == 'raw':
             times_smaller *= times_smaller
         for i, img in enumerate(output):
-            signal = self.image_to_sound(img[0])
+            signal = self.image_to_sound(img[:2] if self.mode == 'magif' else img[0])
             if times_smaller > 1:
                 signal = signal.repeat(times_smaller, axis=-1)                # utils.numpy_upsample_nearest(signal, 1, scale_factor=...)
             self.output_wav(signal, samples_description, i)
@@ -141,7 +223,8 @@ class DeviceSoundSaver(SoundSaver):
     ``SoundSaver`` makes -- and uploaded once, so ``seed=`` gives the same WAVs from both savers (``metrics.SlicedWasserstein``
     treats its randomness the same way).  Images must be square with a power-of-two side in 4 .. 1024; there is no fallback to the
     host.  ``verbose=True`` prints the host saver's line per round and sample; it copies both signals back after every round, a slow
-    debugging aid."""
+    debugging aid.  ``mode='magif'`` takes ``[n, 2, H, W]`` samples (further channels are ignored) through csrc/phase.hip: spectrum, pieces,
+    overlap-add and normalisation, four launches, and draws nothing from the RNG."""
 
     accepts_device_tensors = True            # plugins.OutputGenerator then skips the D2H copy of the fp32 samples
 
@@ -150,11 +233,11 @@ class DeviceSoundSaver(SoundSaver):
         ``[n, nsamp * times_smaller]``: each sample's waveform, peak-normalised and stretched as ``SoundSaver.__call__`` writes it."""
         import torch
         from . import ops
-        if self.mode not in ('abslog', 'reallog', 'raw'):
-            raise ValueError('SoundSaver mode %r is not one of abslog / reallog / raw' % (self.mode,))
+        if self.mode not in ('abslog', 'reallog', 'raw', 'magif'):
+            raise ValueError('SoundSaver mode %r is not one of abslog / reallog / raw / magif' % (self.mode,))
         t = output if torch.is_tensor(output) else torch.from_numpy(np.ascontiguousarray(output, dtype=np.float32))
-        if t.dim() != 4 or t.shape[0] < 1:
-            raise ValueError('DeviceSoundSaver: expected samples [n, 1, H, W], got shape %s' % (tuple(t.shape),))
+        if t.dim() != 4 or t.shape[0] < 1 or (self.mode == 'magif' and t.shape[1] < 2):
+            raise ValueError('DeviceSoundSaver: expected samples [n, %d, H, W], got shape %s' % (2 if self.mode == 'magif' else 1, tuple(t.shape)))
         n, _, H, W = t.shape
         if H != W or H < 4 or H > 1024 or H & (H - 1):
             raise ValueError('DeviceSoundSaver: images must be square with a power-of-two side in 4 .. 1024, got %dx%d' % (H, W))
@@ -165,6 +248,10 @@ class DeviceSoundSaver(SoundSaver):
         if self.mode != 'raw' and nsamp <= H:
             raise ValueError('DeviceSoundSaver: %d frames every %d samples give %d samples, the reflect padding by n_fft/2 = %d '
                              'needs more' % (W, self.hop_length, nsamp, H))
+        if self.mode == 'magif':                                              # spectrum, pieces, overlap-add, normalise: four launches,
+            from . import phase                                               # no random draws (the RNG is not advanced)
+            x = phase.synthesise(_to_device(t)[:, :2].to(torch.float32).contiguous(), self.hop_length, self.drange, self.mag_range)
+            return ops.wave_normalize(x, max(1, times_smaller))
         img = _to_device(t)[:, 0].to(torch.float32).contiguous()             # channel 0, as image_to_sound(img[0])
         if self.mode == 'raw':
             x = img.reshape(n, H * W).to(torch.float64)                       # image.ravel(): a cast, the arithmetic is the kernel's
