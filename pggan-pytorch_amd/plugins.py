@@ -32,13 +32,30 @@ def _check_smoothed(trainer, smoothed, who):
         raise ValueError('%s(smoothed=True) needs Trainer(g_ema=GeneratorEMA(G))' % who)
 
 
-def _output_generator(trainer, smoothed):
+PRECISIONS = ('fp32', 'bf16')
+
+
+def _check_precision(precision, who):
+    if precision not in PRECISIONS:
+        raise ValueError("%s(precision=...) must be 'fp32' or 'bf16', got %r" % (who, precision))
+    return precision
+
+
+def _output_generator(trainer, smoothed, precision='fp32'):
     """The network an output plugin evaluates: the smoothed generator Gs when the trainer keeps one (``smoothed=None``: use it if it is
-    there; ``False``: raw G), at G's growth stage and ordered behind its last update."""
+    there; ``False``: raw G), at G's growth stage and ordered behind its last update.  ``precision='bf16'``: that network's
+    ``sampling.Sampler`` instead -- the same ``forward(z)``, evaluated forward-only on the bf16 matrix cores (sampling.py has the
+    contract).  Measured on an MI355X with 16 untrained images per call (docs/experiments_sampling.md): the bf16 pass takes 2.90 ms
+    against 2.44 ms in fp32 at the 1024x1024 stage (0.84x: SLOWER), ties it at 128x128 .. 512x512 (0.98 - 1.05x) and is slower below;
+    the images differ by 1 % relative L2 and MS-SSIM / SWD at 256x256 move by less than a tenth of the metrics' own noise.  Until the
+    bf16 kernels are tuned the keyword buys half-width activations, not time: every period default stays derived for 'fp32'."""
+    _check_precision(precision, '_output_generator')
     ema = getattr(trainer, 'g_ema', None)
-    if ema is None or smoothed is False:
-        return trainer.G
-    return ema.network()
+    net = trainer.G if ema is None or smoothed is False else ema.network()
+    if precision == 'fp32':
+        return net
+    from .sampling import sampler_for
+    return sampler_for(net)
 
 
 def growth_stage(cur_nimg, lod_training_nimg, lod_transition_nimg, max_depth):
@@ -290,14 +307,18 @@ class OutputGenerator(Plugin):
     hand the fp32 ``[n,C,H,W]`` array to each postprocessor as ``proc(out, kimg)``.  A postprocessor exposing
     ``accepts_device_tensors`` (``utils.DeviceImageSaver``) gets the device tensor instead, so only the final
     uint8 grid crosses PCIe.  ``smoothed``: None = the smoothed generator of ``Trainer(g_ema=...)`` when there is one, else G;
-    False = G; True = the smoothed one, or an error at ``register``."""
+    False = G; True = the smoothed one, or an error at ``register``.
 
-    def __init__(self, sample_fn, output_postprocessors, samples_count=6, output_snapshot_ticks=3, smoothed=None):
+    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
+    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
+
+    def __init__(self, sample_fn, output_postprocessors, samples_count=6, output_snapshot_ticks=3, smoothed=None, precision='fp32'):
         super(OutputGenerator, self).__init__([(output_snapshot_ticks, 'epoch'), (1, 'end')])
         self.sample_fn = sample_fn
         self.output_postprocessors = output_postprocessors
         self.samples_count = samples_count
         self.smoothed = smoothed
+        self.precision = _check_precision(precision, 'OutputGenerator')
 
     def register(self, trainer):
         _check_smoothed(trainer, self.smoothed, 'OutputGenerator')
@@ -308,7 +329,7 @@ class OutputGenerator(Plugin):
         if tr.parallel is not None and tr.parallel.rank != 0:
             return
         gen_input = self.sample_fn(self.samples_count).cuda()
-        out_dev = _output_generator(tr, self.smoothed).forward(gen_input)
+        out_dev = _output_generator(tr, self.smoothed, self.precision).forward(gen_input)
         out_host = None
         for proc in self.output_postprocessors:
             if getattr(proc, 'accepts_device_tensors', False):
@@ -337,9 +358,13 @@ class SWDMonitor(Plugin):
     device yet): 10-15 s per evaluation of 16384 images at the 1024x1024 stage, most of it the generator passes and the real
     batches.  Under 1 % of that stage's time (a tick of 1 kimg is about 3.3 s there) then needs 300-450 ticks between evaluations:
     400.  A run that wants the metric more often trades images for it (``num_images=2048, swd_ticks=50`` costs the same by the
-    same estimate and is noisier)."""
+    same estimate and is noisier).
 
-    def __init__(self, real_batch_fn, sample_fn, num_images=16384, minibatch=16, swd_ticks=400, smoothed=None, **metric_kwargs):
+    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
+    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
+
+    def __init__(self, real_batch_fn, sample_fn, num_images=16384, minibatch=16, swd_ticks=400, smoothed=None, precision='fp32',
+                 **metric_kwargs):
         super(SWDMonitor, self).__init__([(swd_ticks, 'epoch'), (1, 'end')])
         if int(num_images) < 1 or int(minibatch) < 1:
             raise ValueError('num_images and minibatch must be positive')
@@ -347,6 +372,7 @@ class SWDMonitor(Plugin):
         self.num_images, self.minibatch = int(num_images), int(minibatch)
         self.metric_kwargs = metric_kwargs
         self.smoothed = smoothed
+        self.precision = _check_precision(precision, 'SWDMonitor')
         self._metric_obj = None
 
     def register(self, trainer):
@@ -369,7 +395,7 @@ class SWDMonitor(Plugin):
             return
         metric = self._metric(resolution)
         metric.reset()
-        gen = _output_generator(tr, self.smoothed)
+        gen = _output_generator(tr, self.smoothed, self.precision)
         for start in range(0, self.num_images, self.minibatch):
             n = min(self.minibatch, self.num_images - start)
             metric.feed_real(self.real_batch_fn(n))
@@ -397,9 +423,12 @@ class MSSSIMMonitor(Plugin):
     ``num_pairs = 10000`` is the paper's count.  The default period is BORROWED from ``SWDMonitor``'s estimate, not measured: an
     evaluation is 20 000 generator passes against the SWD's 16 384 plus its real batches, and the metric's own kernels are the small
     part; no evaluation of either has been timed on the device inside a training run.  Re-derive it as docs/experiments_swd.md
-    does: ticks >= 100 x evaluation seconds / tick seconds at 1024x1024 keeps the metric under 1 % of that stage's time."""
+    does: ticks >= 100 x evaluation seconds / tick seconds at 1024x1024 keeps the metric under 1 % of that stage's time.
 
-    def __init__(self, sample_fn, num_pairs=10000, minibatch=16, msssim_ticks=400, smoothed=None, **metric_kwargs):
+    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
+    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
+
+    def __init__(self, sample_fn, num_pairs=10000, minibatch=16, msssim_ticks=400, smoothed=None, precision='fp32', **metric_kwargs):
         super(MSSSIMMonitor, self).__init__([(msssim_ticks, 'epoch'), (1, 'end')])
         if int(num_pairs) < 1 or int(minibatch) < 1:
             raise ValueError('num_pairs and minibatch must be positive')
@@ -407,6 +436,7 @@ class MSSSIMMonitor(Plugin):
         self.num_pairs, self.minibatch = int(num_pairs), int(minibatch)
         self.metric_kwargs = metric_kwargs
         self.smoothed = smoothed
+        self.precision = _check_precision(precision, 'MSSSIMMonitor')
         self._metric_obj = None
 
     def register(self, trainer):
@@ -430,7 +460,7 @@ class MSSSIMMonitor(Plugin):
             return
         metric = self._metric(resolution, int(tr.G.num_channels))
         metric.reset()
-        gen = _output_generator(tr, self.smoothed)
+        gen = _output_generator(tr, self.smoothed, self.precision)
         for start in range(0, self.num_pairs, self.minibatch):
             n = min(self.minibatch, self.num_pairs - start)
             a = gen.forward(self.sample_fn(n).cuda())
@@ -460,10 +490,13 @@ class NNMonitor(Plugin):
     The default period follows docs/experiments_nn.md: a pass over the stack measured 0.39 ms per GB at 1024x1024 (2.6 TB/s with 64
     queries), i.e. 36 ms for 30 000 images of 3 x 1024^2 by proportion (that size itself was not run), 64 samples and their mirrors are
     two passes, and the 64 generator passes are bounded by 64/3 measured train steps of 10.1 ms = 0.22 s; an evaluation is under 0.3 s,
-    and under 1 % of a 3.3 s tick of 1 kimg (the rule of docs/experiments_swd.md) needs ticks >= 100 x 0.3 / 3.3 = 9: 10."""
+    and under 1 % of a 3.3 s tick of 1 kimg (the rule of docs/experiments_swd.md) needs ticks >= 100 x 0.3 / 3.3 = 9: 10.
+
+    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
+    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
 
     def __init__(self, dataset, sample_fn, num_samples=64, k=3, nn_ticks=10, postprocessors=(), smoothed=None, mirror=None,
-                 drange=(-1, 1)):
+                 drange=(-1, 1), precision='fp32'):
         super(NNMonitor, self).__init__([(nn_ticks, 'epoch'), (1, 'end')])
         if isinstance(k, bool) or int(k) != k or int(k) < 1:
             raise ValueError('k must be a positive integer, got %r' % (k,))
@@ -475,6 +508,7 @@ class NNMonitor(Plugin):
         self.smoothed = smoothed
         self.mirror = bool(getattr(dataset, 'mirror_augment', False)) if mirror is None else bool(mirror)
         self.drange = drange
+        self.precision = _check_precision(precision, 'NNMonitor')
         self._nn = None
 
     def register(self, trainer):
@@ -493,7 +527,7 @@ class NNMonitor(Plugin):
             return
         import torch
         nn = self._search()
-        samples = _output_generator(tr, self.smoothed).forward(self.sample_fn(self.num_samples).cuda())
+        samples = _output_generator(tr, self.smoothed, self.precision).forward(self.sample_fn(self.num_samples).cuda())
         res = nn.search(samples)
         nearest = res['rms'][:, 0].numpy()                                 # fp64 on the host
         tr.stats['nn_rms'] = dict(log_name='nn_rms', log_epoch_fields=_STAT_FMT, val=float(nearest.mean()))
@@ -536,10 +570,13 @@ class NDBMonitor(Plugin):
     images of 3x1024^2 by proportion (that size itself was not run), once per stage; the 8192 generator passes are bounded by 8192 images
     at the 296 img/s of a whole measured train step, 27.7 s.  An evaluation is under 27.8 s, and under 1 % of a 3.3 s tick of 1 kimg (the
     rule of docs/experiments_swd.md) needs ticks >= 100 x 27.8 / 3.3 = 842: 850.  ``num_samples=2048, ndb_ticks=200`` costs the same
-    share with a noisier histogram."""
+    share with a noisier histogram.
+
+    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
+    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
 
     def __init__(self, dataset, sample_fn, num_samples=8192, minibatch=16, k=50, holdout=None, ndb_ticks=850, smoothed=None,
-                 **metric_kwargs):
+                 precision='fp32', **metric_kwargs):
         super(NDBMonitor, self).__init__([(ndb_ticks, 'epoch'), (1, 'end')])
         if int(num_samples) < 1 or int(minibatch) < 1:
             raise ValueError('num_samples and minibatch must be positive')
@@ -547,6 +584,7 @@ class NDBMonitor(Plugin):
         self.num_samples, self.minibatch, self.k = int(num_samples), int(minibatch), k
         self.holdout = min(len(dataset) // 5, self.num_samples) if holdout is None else holdout
         self.smoothed = smoothed
+        self.precision = _check_precision(precision, 'NDBMonitor')
         self.metric_kwargs = metric_kwargs
         self._metric_obj = None
 
@@ -577,7 +615,7 @@ class NDBMonitor(Plugin):
             return
         metric = self._metric()
         metric.reset()
-        gen = _output_generator(tr, self.smoothed)
+        gen = _output_generator(tr, self.smoothed, self.precision)
         for start in range(0, self.num_samples, self.minibatch):
             metric.feed(gen.forward(self.sample_fn(min(self.minibatch, self.num_samples - start)).cuda()))
         res = metric.result()

@@ -141,13 +141,17 @@ class DeviceImageSaver(object):
         im.save(os.path.join(self.samples_path, fname.format(description)))
 
 
-def output_samples(generator_path, num_samples, postprocessors, description):
-    """reference generate.py:18-30: load a whole-module generator snapshot, sample, run the postprocessors."""
+def output_samples(generator_path, num_samples, postprocessors, description, precision='fp32'):
+    """reference generate.py:18-30: load a whole-module generator snapshot, sample, run the postprocessors.  ``precision='bf16'``
+    evaluates the snapshot with ``sampling.Sampler`` (forward-only on the bf16 matrix cores; measured 0.84x the fp32 pass's speed at the
+    1024x1024 stage and 1 % relative L2 from its images: docs/experiments_sampling.md)."""
+    from .sampling import generator_for, check_precision
+    check_precision(precision, 'output_samples(precision=...)')
     G = torch.load(generator_path, weights_only=False)
     G.cuda()
     latent_size = getattr(G, 'latent_size', 512)
     gen_input = random_latents(num_samples, latent_size).cuda()
-    out_dev = G.forward(gen_input)
+    out_dev = generator_for(G, precision).forward(gen_input)
     out_host = None
     for proc in postprocessors:
         if getattr(proc, 'accepts_device_tensors', False):
