@@ -1,11 +1,13 @@
 """ctypes binding of libpggan_hip.so, derived at import from the C headers that declare its ABI.
 
 include/pggan_hip.h (the product boundary), include/pggan_hip_debug.h (thread-local diagnostic exports) and
-include/pggan_hip_cluster.h, include/pggan_hip_gan.h, include/pggan_hip_phase.h and include/pggan_hip_sampling.h (the k-means, the
-GAN-objective, the magnitude + instantaneous-frequency and the bf16 sampling additions to the boundary) are the one statement
+include/pggan_hip_cluster.h, include/pggan_hip_gan.h, include/pggan_hip_phase.h, include/pggan_hip_sampling.h and
+include/pggan_hip_projection.h (the k-means, the GAN-objective, the magnitude + instantaneous-frequency, the bf16 sampling and the
+projection-loss additions to the boundary) are the one statement
 of the ABI: the compiler holds every definition in csrc/*.hip against them, and this module parses them once into SIGNATURES /
-DEBUG_SIGNATURES / CLUSTER_SIGNATURES / GAN_SIGNATURES / PHASE_SIGNATURES / SAMPLING_SIGNATURES (name -> argtypes), the return types, and
-CONSTANTS / CLUSTER_CONSTANTS / GAN_CONSTANTS / PHASE_CONSTANTS / SAMPLING_CONSTANTS (every ``#define PG_*`` of the product header / of an addition as an integer).  A new entry point is
+DEBUG_SIGNATURES / CLUSTER_SIGNATURES / GAN_SIGNATURES / PHASE_SIGNATURES / SAMPLING_SIGNATURES / PROJECTION_SIGNATURES (name -> argtypes), the
+return types, and CONSTANTS / CLUSTER_CONSTANTS / GAN_CONSTANTS / PHASE_CONSTANTS / SAMPLING_CONSTANTS / PROJECTION_CONSTANTS (every
+``#define PG_*`` of the product header / of an addition as an integer).  A new entry point is
 declared in the header, defined in csrc/ and wrapped in ops.py; nothing is restated here.
 
 There is deliberately NO fallback: a prototype or ``#define`` the parser does not fully understand, a missing shared library or an
@@ -123,6 +125,9 @@ _RESTYPE_OF.update(_phase_restypes)
 # ... and the forward-only bf16 generator of the samplers and metric monitors (csrc/sampling.hip, wrapped in sampling.py)
 SAMPLING_SIGNATURES, _sampling_restypes, SAMPLING_CONSTANTS = _read_header('pggan_hip_sampling.h')
 _RESTYPE_OF.update(_sampling_restypes)
+# ... and the pyramid loss of the latent projection with its image gradient (csrc/projection.hip, wrapped in ops.py, used by projection.py)
+PROJECTION_SIGNATURES, _projection_restypes, PROJECTION_CONSTANTS = _read_header('pggan_hip_projection.h')
+_RESTYPE_OF.update(_projection_restypes)
 ABI_VERSION = CONSTANTS['PG_ABI_VERSION']          # load() holds the library's pg_abi_version() against it: a stale .so is refused
 
 _lib = None
@@ -142,7 +147,8 @@ def load():
     except OSError as e:
         raise PgganLibraryError('cannot load %s: %s' % (LIB_PATH, e))
     for name, argtypes in (list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())
-                           + list(GAN_SIGNATURES.items()) + list(PHASE_SIGNATURES.items()) + list(SAMPLING_SIGNATURES.items())):
+                           + list(GAN_SIGNATURES.items()) + list(PHASE_SIGNATURES.items()) + list(SAMPLING_SIGNATURES.items())
+                           + list(PROJECTION_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1364,3 +1364,58 @@ def segment_stats(flat, chunks, ranges, partials=None):
     _lib.call('pg_segment_stats_f32', flat.data_ptr(), flat.numel(), chunks.data_ptr(), nchunks, partials.data_ptr(), s)
     _lib.call('pg_segment_stats_finish', partials.data_ptr(), nchunks, ranges.data_ptr(), S, out.data_ptr(), s)
     return out
+
+
+# ------------------------------------------------------------------------- pyramid loss of the latent projection (csrc/projection.hip)
+PYR = {name[len('PG_PYR_'):]: value for name, value in _lib.PROJECTION_CONSTANTS.items() if name.startswith('PG_PYR_')}   # the addition's own table
+PYR_TILE, PYR_MAX_SIDE, PYR_MAX_C, PYR_SCRATCH_PER_TILE = PYR['TILE'], PYR['MAX_SIDE'], PYR['MAX_C'], PYR['SCRATCH_PER_TILE']
+
+
+def pyramid_levels(r):
+    """Levels of the box-mean pyramid of an r x r image: sides r, r/2, .., 4."""
+    return int(r).bit_length() - 2
+
+
+def pyramid_scratch_words(N, C, r):
+    """fp64 words of scratch ``pyramid_loss`` needs for a batch [N,C,r,r]."""
+    return PYR_SCRATCH_PER_TILE * N * C * (r // min(r, PYR_TILE)) ** 2
+
+
+def pyramid_loss(img, target, weights=None, want_grad=True, scratch=None):
+    """Multi-resolution squared error of two fp32 device batches [N,C,r,r] (r a power of two in 4 .. 1024, C in 1 .. 4) and its gradient
+    with respect to ``img`` (pg_pyr_loss_grad, include/pggan_hip_projection.h):
+
+        loss[n] = sum_l w_l mean_{c,y,x} P_l(img - target)[n]^2,    P_l the l-fold 2x2 box mean, sides r .. 4
+
+    ``weights``: a sequence of up to ``pyramid_levels(r)`` non-negative floats, w_l of the levels from the finest (missing ones are 0);
+    None: every level 1.  Returns ``(loss [N], grad [N,C,r,r])``, fp32 device tensors; ``want_grad=False`` gives ``(loss, None)`` in one
+    pass over the images.  fp64 sums in a fixed order, one rounding per output, no atomics: two calls give the same bits.  ``scratch``:
+    a float64 device tensor of at least ``pyramid_scratch_words(N, C, r)`` elements to reuse.  No host synchronisation."""
+    for t, name in ((img, 'img'), (target, 'target')):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('pyramid_loss %s: expected a contiguous float32 device tensor' % name)
+    if img.dim() != 4 or img.shape != target.shape or img.device != target.device:
+        raise ValueError('pyramid_loss: expected two equal shapes [N,C,r,r] on one device, got %s and %s' % (tuple(img.shape), tuple(target.shape)))
+    N, C, r, W = img.shape
+    if N < 1 or not 1 <= C <= PYR_MAX_C or r != W or r < 4 or (r & (r - 1)) or r > PYR_MAX_SIDE:
+        raise ValueError('pyramid_loss: expected [N,C,r,r] with N >= 1, C in 1 .. %d and r a power of two in 4 .. %d, got %s'
+                         % (PYR_MAX_C, PYR_MAX_SIDE, tuple(img.shape)))
+    wbuf, nlev = None, 0
+    if weights is not None:
+        ws = [float(w) for w in weights]
+        nlev = len(ws)
+        if not 1 <= nlev <= pyramid_levels(r) or any(not (0.0 <= w < float('inf')) for w in ws):
+            raise ValueError('pyramid_loss: weights must be 1 .. %d finite non-negative numbers for r = %d, got %r' % (pyramid_levels(r), r, ws))
+        wbuf = (ctypes.c_float * nlev)(*ws)
+    words = pyramid_scratch_words(N, C, r)
+    if scratch is None:
+        scratch = torch.empty(words, device=img.device, dtype=torch.float64)
+    elif (not torch.is_tensor(scratch) or scratch.device != img.device or scratch.dtype != torch.float64 or not scratch.is_contiguous()
+          or scratch.numel() < words):
+        raise ValueError('pyramid_loss: scratch must be a contiguous float64 tensor of at least %d elements on the device of the images' % words)
+    require_gpu()
+    loss = torch.empty(N, device=img.device, dtype=torch.float32)
+    grad = torch.empty_like(img) if want_grad else None
+    _lib.call('pg_pyr_loss_grad', img.data_ptr(), target.data_ptr(), ctypes.cast(wbuf, ctypes.c_void_p) if wbuf is not None else None, nlev,
+              grad.data_ptr() if grad is not None else None, loss.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, N, C, r, _stream())
+    return loss, grad

@@ -627,6 +627,117 @@ class NDBMonitor(Plugin):
         self.epoch(*args)
 
 
+class ProjectionMonitor(Plugin):
+    """Recall-style measure per tick (``projection.Projector``; the reference reports none): every ``projection_ticks`` ticks and at the
+    end, a FIXED set of ``num_images`` real images is projected into the latent space of the generator -- of the smoothed generator when
+    the trainer keeps one (``smoothed``: None = Gs if there is one, False = raw G, True = Gs or an error at ``register``) -- and the
+    pyramid loss the search ends at says how well the generator can reproduce images it was not asked to produce.  It is defined for
+    1-, 2-, 3- and 4-channel networks alike.
+
+    ``source``: a ``DeviceImageDataset`` -- the targets are its LAST ``num_images`` images at the current growth stage with alpha 1 and no
+    mirror, the same indices at every evaluation (the end of the stack, where ``metrics.NDB`` holds images out as well; the training
+    stream is not moved) -- or ``real_batch_fn(n)`` -> fp32 device batch ``[n,C,r,r]`` at the current stage's resolution, called ONCE per
+    resolution and kept (give it a seeded stream of its own, e.g. ``dataset.metric_batches(seed)``).  ``projector_kwargs`` go to
+    ``Projector`` (lr, betas, level_weights, seed).
+
+    Writes ``stats['proj_loss']`` (the mean over the targets of the final loss) and ``stats['proj_loss_max']`` (the worst target)
+    under the stat-dict convention of the other monitors.  With ``samples_path`` it writes ``proj_<kimg>.png`` there through
+    ``utils.DeviceImageSaver``'s grid path (``drange``, ``resolution`` as there): ONE batch of 2 x num_images images, each target followed
+    by its reconstruction, so that with an even grid width (ceil(sqrt(2 num_images)): 4 for the default 8) a target stands beside its
+    reconstruction.  Every post-processor gets the same batch as ``proc(batch, 'proj_%06d' % kimg)``.  Rank 0 evaluates (replicas are
+    identical).  Opt-in: a run that does not register it pays nothing.  ``precision='bf16'`` is refused: the bf16 sampler has no
+    backward pass.
+
+    The defaults follow docs/experiments_projection.md: a 200-step projection of 8 images measured 0.89 s at the 1024x1024 stage (4.47 ms
+    per step) and 0.47 s at 256x256 (2.37 ms per step) on an MI355X, untrained weights.  Under 1 % of a 3.3 s tick of 1 kimg at 1024x1024
+    (the rule of docs/experiments_swd.md) needs ticks >= 100 x 0.89 / 3.3 = 27.1: 30.  200 steps is where the search was measured; on the
+    untrained networks it takes the loss of the generator's own images to 0.14 - 0.26 of the start value, a trained one was not run."""
+
+    def __init__(self, source, num_images=8, steps=200, projection_ticks=30, smoothed=None, precision='fp32', samples_path=None,
+                 drange=(-1, 1), resolution=512, postprocessors=(), **projector_kwargs):
+        super(ProjectionMonitor, self).__init__([(projection_ticks, 'epoch'), (1, 'end')])
+        _check_precision(precision, 'ProjectionMonitor')
+        if precision != 'fp32':
+            raise ValueError("ProjectionMonitor(precision=%r): the projection needs the generator's backward sweep, which the bf16 "
+                             "sampler does not have; only 'fp32' is taken" % (precision,))
+        if isinstance(num_images, bool) or int(num_images) != num_images or int(num_images) < 1:
+            raise ValueError('num_images must be a positive integer, got %r' % (num_images,))
+        if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+            raise ValueError('steps must be a positive integer, got %r' % (steps,))
+        if not callable(source) and not (hasattr(source, '_make') and hasattr(source, '__len__')):
+            raise ValueError('ProjectionMonitor: source must be a DeviceImageDataset or a function n -> real batch, got %s' % type(source).__name__)
+        if not callable(source) and len(source) < int(num_images):
+            raise ValueError('ProjectionMonitor: %d targets from a dataset of %d images' % (num_images, len(source)))
+        self.source = source
+        self.num_images, self.steps = int(num_images), int(steps)
+        self.smoothed, self.precision = smoothed, precision
+        self.samples_path, self.drange, self.resolution = samples_path, drange, resolution
+        self.postprocessors = postprocessors
+        self.projector_kwargs = projector_kwargs
+        self._targets = {}               # resolution -> the fixed targets of that stage (real_batch_fn sources)
+        self._projector = None           # (network it was made for, Projector)
+
+    def register(self, trainer):
+        _check_smoothed(trainer, self.smoothed, 'ProjectionMonitor')
+        self.trainer = trainer
+
+    def targets(self, resolution):
+        """The fixed targets at ``resolution``: the same images at every call."""
+        import torch
+        if not callable(self.source):
+            ds = self.source
+            M = len(ds)
+            idx = torch.arange(M - self.num_images, M, dtype=torch.int64, device=getattr(ds, 'device', 'cpu'))
+            return ds._make(idx, None, 1.0)
+        t = self._targets.get(resolution)
+        if t is None:
+            t = self.source(self.num_images)
+            if tuple(t.shape[-2:]) != (resolution, resolution) or t.shape[0] != self.num_images:
+                raise ValueError('ProjectionMonitor: real_batch_fn(%d) gave %s at the %dx%d stage'
+                                 % (self.num_images, tuple(t.shape), resolution, resolution))
+            self._targets = {resolution: t}                                  # (one stage's targets are alive at a time)
+        return t
+
+    def _projector_for(self, net):
+        if self._projector is None or self._projector[0]() is not net:
+            import weakref
+            from .projection import Projector
+            self._projector = (weakref.ref(net), Projector(net, steps=self.steps, **self.projector_kwargs))
+        return self._projector[1]
+
+    def epoch(self, epoch_index):
+        tr = self.trainer
+        if tr.parallel is not None and tr.parallel.rank != 0:
+            return
+        import torch
+        net = _output_generator(tr, self.smoothed, 'fp32')
+        targets = self.targets(4 * 2 ** int(net.depth))
+        res = self._projector_for(net).project(targets)
+        loss = res.loss.double().cpu()                                       # the one host synchronisation of an evaluation
+        tr.stats['proj_loss'] = dict(log_name='proj_loss', log_epoch_fields=['{val:.5f}'], val=float(loss.mean()))
+        tr.stats['proj_loss_max'] = dict(log_name='proj_loss_max', log_epoch_fields=['{val:.5f}'], val=float(loss.max()))
+        if not self.postprocessors and self.samples_path is None:
+            return
+        batch = torch.stack([targets, res.images], dim=1).reshape((2 * targets.shape[0],) + tuple(targets.shape[1:]))
+        if self.samples_path is not None:
+            from .utils import DeviceImageSaver
+            saver = DeviceImageSaver(self.samples_path, self.drange, self.resolution)
+            saver.output_file_format = 'proj_{}.png'
+            saver(batch, tr.cur_nimg // 1000)
+        description = 'proj_%06d' % (tr.cur_nimg // 1000)
+        host = None
+        for proc in self.postprocessors:
+            if getattr(proc, 'accepts_device_tensors', False):
+                proc(batch, description)
+            else:
+                if host is None:
+                    host = batch.cpu().numpy()
+                proc(host, description)
+
+    def end(self, *args):
+        self.epoch(*args)
+
+
 class LossMonitor(Plugin):
     """The losses of a run per tick (replaces the reference's four ``EfficientLossMonitor``s, train.py:170-171 / plugins.py:102-111, which
     read every loss on the host every iteration).  ``iteration(i, *losses)`` makes ONE ``telemetry.ScalarStats.push`` of the tensors the

@@ -161,3 +161,32 @@ def output_samples(generator_path, num_samples, postprocessors, description, pre
                 out_host = out_dev.cpu().numpy()
             proc(out_host, description)
     return out_dev
+
+
+def project_samples(generator_path, targets, postprocessors, description, **projector_kw):
+    """The inverse of ``output_samples``: load a whole-module generator snapshot and find the latents whose images match ``targets``
+    (``projection.Projector``; ``projector_kw``: steps, lr, betas, level_weights, seed).  ``targets``: fp32 ``[M,C,r,r]`` in the
+    generator's output range, or uint8 ``[M,C,r,r]``, which goes through ``prepare_real_batch`` with alpha 1 -- a tensor or an array, on
+    the host or the device; r is the resolution of the snapshot's growth stage.  Every post-processor gets ``[targets; reconstructions]``
+    (the M targets, then their M reconstructions) under ``description``: ``DeviceSoundSaver`` then writes each target's spectrogram and
+    its resynthesis as WAVs.  Returns the latents ``[M,latent]`` on the device."""
+    from .projection import Projector
+    G = torch.load(generator_path, weights_only=False)
+    G.cuda()
+    t = targets if torch.is_tensor(targets) else torch.from_numpy(np.ascontiguousarray(targets))
+    if t.dtype == torch.uint8:
+        t = prepare_real_batch(t.cuda().contiguous(), 1.0)
+    elif t.dtype != torch.float32:
+        raise ValueError('project_samples: targets must be uint8 or float32, got %s' % t.dtype)
+    t = t.cuda().contiguous()
+    res = Projector(G, **projector_kw).project(t)
+    out_dev = torch.cat([t, res.images], dim=0)
+    out_host = None
+    for proc in postprocessors:
+        if getattr(proc, 'accepts_device_tensors', False):
+            proc(out_dev, description)
+        else:
+            if out_host is None:
+                out_host = out_dev.cpu().numpy()
+            proc(out_host, description)
+    return res.z
