@@ -65,12 +65,11 @@ USE_LAZY_UNPOOL = True         # tests/test_winograd.py::test_engine_with_lazy_p
 
 def _live_conv_layers(net):
     """3x3 / 4x4 conv layers that can run at the network's current growth stage (D: blocks[-(depth+1):], network.py:227-238;
-    G: block0 and blocks[:depth], network.py:124-130)."""
+    G: ``Generator.stage_convs``)."""
     depth = int(net.depth)
-    if hasattr(net, 'linear'):                                  # Discriminator
-        blocks = list(net.blocks)[len(net.blocks) - 1 - depth:]
-    else:
-        blocks = [net.block0] + list(net.blocks)[:depth]
+    if not hasattr(net, 'linear'):                              # Generator
+        return [lay for _, lay in net.stage_convs(depth)]
+    blocks = list(net.blocks)[len(net.blocks) - 1 - depth:]
     return [m for b in blocks for m in (b.c1, b.c2)]
 
 
@@ -642,10 +641,9 @@ def generator_forward(G, z, save=False, out=None, pair_out=None):
         hprev, h = h, a2
     if img is not None:
         return (img, ctx) if save else img
-    t = G.blocks[depth - 1].toRGB
+    t, pt = G.rgb_heads(depth, alpha)
     prev = None
-    if alpha < 1.0:                                                           # :131-135
-        pt = G.blocks[depth - 2].toRGB if depth > 1 else b0.toRGB
+    if pt is not None:                                                        # :131-135
         prev = ops.torgb_fwd(hprev, pt.conv.weight.data, pt.conv.bias.data, N, C, H // 2, H // 2, pt.c)
     img = to_rgb(h, t, H, out_mul=alpha, prev=prev, prev_mul=1.0 - alpha)    # :138
     return (img, ctx) if save else img
@@ -661,8 +659,8 @@ def generator_backward(G, ctx, g_out):
     active = [b0.c1, b0.c2]
     g_extra = None
     top_done = False
+    t, pt = G.rgb_heads(depth, alpha)
     if depth == 0:
-        t = b0.toRGB
         with _on_side(g_out, ctx.y2):
             ops.torgb_wgrad(g_out, ctx.y2, t._gw, t._gb, N, C, 4, 4, t.c, 1.0)
         g = ops.torgb_bwd_data(g_out, t.conv.weight.data, N, C, 4, 4, t.c)
@@ -670,7 +668,6 @@ def generator_backward(G, ctx, g_out):
     else:
         rec = ctx.recs[-1]
         H = rec.H
-        t = rec.blk.toRGB
         with _on_side(g_out, rec.a2):
             ops.torgb_wgrad(g_out, rec.a2, t._gw, t._gb, N, C, H, H, alpha * t.c, alpha)
         # toRGB's adjoint + the adjoint of the top block's last (LeakyReLU -> PixelNorm) in one launch (network.py:138, :44-52)
@@ -680,8 +677,7 @@ def generator_backward(G, ctx, g_out):
         else:                                         # (a generator built without PixelNorm: the adjoint is LeakyReLU' alone)
             g = ops.torgb_bwd_data(g_out, t.conv.weight.data, N, C, H, H, alpha * t.c)
         active.append(t)
-        if alpha < 1.0:
-            pt = G.blocks[depth - 2].toRGB if depth > 1 else b0.toRGB
+        if pt is not None:
             with _on_side(g_out, rec.inp):
                 ops.torgb_wgrad(g_out, rec.inp, pt._gw, pt._gb, N, C, H // 2, H // 2, (1 - alpha) * pt.c,
                                 1 - alpha, down=True)
@@ -1191,13 +1187,7 @@ def d_exchange_layers(D, depth, alpha):
 def g_exchange_layers(G, depth, alpha):
     """Layers that receive a gradient in a G step at (depth, alpha) (the ``active`` list of generator_backward)."""
     G._ensure_buffers()
-    layers = [G.block0.c1, G.block0.c2]
-    for i in range(depth):
-        layers += [G.blocks[i].c1, G.blocks[i].c2]
-    layers.append(G.blocks[depth - 1].toRGB if depth > 0 else G.block0.toRGB)
-    if depth > 0 and alpha < 1.0:
-        layers.append(G.blocks[depth - 2].toRGB if depth > 1 else G.block0.toRGB)
-    return layers
+    return [lay for _, lay in G.stage_convs(depth)] + [t for t in G.rgb_heads(depth, alpha) if t is not None]
 
 
 def discriminator_forward(D, x):

@@ -395,6 +395,23 @@ class Generator(_FlatParamsMixin, nn.Module):
         from . import engine
         return engine.generator_forward(self, x)
 
+    # The stage structure (reference network.py:124-138), stated once for every walker of the generator: the engine's passes, the
+    # gradient exchange, the bf16 sampler and the projector.
+    def stage_convs(self, depth):
+        """``[(dotted name, layer), ...]`` of the conv layers that run at ``depth``, in evaluation order."""
+        out = [('block0.c1', self.block0.c1), ('block0.c2', self.block0.c2)]
+        for i in range(depth):
+            out += [('blocks.%d.c1' % i, self.blocks[i].c1), ('blocks.%d.c2' % i, self.blocks[i].c2)]
+        return out
+
+    def rgb_heads(self, depth, alpha):
+        """``(head, previous)``: the toRGB of the top block at ``depth``, and the toRGB of the stage below that the fade-in blends in
+        with weight 1 - alpha (None unless ``depth > 0 and alpha < 1``)."""
+        head = self.blocks[depth - 1].toRGB if depth > 0 else self.block0.toRGB
+        if not (depth > 0 and alpha < 1.0):
+            return head, None
+        return head, (self.blocks[depth - 2].toRGB if depth > 1 else self.block0.toRGB)
+
 
 class Discriminator(_FlatParamsMixin, nn.Module):
     """reference network.py:190-240."""

@@ -24,7 +24,15 @@ class Plugin(object):
         raise NotImplementedError
 
 
-_STAT_FMT = ['{val:.2f}']
+def _stat(stats, name, value, fmt='{val:.2f}', **extra):
+    """One entry of ``trainer.stats`` under the convention the reference's ``Logger`` prints (``log_name``, ``log_epoch_fields``, ``val``)."""
+    stats[name] = dict(log_name=name, log_epoch_fields=[fmt], val=value, **extra)
+
+
+def _is_replica(trainer):
+    """Replicas of a data-parallel run are identical: rank 0 alone writes and evaluates."""
+    dp = getattr(trainer, 'parallel', None)
+    return dp is not None and dp.rank != 0
 
 
 def _check_smoothed(trainer, smoothed, who):
@@ -32,30 +40,23 @@ def _check_smoothed(trainer, smoothed, who):
         raise ValueError('%s(smoothed=True) needs Trainer(g_ema=GeneratorEMA(G))' % who)
 
 
-PRECISIONS = ('fp32', 'bf16')
-
-
 def _check_precision(precision, who):
-    if precision not in PRECISIONS:
-        raise ValueError("%s(precision=...) must be 'fp32' or 'bf16', got %r" % (who, precision))
-    return precision
+    from .sampling import check_precision
+    return check_precision(precision, '%s(precision=...)' % who)
 
 
 def _output_generator(trainer, smoothed, precision='fp32'):
     """The network an output plugin evaluates: the smoothed generator Gs when the trainer keeps one (``smoothed=None``: use it if it is
     there; ``False``: raw G), at G's growth stage and ordered behind its last update.  ``precision='bf16'``: that network's
     ``sampling.Sampler`` instead -- the same ``forward(z)``, evaluated forward-only on the bf16 matrix cores (sampling.py has the
-    contract).  Measured on an MI355X with 16 untrained images per call (docs/experiments_sampling.md): the bf16 pass takes 2.90 ms
-    against 2.44 ms in fp32 at the 1024x1024 stage (0.84x: SLOWER), ties it at 128x128 .. 512x512 (0.98 - 1.05x) and is slower below;
+    contract).  Measured on an MI355X with 16 untrained images per call (docs/experiments_sampling.md): the bf16 pass is SLOWER than
+    the fp32 one at the 1024x1024 stage (2.90 against 2.44 ms: 0.84x), ties it at 128x128 .. 512x512 (0.98 - 1.05x) and is slower below;
     the images differ by 1 % relative L2 and MS-SSIM / SWD at 256x256 move by less than a tenth of the metrics' own noise.  Until the
     bf16 kernels are tuned the keyword buys half-width activations, not time: every period default stays derived for 'fp32'."""
+    from .sampling import generator_for
     _check_precision(precision, '_output_generator')
     ema = getattr(trainer, 'g_ema', None)
-    net = trainer.G if ema is None or smoothed is False else ema.network()
-    if precision == 'fp32':
-        return net
-    from .sampling import sampler_for
-    return sampler_for(net)
+    return generator_for(trainer.G if ema is None or smoothed is False else ema.network(), precision)
 
 
 def growth_stage(cur_nimg, lod_training_nimg, lod_transition_nimg, max_depth):
@@ -107,9 +108,9 @@ class DepthManager(Plugin):
         self.trainer = trainer
         stats = trainer.stats
         stats['minibatch_size'] = self.minibatch_default
-        stats['alpha'] = dict(log_name='alpha', log_epoch_fields=list(_STAT_FMT), val=self.alpha)
+        _stat(stats, 'alpha', self.alpha)
         if self._reports_lod:
-            stats['lod'] = dict(log_name='lod', log_epoch_fields=list(_STAT_FMT), val=self.lod)
+            _stat(stats, 'lod', self.lod)
         self.iteration()                                             # stage 0 is applied before the first step
 
     def _enter_stage(self, depth):
@@ -197,8 +198,8 @@ class TimeMonitor(Plugin):
         self.start_time = self.epoch_start = time.time()
         self.start_nimg = trainer.cur_nimg
         trainer.stats['sec'] = {'log_format': ':.1f'}
-        trainer.stats['img/s'] = dict(val=0.0, log_epoch_fields=['{val:.1f}'], log_name='img/s')
-        trainer.stats['d_gp_ms'] = dict(val=0.0, log_epoch_fields=['{val:.3f}'], log_name='d_gp_ms')
+        _stat(trainer.stats, 'img/s', 0.0, '{val:.1f}')
+        _stat(trainer.stats, 'd_gp_ms', 0.0, '{val:.3f}')
         trainer.d_step_probe = dict(every=max(1, self.sample_every), pairs=[])
 
     def epoch(self, epoch_index):
@@ -249,8 +250,8 @@ class SaverPlugin(Plugin):
     def epoch(self, epoch_index):
         import torch
         tr = self.trainer
-        if tr.parallel is not None and tr.parallel.rank != 0:
-            return                                                   # replicas are identical: rank 0 writes
+        if _is_replica(tr):
+            return
         if not self.keep_old_checkpoints:
             self._clear(self.last_pattern.format('*', '*'))
         kimg = '{:06}'.format(tr.cur_nimg // 1000)
@@ -302,53 +303,73 @@ def load_trainer_state(resume_network, result_dir, optimizer_d, optimizer_g):
     return state['cur_nimg']
 
 
-class OutputGenerator(Plugin):
-    """Sample-grid hook (plugins.py:177-195): every ``output_snapshot_ticks`` ticks run G on fresh latents and
-    hand the fp32 ``[n,C,H,W]`` array to each postprocessor as ``proc(out, kimg)``.  A postprocessor exposing
-    ``accepts_device_tensors`` (``utils.DeviceImageSaver``) gets the device tensor instead, so only the final
-    uint8 grid crosses PCIe.  ``smoothed``: None = the smoothed generator of ``Trainer(g_ema=...)`` when there is one, else G;
-    False = G; True = the smoothed one, or an error at ``register``.
+class Evaluation(Plugin):
+    """What the per-tick evaluations share: they fire every ``ticks`` ticks and at the end, on rank 0 only (replicas are identical), as
+    ``evaluate(tick)`` -- the one method a subclass writes.  ``smoothed``: None = the smoothed generator of ``Trainer(g_ema=...)`` when
+    there is one, else G; False = G; True = the smoothed one, or an error at ``register``.  ``precision``: 'fp32' (default) evaluates
+    that network itself, 'bf16' its ``sampling.Sampler``; ``_output_generator`` has the rule and the measured cost of 'bf16'.
+    ``generator()`` is the object to call ``.forward(z)`` on, ``stat(name, value, fmt)`` writes one ``trainer.stats`` entry, and
+    ``cached(key, make)`` keeps the one metric object of the current stage in ``_metric_obj``."""
 
-    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
-    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
-
-    def __init__(self, sample_fn, output_postprocessors, samples_count=6, output_snapshot_ticks=3, smoothed=None, precision='fp32'):
-        super(OutputGenerator, self).__init__([(output_snapshot_ticks, 'epoch'), (1, 'end')])
-        self.sample_fn = sample_fn
-        self.output_postprocessors = output_postprocessors
-        self.samples_count = samples_count
+    def __init__(self, ticks, smoothed=None, precision='fp32'):
+        super(Evaluation, self).__init__([(ticks, 'epoch'), (1, 'end')])
         self.smoothed = smoothed
-        self.precision = _check_precision(precision, 'OutputGenerator')
+        self.precision = _check_precision(precision, type(self).__name__)
+        self._metric_obj = self._metric_key = None
 
     def register(self, trainer):
-        _check_smoothed(trainer, self.smoothed, 'OutputGenerator')
+        _check_smoothed(trainer, self.smoothed, type(self).__name__)
         self.trainer = trainer
 
     def epoch(self, epoch_index):
-        tr = self.trainer
-        if tr.parallel is not None and tr.parallel.rank != 0:
-            return
-        gen_input = self.sample_fn(self.samples_count).cuda()
-        out_dev = _output_generator(tr, self.smoothed, self.precision).forward(gen_input)
-        out_host = None
-        for proc in self.output_postprocessors:
-            if getattr(proc, 'accepts_device_tensors', False):
-                proc(out_dev, tr.cur_nimg // 1000)
-            else:
-                if out_host is None:
-                    out_host = out_dev.cpu().numpy()
-                proc(out_host, tr.cur_nimg // 1000)
+        if not _is_replica(self.trainer):
+            self.evaluate(epoch_index)
 
     def end(self, *args):
         self.epoch(*args)
 
+    def evaluate(self, tick):
+        raise NotImplementedError
 
-class SWDMonitor(Plugin):
+    def generator(self):
+        return _output_generator(self.trainer, self.smoothed, self.precision)
+
+    def stat(self, name, value, fmt='{val:.2f}'):
+        _stat(self.trainer.stats, name, value, fmt)
+
+    def cached(self, key, make):
+        """``make()`` when ``key`` has changed, else the object made last.  One is alive at a time: the buffers of a metric are gigabytes
+        at the default sizes, so a new stage drops the last stage's object BEFORE it allocates its own."""
+        if self._metric_obj is None or self._metric_key != key:
+            self._metric_obj = None
+            self._metric_obj, self._metric_key = make(), key
+        return self._metric_obj
+
+
+class OutputGenerator(Evaluation):
+    """Sample-grid hook (plugins.py:177-195): every ``output_snapshot_ticks`` ticks run G on fresh latents and
+    hand the fp32 ``[n,C,H,W]`` array to each postprocessor as ``proc(out, kimg)``.  A postprocessor exposing
+    ``accepts_device_tensors`` (``utils.DeviceImageSaver``) gets the device tensor instead, so only the final
+    uint8 grid crosses PCIe.  ``smoothed``, ``precision``: as in ``Evaluation``."""
+
+    def __init__(self, sample_fn, output_postprocessors, samples_count=6, output_snapshot_ticks=3, smoothed=None, precision='fp32'):
+        super(OutputGenerator, self).__init__(output_snapshot_ticks, smoothed, precision)
+        self.sample_fn = sample_fn
+        self.output_postprocessors = output_postprocessors
+        self.samples_count = samples_count
+
+    def evaluate(self, tick):
+        from .utils import run_postprocessors
+        out_dev = self.generator().forward(self.sample_fn(self.samples_count).cuda())
+        run_postprocessors(out_dev, self.trainer.cur_nimg // 1000, self.output_postprocessors)
+
+
+class SWDMonitor(Evaluation):
     """Quality metric per tick (``metrics.SlicedWasserstein``; the reference reports none): every ``swd_ticks`` ticks and at the end,
     ``num_images`` real images from ``real_batch_fn(n)`` (fp32 device batches ``[n,3,R,R]`` at the current stage's resolution, e.g.
     ``utils.prepare_real_batch`` of a dataset batch) are measured against as many of ``G.forward(sample_fn(n).cuda())``, ``minibatch``
     at a time -- of the smoothed generator when the trainer keeps one, which is what the paper measures (``smoothed`` as in
-    ``OutputGenerator``: None = Gs if there is one, False = raw G, True = Gs or an error at ``register``).  Writes ``stats['swd']``
+    ``Evaluation``).  Writes ``stats['swd']``
     (the mean over the pyramid levels, x 1000) and one ``stats['swd_<res>']`` per level under the stat-dict convention of the other monitors.  Stages below 16x16 have no pyramid level: nothing is written there.  Rank 0
     evaluates (replicas are identical).  ``metric_kwargs`` go to ``SlicedWasserstein`` (patches_per_image, dir_repeats,
     dirs_per_repeat, seed).  One metric object (buffers, patch centres, directions) is alive at a time: a new stage drops the last
@@ -360,61 +381,40 @@ class SWDMonitor(Plugin):
     400.  A run that wants the metric more often trades images for it (``num_images=2048, swd_ticks=50`` costs the same by the
     same estimate and is noisier).
 
-    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
-    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
+    ``precision``: 'fp32' (default) or 'bf16', as in ``Evaluation``."""
 
     def __init__(self, real_batch_fn, sample_fn, num_images=16384, minibatch=16, swd_ticks=400, smoothed=None, precision='fp32',
                  **metric_kwargs):
-        super(SWDMonitor, self).__init__([(swd_ticks, 'epoch'), (1, 'end')])
+        super(SWDMonitor, self).__init__(swd_ticks, smoothed, precision)
         if int(num_images) < 1 or int(minibatch) < 1:
             raise ValueError('num_images and minibatch must be positive')
         self.real_batch_fn, self.sample_fn = real_batch_fn, sample_fn
         self.num_images, self.minibatch = int(num_images), int(minibatch)
         self.metric_kwargs = metric_kwargs
-        self.smoothed = smoothed
-        self.precision = _check_precision(precision, 'SWDMonitor')
-        self._metric_obj = None
 
-    def register(self, trainer):
-        _check_smoothed(trainer, self.smoothed, 'SWDMonitor')
-        self.trainer = trainer
-
-    def _metric(self, resolution):
-        if self._metric_obj is None or self._metric_obj.resolution != resolution:
-            from .metrics import SlicedWasserstein
-            self._metric_obj = None                                      # a new stage: free the last one's buffers before allocating
-            self._metric_obj = SlicedWasserstein(resolution, self.num_images, **self.metric_kwargs)
-        return self._metric_obj
-
-    def epoch(self, epoch_index):
-        tr = self.trainer
-        if tr.parallel is not None and tr.parallel.rank != 0:
-            return
-        resolution = 4 * 2 ** tr.G.depth
+    def evaluate(self, tick):
+        from .metrics import SlicedWasserstein
+        resolution = 4 * 2 ** self.trainer.G.depth
         if resolution < 16:
             return
-        metric = self._metric(resolution)
+        metric = self.cached(resolution, lambda: SlicedWasserstein(resolution, self.num_images, **self.metric_kwargs))
         metric.reset()
-        gen = _output_generator(tr, self.smoothed, self.precision)
+        gen = self.generator()
         for start in range(0, self.num_images, self.minibatch):
             n = min(self.minibatch, self.num_images - start)
             metric.feed_real(self.real_batch_fn(n))
             metric.feed_fake(gen.forward(self.sample_fn(n).cuda()))
         res = metric.result()
-        tr.stats['swd'] = dict(log_name='swd', log_epoch_fields=['{val:.3f}'], val=res['mean'])
+        self.stat('swd', res['mean'], '{val:.3f}')
         for size, value in zip(res['levels'], res['swd']):
-            name = 'swd_%d' % size
-            tr.stats[name] = dict(log_name=name, log_epoch_fields=['{val:.3f}'], val=value)
-
-    def end(self, *args):
-        self.epoch(*args)
+            self.stat('swd_%d' % size, value, '{val:.3f}')
 
 
-class MSSSIMMonitor(Plugin):
+class MSSSIMMonitor(Evaluation):
     """Diversity metric per tick (``metrics.MultiScaleSSIM``; the reference reports none): every ``msssim_ticks`` ticks and at the end,
     ``num_pairs`` pairs of generated images are compared, ``minibatch`` pairs at a time.  Each round is two forward passes on
     independent latents from ``sample_fn(n).cuda()``, fed as pairs -- of the smoothed generator when the trainer keeps one (``smoothed``
-    as in ``OutputGenerator``: None = Gs if there is one, False = raw G, True = Gs or an error at ``register``).  Writes
+    as in ``Evaluation``).  Writes
     ``stats['msssim']`` (the mean over the pairs; it RISES when the generator loses variation) and ``stats['msssim_std']`` under the
     stat-dict convention of the other monitors.  The channel count comes from ``G``: one-channel networks are measured like RGB
     ones.  Stages below 16x16 have no scale: nothing is written there.  Rank 0 evaluates (replicas are identical).
@@ -425,58 +425,38 @@ class MSSSIMMonitor(Plugin):
     part; no evaluation of either has been timed on the device inside a training run.  Re-derive it as docs/experiments_swd.md
     does: ticks >= 100 x evaluation seconds / tick seconds at 1024x1024 keeps the metric under 1 % of that stage's time.
 
-    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
-    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
+    ``precision``: 'fp32' (default) or 'bf16', as in ``Evaluation``."""
 
     def __init__(self, sample_fn, num_pairs=10000, minibatch=16, msssim_ticks=400, smoothed=None, precision='fp32', **metric_kwargs):
-        super(MSSSIMMonitor, self).__init__([(msssim_ticks, 'epoch'), (1, 'end')])
+        super(MSSSIMMonitor, self).__init__(msssim_ticks, smoothed, precision)
         if int(num_pairs) < 1 or int(minibatch) < 1:
             raise ValueError('num_pairs and minibatch must be positive')
         self.sample_fn = sample_fn
         self.num_pairs, self.minibatch = int(num_pairs), int(minibatch)
         self.metric_kwargs = metric_kwargs
-        self.smoothed = smoothed
-        self.precision = _check_precision(precision, 'MSSSIMMonitor')
-        self._metric_obj = None
 
-    def register(self, trainer):
-        _check_smoothed(trainer, self.smoothed, 'MSSSIMMonitor')
-        self.trainer = trainer
-
-    def _metric(self, resolution, num_channels):
-        m = self._metric_obj
-        if m is None or (m.resolution, m.num_channels) != (resolution, num_channels):
-            from .metrics import MultiScaleSSIM
-            self._metric_obj = None                                      # a new stage: free the last one's buffers before allocating
-            self._metric_obj = MultiScaleSSIM(resolution, self.num_pairs, num_channels=num_channels, **self.metric_kwargs)
-        return self._metric_obj
-
-    def epoch(self, epoch_index):
-        tr = self.trainer
-        if tr.parallel is not None and tr.parallel.rank != 0:
-            return
-        resolution = 4 * 2 ** tr.G.depth
+    def evaluate(self, tick):
+        from .metrics import MultiScaleSSIM
+        resolution, channels = 4 * 2 ** self.trainer.G.depth, int(self.trainer.G.num_channels)
         if resolution < 16:
             return
-        metric = self._metric(resolution, int(tr.G.num_channels))
+        metric = self.cached((resolution, channels),
+                             lambda: MultiScaleSSIM(resolution, self.num_pairs, num_channels=channels, **self.metric_kwargs))
         metric.reset()
-        gen = _output_generator(tr, self.smoothed, self.precision)
+        gen = self.generator()
         for start in range(0, self.num_pairs, self.minibatch):
             n = min(self.minibatch, self.num_pairs - start)
             a = gen.forward(self.sample_fn(n).cuda())
             metric.feed(a, gen.forward(self.sample_fn(n).cuda()))
         res = metric.result()
-        tr.stats['msssim'] = dict(log_name='msssim', log_epoch_fields=['{val:.4f}'], val=res['msssim'])
-        tr.stats['msssim_std'] = dict(log_name='msssim_std', log_epoch_fields=['{val:.4f}'], val=res['std'])
-
-    def end(self, *args):
-        self.epoch(*args)
+        self.stat('msssim', res['msssim'], '{val:.4f}')
+        self.stat('msssim_std', res['std'], '{val:.4f}')
 
 
-class NNMonitor(Plugin):
+class NNMonitor(Evaluation):
     """Novelty check per tick (``metrics.NearestNeighbours``; the reference reports none): every ``nn_ticks`` ticks and at the end,
     ``num_samples`` images of ``G.forward(sample_fn(num_samples).cuda())`` -- of the smoothed generator when the trainer keeps one
-    (``smoothed`` as in ``OutputGenerator``) -- are searched for their ``k`` nearest training images in ``dataset`` (a
+    (``smoothed`` as in ``Evaluation``) -- are searched for their ``k`` nearest training images in ``dataset`` (a
     ``DeviceImageDataset``; the stack of the current growth stage is searched) by exact L2 distance over the 0..255 levels of the saved
     image.  Writes ``stats['nn_rms']``, the mean over the samples of the distance to the nearest training image as an RMS difference per
     byte in levels, and ``stats['nn_rms_min']``, the smallest of them -- the most suspicious sample: a value near 0 is a copy -- under the
@@ -492,12 +472,11 @@ class NNMonitor(Plugin):
     two passes, and the 64 generator passes are bounded by 64/3 measured train steps of 10.1 ms = 0.22 s; an evaluation is under 0.3 s,
     and under 1 % of a 3.3 s tick of 1 kimg (the rule of docs/experiments_swd.md) needs ticks >= 100 x 0.3 / 3.3 = 9: 10.
 
-    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
-    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
+    ``precision``: 'fp32' (default) or 'bf16', as in ``Evaluation``."""
 
     def __init__(self, dataset, sample_fn, num_samples=64, k=3, nn_ticks=10, postprocessors=(), smoothed=None, mirror=None,
                  drange=(-1, 1), precision='fp32'):
-        super(NNMonitor, self).__init__([(nn_ticks, 'epoch'), (1, 'end')])
+        super(NNMonitor, self).__init__(nn_ticks, smoothed, precision)
         if isinstance(k, bool) or int(k) != k or int(k) < 1:
             raise ValueError('k must be a positive integer, got %r' % (k,))
         if int(num_samples) != num_samples or int(num_samples) < int(k) + 1:
@@ -505,57 +484,32 @@ class NNMonitor(Plugin):
         self.dataset, self.sample_fn = dataset, sample_fn
         self.num_samples, self.k = int(num_samples), int(k)
         self.postprocessors = postprocessors
-        self.smoothed = smoothed
         self.mirror = bool(getattr(dataset, 'mirror_augment', False)) if mirror is None else bool(mirror)
         self.drange = drange
-        self.precision = _check_precision(precision, 'NNMonitor')
-        self._nn = None
 
-    def register(self, trainer):
-        _check_smoothed(trainer, self.smoothed, 'NNMonitor')
-        self.trainer = trainer
-
-    def _search(self):
-        if self._nn is None:
-            from .metrics import NearestNeighbours
-            self._nn = NearestNeighbours(self.dataset, k=self.k, mirror=self.mirror, drange=self.drange)
-        return self._nn
-
-    def epoch(self, epoch_index):
-        tr = self.trainer
-        if tr.parallel is not None and tr.parallel.rank != 0:
-            return
+    def evaluate(self, tick):
         import torch
-        nn = self._search()
-        samples = _output_generator(tr, self.smoothed, self.precision).forward(self.sample_fn(self.num_samples).cuda())
+        from .metrics import NearestNeighbours
+        from .utils import run_postprocessors
+        nn = self.cached('all stages', lambda: NearestNeighbours(self.dataset, k=self.k, mirror=self.mirror, drange=self.drange))
+        samples = self.generator().forward(self.sample_fn(self.num_samples).cuda())
         res = nn.search(samples)
         nearest = res['rms'][:, 0].numpy()                                 # fp64 on the host
-        tr.stats['nn_rms'] = dict(log_name='nn_rms', log_epoch_fields=_STAT_FMT, val=float(nearest.mean()))
-        tr.stats['nn_rms_min'] = dict(log_name='nn_rms_min', log_epoch_fields=_STAT_FMT, val=float(nearest.min()))
+        self.stat('nn_rms', float(nearest.mean()))
+        self.stat('nn_rms_min', float(nearest.min()))
         if not self.postprocessors:
             return
         rows = self.k + 1
         near = nn.neighbours({name: res[name][:rows] for name in ('index', 'mirrored')})          # [rows, k, C, r, r]
         shown = samples[:rows].to(near.device)
         batch = torch.cat([shown.unsqueeze(1), near], dim=1).reshape((rows * rows,) + tuple(shown.shape[1:]))
-        description = 'nn_%06d' % (tr.cur_nimg // 1000)
-        host = None
-        for proc in self.postprocessors:
-            if getattr(proc, 'accepts_device_tensors', False):
-                proc(batch, description)
-            else:
-                if host is None:
-                    host = batch.cpu().numpy()
-                proc(host, description)
-
-    def end(self, *args):
-        self.epoch(*args)
+        run_postprocessors(batch, 'nn_%06d' % (self.trainer.cur_nimg // 1000), self.postprocessors)
 
 
-class NDBMonitor(Plugin):
+class NDBMonitor(Evaluation):
     """Mode-coverage metric per tick (``metrics.NDB``: NDB/k and the JS divergence over k-means bins of the training images; the
     reference reports none): every ``ndb_ticks`` ticks and at the end, ``num_samples`` images of ``G.forward(sample_fn(n).cuda())``,
-    ``minibatch`` at a time -- of the smoothed generator when the trainer keeps one (``smoothed`` as in ``OutputGenerator``) -- are counted
+    ``minibatch`` at a time -- of the smoothed generator when the trainer keeps one (``smoothed`` as in ``Evaluation``) -- are counted
     per bin and compared with the proportions of held-out training images.  ``dataset``: a ``DeviceImageDataset``; the bins are
     fitted on ``level_stack()`` of the current growth stage and REFITTED when the stage's resolution differs from the fitted one (a
     fit happens once per stage, not per evaluation).  ``holdout=None`` holds out ``min(M // 5, num_samples)`` training images for the
@@ -572,25 +526,17 @@ class NDBMonitor(Plugin):
     rule of docs/experiments_swd.md) needs ticks >= 100 x 27.8 / 3.3 = 842: 850.  ``num_samples=2048, ndb_ticks=200`` costs the same
     share with a noisier histogram.
 
-    ``precision``: 'fp32' (default) evaluates the network itself, 'bf16' its ``sampling.Sampler`` (``_output_generator``); measured 0.84x the
-    fp32 pass's speed at the 1024x1024 stage (2.90 against 2.44 ms for 16 images), images 1 % relative L2 apart: docs/experiments_sampling.md."""
+    ``precision``: 'fp32' (default) or 'bf16', as in ``Evaluation``."""
 
     def __init__(self, dataset, sample_fn, num_samples=8192, minibatch=16, k=50, holdout=None, ndb_ticks=850, smoothed=None,
                  precision='fp32', **metric_kwargs):
-        super(NDBMonitor, self).__init__([(ndb_ticks, 'epoch'), (1, 'end')])
+        super(NDBMonitor, self).__init__(ndb_ticks, smoothed, precision)
         if int(num_samples) < 1 or int(minibatch) < 1:
             raise ValueError('num_samples and minibatch must be positive')
         self.dataset, self.sample_fn = dataset, sample_fn
         self.num_samples, self.minibatch, self.k = int(num_samples), int(minibatch), k
         self.holdout = min(len(dataset) // 5, self.num_samples) if holdout is None else holdout
-        self.smoothed = smoothed
-        self.precision = _check_precision(precision, 'NDBMonitor')
         self.metric_kwargs = metric_kwargs
-        self._metric_obj = None
-
-    def register(self, trainer):
-        _check_smoothed(trainer, self.smoothed, 'NDBMonitor')
-        self.trainer = trainer
 
     def _stage_resolution(self):
         stage = getattr(self.dataset, '_stage', None)
@@ -599,38 +545,25 @@ class NDBMonitor(Plugin):
         stack, depthdiff = stage()                                           # (no level is made for the answer)
         return int(stack.shape[-1]) >> depthdiff
 
-    def _metric(self):
-        """The metric, fitted on the data set's current stage."""
-        if self._metric_obj is None:
-            from .metrics import NDB
-            self._metric_obj = NDB(self.dataset, k=self.k, holdout=self.holdout, **self.metric_kwargs)
-        m = self._metric_obj
-        if m.resolution != self._stage_resolution():
-            m.fit()
-        return m
-
-    def epoch(self, epoch_index):
-        tr = self.trainer
-        if tr.parallel is not None and tr.parallel.rank != 0:
-            return
-        metric = self._metric()
+    def evaluate(self, tick):
+        from .metrics import NDB
+        metric = self.cached('all stages', lambda: NDB(self.dataset, k=self.k, holdout=self.holdout, **self.metric_kwargs))
+        if metric.resolution != self._stage_resolution():
+            metric.fit()                                                     # (once per stage: the bins are refitted, the object stays)
         metric.reset()
-        gen = _output_generator(tr, self.smoothed, self.precision)
+        gen = self.generator()
         for start in range(0, self.num_samples, self.minibatch):
             metric.feed(gen.forward(self.sample_fn(min(self.minibatch, self.num_samples - start)).cuda()))
         res = metric.result()
-        tr.stats['ndb'] = dict(log_name='ndb', log_epoch_fields=['{val:d}'], val=res['ndb'])
-        tr.stats['ndb_over_k'] = dict(log_name='ndb_over_k', log_epoch_fields=['{val:.3f}'], val=res['ndb_over_k'])
-        tr.stats['jsd'] = dict(log_name='jsd', log_epoch_fields=['{val:.4f}'], val=res['jsd'])
-
-    def end(self, *args):
-        self.epoch(*args)
+        self.stat('ndb', res['ndb'], '{val:d}')
+        self.stat('ndb_over_k', res['ndb_over_k'], '{val:.3f}')
+        self.stat('jsd', res['jsd'], '{val:.4f}')
 
 
-class ProjectionMonitor(Plugin):
+class ProjectionMonitor(Evaluation):
     """Recall-style measure per tick (``projection.Projector``; the reference reports none): every ``projection_ticks`` ticks and at the
     end, a FIXED set of ``num_images`` real images is projected into the latent space of the generator -- of the smoothed generator when
-    the trainer keeps one (``smoothed``: None = Gs if there is one, False = raw G, True = Gs or an error at ``register``) -- and the
+    the trainer keeps one (``smoothed`` as in ``Evaluation``) -- and the
     pyramid loss the search ends at says how well the generator can reproduce images it was not asked to produce.  It is defined for
     1-, 2-, 3- and 4-channel networks alike.
 
@@ -655,8 +588,7 @@ class ProjectionMonitor(Plugin):
 
     def __init__(self, source, num_images=8, steps=200, projection_ticks=30, smoothed=None, precision='fp32', samples_path=None,
                  drange=(-1, 1), resolution=512, postprocessors=(), **projector_kwargs):
-        super(ProjectionMonitor, self).__init__([(projection_ticks, 'epoch'), (1, 'end')])
-        _check_precision(precision, 'ProjectionMonitor')
+        super(ProjectionMonitor, self).__init__(projection_ticks, smoothed, precision)
         if precision != 'fp32':
             raise ValueError("ProjectionMonitor(precision=%r): the projection needs the generator's backward sweep, which the bf16 "
                              "sampler does not have; only 'fp32' is taken" % (precision,))
@@ -670,16 +602,11 @@ class ProjectionMonitor(Plugin):
             raise ValueError('ProjectionMonitor: %d targets from a dataset of %d images' % (num_images, len(source)))
         self.source = source
         self.num_images, self.steps = int(num_images), int(steps)
-        self.smoothed, self.precision = smoothed, precision
         self.samples_path, self.drange, self.resolution = samples_path, drange, resolution
         self.postprocessors = postprocessors
         self.projector_kwargs = projector_kwargs
         self._targets = {}               # resolution -> the fixed targets of that stage (real_batch_fn sources)
         self._projector = None           # (network it was made for, Projector)
-
-    def register(self, trainer):
-        _check_smoothed(trainer, self.smoothed, 'ProjectionMonitor')
-        self.trainer = trainer
 
     def targets(self, resolution):
         """The fixed targets at ``resolution``: the same images at every call."""
@@ -705,37 +632,24 @@ class ProjectionMonitor(Plugin):
             self._projector = (weakref.ref(net), Projector(net, steps=self.steps, **self.projector_kwargs))
         return self._projector[1]
 
-    def epoch(self, epoch_index):
-        tr = self.trainer
-        if tr.parallel is not None and tr.parallel.rank != 0:
-            return
+    def evaluate(self, tick):
         import torch
-        net = _output_generator(tr, self.smoothed, 'fp32')
+        from .utils import DeviceImageSaver, run_postprocessors
+        tr = self.trainer
+        net = self.generator()
         targets = self.targets(4 * 2 ** int(net.depth))
         res = self._projector_for(net).project(targets)
         loss = res.loss.double().cpu()                                       # the one host synchronisation of an evaluation
-        tr.stats['proj_loss'] = dict(log_name='proj_loss', log_epoch_fields=['{val:.5f}'], val=float(loss.mean()))
-        tr.stats['proj_loss_max'] = dict(log_name='proj_loss_max', log_epoch_fields=['{val:.5f}'], val=float(loss.max()))
+        self.stat('proj_loss', float(loss.mean()), '{val:.5f}')
+        self.stat('proj_loss_max', float(loss.max()), '{val:.5f}')
         if not self.postprocessors and self.samples_path is None:
             return
         batch = torch.stack([targets, res.images], dim=1).reshape((2 * targets.shape[0],) + tuple(targets.shape[1:]))
         if self.samples_path is not None:
-            from .utils import DeviceImageSaver
             saver = DeviceImageSaver(self.samples_path, self.drange, self.resolution)
             saver.output_file_format = 'proj_{}.png'
             saver(batch, tr.cur_nimg // 1000)
-        description = 'proj_%06d' % (tr.cur_nimg // 1000)
-        host = None
-        for proc in self.postprocessors:
-            if getattr(proc, 'accepts_device_tensors', False):
-                proc(batch, description)
-            else:
-                if host is None:
-                    host = batch.cpu().numpy()
-                proc(host, description)
-
-    def end(self, *args):
-        self.epoch(*args)
+        run_postprocessors(batch, 'proj_%06d' % (tr.cur_nimg // 1000), self.postprocessors)
 
 
 class LossMonitor(Plugin):
@@ -766,8 +680,7 @@ class LossMonitor(Plugin):
         self.trainer = trainer
         trainer.loss_monitor = self      # HealthMonitor looks here
         for name in self.names:
-            trainer.stats[name] = dict(log_name=name, log_epoch_fields=['{val:.4f}'], val=float('nan'), last=float('nan'),
-                                       epoch_mean=float('nan'))
+            _stat(trainer.stats, name, float('nan'), '{val:.4f}', last=float('nan'), epoch_mean=float('nan'))
 
     def iteration(self, i, *losses):
         if len(losses) < len(self.names):
@@ -779,16 +692,15 @@ class LossMonitor(Plugin):
         self.last = (epoch_index, res)
         for name in self.names:
             r = res[name]
-            self.trainer.stats[name] = dict(log_name=name, log_epoch_fields=['{val:.4f}'], val=r['mean'], last=r['last'],
-                                            epoch_mean=r['mean'], min=r['min'], max=r['max'], std=r['std'], count=r['count'],
-                                            nonfinite=r['nonfinite'], first_bad=r['first_bad'])
+            _stat(self.trainer.stats, name, r['mean'], '{val:.4f}', last=r['last'], epoch_mean=r['mean'], min=r['min'], max=r['max'],
+                  std=r['std'], count=r['count'], nonfinite=r['nonfinite'], first_bad=r['first_bad'])
 
     def end(self, *args):
         if not self.scalars.empty:                                       # (iterations since the last tick closed)
             self.epoch(*args)
 
 
-class HealthMonitor(Plugin):
+class HealthMonitor(Evaluation):
     """Numerical guard and per-layer norms of D and G (the reference has neither): every ``health_ticks`` ticks and at the end, after
     ``engine.wait_pending(net)``, ONE ``telemetry.SegmentStats.measure`` of each network's flat parameters and -- when its optimizer is a
     ``FusedAdam`` -- one of Adam's first moment (``FusedAdam.flat_moments``), segmented into the weight and the bias of every layer.  With a
@@ -806,15 +718,12 @@ class HealthMonitor(Plugin):
     (replicas are identical)."""
 
     def __init__(self, health_ticks=1, on_nonfinite='raise', per_layer=False):
-        super(HealthMonitor, self).__init__([(health_ticks, 'epoch'), (1, 'end')])
+        super(HealthMonitor, self).__init__(health_ticks)                # (it evaluates no generator: ``smoothed`` / ``precision`` stay unused)
         if on_nonfinite not in ('raise', 'warn'):
             raise ValueError("on_nonfinite must be 'raise' or 'warn', got %r" % (on_nonfinite,))
         self.on_nonfinite, self.per_layer = on_nonfinite, bool(per_layer)
         self._seg = {}                   # net name -> (flat buffer address, SegmentStats)
         self._table = []
-
-    def register(self, trainer):
-        self.trainer = trainer
 
     def report(self):
         return [dict(row) for row in self._table]
@@ -826,13 +735,11 @@ class HealthMonitor(Plugin):
             hit = self._seg[which] = (net._flat_param.data_ptr(), SegmentStats.for_network(net))
         return hit[1]
 
-    def epoch(self, epoch_index):
+    def evaluate(self, epoch_index):
         tr = self.trainer
-        if getattr(tr, 'parallel', None) is not None and tr.parallel.rank != 0:
-            return
         from . import engine
         from .telemetry import TrainingDiverged
-        fmt = ['{val:.4g}']
+        fmt = '{val:.4g}'
         table, problems = [], []
         for which, net, opt in (('D', tr.D, tr.optimizer_d), ('G', tr.G, tr.optimizer_g)):
             flat = getattr(net, '_flat_param', None)
@@ -846,10 +753,10 @@ class HealthMonitor(Plugin):
             g = seg.measure(moments[0]) if moments is not None else None
             w = w.cpu().numpy()
             g = g.cpu().numpy() if g is not None else None
-            tr.stats[which + '_wnorm'] = dict(log_name=which + '_wnorm', log_epoch_fields=fmt, val=math.sqrt(float(w[:, 1].sum())))
+            self.stat(which + '_wnorm', math.sqrt(float(w[:, 1].sum())), fmt)
             if g is not None:
-                tr.stats[which + '_gnorm'] = dict(log_name=which + '_gnorm', log_epoch_fields=fmt, val=math.sqrt(float(g[:, 1].sum())))
-                tr.stats[which + '_gmax'] = dict(log_name=which + '_gmax', log_epoch_fields=fmt, val=float(g[:, 2].max()))
+                self.stat(which + '_gnorm', math.sqrt(float(g[:, 1].sum())), fmt)
+                self.stat(which + '_gmax', float(g[:, 2].max()), fmt)
             bad = []
             for i, (name, (off, n)) in enumerate(zip(seg.names, seg.segments)):
                 row = dict(net=which, layer=name, offset=off, length=n, wnorm=math.sqrt(float(w[i, 1])), wmax=float(w[i, 2]),
@@ -860,8 +767,7 @@ class HealthMonitor(Plugin):
                 if self.per_layer:
                     for key in ('wnorm', 'gnorm'):
                         if row[key] is not None:
-                            stat = '%s_%s/%s' % (which, key, name)
-                            tr.stats[stat] = dict(log_name=stat, log_epoch_fields=fmt, val=row[key])
+                            self.stat('%s_%s/%s' % (which, key, name), row[key], fmt)
                 if row['w_nonfinite']:
                     bad.append('%s: %d of %d weights' % (name, row['w_nonfinite'], n))
                 if row['g_nonfinite']:
@@ -882,6 +788,3 @@ class HealthMonitor(Plugin):
             if self.on_nonfinite == 'raise':
                 raise TrainingDiverged(msg)
             warnings.warn(msg, RuntimeWarning)
-
-    def end(self, *args):
-        self.epoch(*args)

@@ -36,14 +36,6 @@ from . import engine, ops
 Projection = collections.namedtuple('Projection', 'z images loss history')
 
 
-def _live_layers(net, depth):
-    """(name, layer) of the conv layers that run at ``depth``, in evaluation order."""
-    out = [('block0.c1', net.block0.c1), ('block0.c2', net.block0.c2)]
-    for i in range(depth):
-        out += [('blocks.%d.c1' % i, net.blocks[i].c1), ('blocks.%d.c2' % i, net.blocks[i].c2)]
-    return out
-
-
 class Projector(object):
     """``Projector(net, steps=200, lr=0.1, betas=(0.9, 0.999), level_weights=None, seed=0)``: projection onto the images of a
     ``Generator`` (``G`` or ``GeneratorEMA.network()``) at ``net.depth`` / ``net.alpha`` as they are at the call.
@@ -71,7 +63,7 @@ class Projector(object):
             raise ValueError('Projector: %d image channels (1 .. %d)' % (net.num_channels, ops.PYR_MAX_C))
         if int(net.latent_size) % 4:
             raise ValueError('Projector: latent size %d is not a multiple of 4' % net.latent_size)
-        for name, lay in _live_layers(net, len(net.blocks)):
+        for name, lay in net.stage_convs(len(net.blocks)):
             first = name == 'block0.c1'
             if (lay.ksize, lay.pad) != ((4, 3) if first else (3, 1)):
                 raise ValueError('Projector: layer %s is %dx%d pad %d, not the %s conv the sweep is written for'
@@ -103,7 +95,7 @@ class Projector(object):
         key = (flat.data_ptr(), net._param_version, depth)
         if self._seen == key:
             return
-        layers = _live_layers(net, depth)
+        layers = net.stage_convs(depth)
         total = sum(lay.conv.weight.numel() for _, lay in layers)
         if self._wt_buf is None or self._wt_buf.device != flat.device or self._wt_buf.numel() != total:
             self._wt_buf = torch.empty(total, device=flat.device, dtype=torch.float32)
@@ -152,15 +144,13 @@ class Projector(object):
         C = int(net.num_channels)
         b0 = net.block0
         extra = None
+        t, pt = net.rgb_heads(depth, alpha)
         if depth == 0:
-            t = b0.toRGB
             gh = ops.torgb_bwd_data(g, t.conv.weight.data, N, C, 4, 4, t.c)
         else:
             H = ctx.recs[-1].H
-            t = ctx.recs[-1].blk.toRGB
             gh = ops.torgb_bwd_data(g, t.conv.weight.data, N, C, H, H, alpha * t.c)
-            if alpha < 1.0:
-                pt = net.blocks[depth - 2].toRGB if depth > 1 else b0.toRGB
+            if pt is not None:
                 extra = ops.torgb_bwd_data(g, pt.conv.weight.data, N, C, H // 2, H // 2, (1.0 - alpha) * pt.c, down=True)
         for rec in reversed(ctx.recs):
             c1, c2, H = rec.blk.c1, rec.blk.c2, rec.H

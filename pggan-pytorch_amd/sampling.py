@@ -99,11 +99,8 @@ def torgb_bf16(x, w, bias, N, C, H, W, scale, out_mul=1.0, prev=None, prev_w=Non
 
 # ------------------------------------------------------------------------------------ the sampler
 def _conv3_layers(net):
-    """(name, layer) of every 3x3 layer of a generator, in evaluation order."""
-    out = [('block0.c2', net.block0.c2)]
-    for i, blk in enumerate(net.blocks):
-        out += [('blocks.%d.c1' % i, blk.c1), ('blocks.%d.c2' % i, blk.c2)]
-    return out
+    """(name, layer) of every 3x3 layer of a generator, in evaluation order: all of its convs but block 0's c1."""
+    return net.stage_convs(len(net.blocks))[1:]
 
 
 class Sampler(object):
@@ -201,9 +198,8 @@ class Sampler(object):
             a2 = self._layer(a1, blk.c2, N, H)
             acts += [a1, a2]
             hprev, h = h, a2
-        t = net.blocks[depth - 1].toRGB if depth > 0 else b0.toRGB
-        if depth > 0 and alpha < 1.0:
-            pt = net.blocks[depth - 2].toRGB if depth > 1 else b0.toRGB
+        t, pt = net.rgb_heads(depth, alpha)
+        if pt is not None:
             img = torgb_bf16(h, t.conv.weight.data, t.conv.bias.data, N, C, H, H, t.c, out_mul=alpha, prev=hprev,
                              prev_w=pt.conv.weight.data, prev_bias=pt.conv.bias.data, prev_scale=pt.c, prev_mul=1.0 - alpha)
         else:
