@@ -1217,24 +1217,41 @@ def _assign_grads(net, layers, linear=False):
 REAL_THIRD_IN_STEP = True      # False: reference half of tests/test_e2e_gpu.py::test_three_pass_d_forward_matches_whole_batch_forward
 
 
-class Objective(_collections.namedtuple('Objective', 'kind drift penalty weight target')):
+class Objective(_collections.namedtuple('Objective', 'kind drift penalty weight target family', defaults=('pinned',))):
     """What the loss block of a step computes: ``kind`` a key of ``ops.GAN_KINDS``, ``drift`` the weight of the
-    s_r^2 term, ``penalty`` 'gp' | 'r1' | None with its ``weight`` (lambda / gamma) and, for 'gp', the ``target`` norm.  Immutable and
-    hashable: it is part of the key of a launch plan.  ``objective=None`` everywhere below is WGAN-GP on the original kernels."""
+    s_r^2 term, ``penalty`` 'gp' | 'r1' | None with its ``weight`` (lambda / gamma) and, for 'gp', the ``target`` norm.  ``family`` names
+    the kernels of the loss block: 'pinned' (csrc/gan_losses.hip, every rounding spelled out: what ``gan_losses`` builds) or 'original'
+    (``pg_d_loss`` / ``pg_g_loss`` of csrc/elementwise.hip, contraction left to the compiler: WGAN-GP as ``wgan_gp_D_loss`` /
+    ``wgan_gp_G_loss`` state it, kind 'wgan' with penalty 'gp' only).  The two are not bit-equal, so the family stays a property of the
+    objective.  Immutable and hashable: it is part of the key of a launch plan."""
     __slots__ = ()
+
+
+WGAN_GP = Objective('wgan', 0.001, 'gp', 10.0, 1.0, 'original')      # the defaults of wgan_gp_D_loss
+
+
+def _d_loss_block(obj, s, pen, N):
+    if obj.family == 'original':
+        return ops.d_loss(s, pen, N, obj.drift)                              # :48,55,62
+    return ops.gan_d_loss(s, pen, N, obj.kind, obj.drift)
+
+
+def _g_loss_block(obj, s):
+    return ops.g_loss(s) if obj.family == 'original' else ops.gan_g_loss(s, obj.kind)
 
 
 def _penalty_seed(obj, gimg, ss, N):
     if obj.penalty == 'r1':
         return ops.r1_seed(gimg, ss, obj.weight, 1.0 / N)
-    return ops.gp_seed(gimg, ss, obj.weight, obj.target, 1.0 / N)
+    return ops.gp_seed(gimg, ss, obj.weight, obj.target, 1.0 / N)        # :29-31
 
 
-def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_target, objective=None):
-    """Forward half of wgan_gp_D_loss (wgan_gp_loss.py:36-65): three D passes batched as
-    [real | fake | mixed], G without graph, and the first backward of the gradient penalty.
-    With an ``Objective`` (penalty 'gp' or 'r1') the same schedule with that objective's loss block and penalty seed; its fields stand in
-    for the three iwass arguments, which are not read.  R1 is the penalty at ``mix`` == 0, i.e. at the real images."""
+def d_loss_forward(D, G, real, latents, mix, objective):
+    """Forward half of a D loss (wgan_gp_loss.py:36-65): three D passes batched as [real | fake | mixed], G without graph, and the first
+    backward of the gradient penalty, with the loss block and the penalty seed of ``objective``.  R1 is the penalty at ``mix`` == 0, i.e.
+    at the real images; an objective without a penalty takes one pass over [real | fake] (``_d_plain_loss_forward``; ``mix`` is not read)."""
+    if objective.penalty is None:
+        return _d_plain_loss_forward(D, G, real, latents, objective)
     ops.require_gpu()
     real = _check_dev(real, 'real images')
     latents = _check_dev(latents, 'latents')
@@ -1293,17 +1310,11 @@ def d_loss_forward(D, G, real, latents, mix, iwass_lambda, iwass_epsilon, iwass_
     sub = ctx.slice(2 * N, 3 * N, 2, 3)
     gimg, adj = d_backward(D, sub, _ones(N, real.device), full=False, want_gimg=True, save_adjoints=True)  # :25-28
     ss = ops.row_sumsq(gimg)
-    if objective is None:
-        gp, u = ops.gp_seed(gimg, ss, iwass_lambda, iwass_target, 1.0 / N)    # :29-31
-    else:
-        gp, u = _penalty_seed(objective, gimg, ss, N)
+    gp, u = _penalty_seed(objective, gimg, ss, N)
     probe('D.gp_bwd_end')
     if fake_done is not None:
         _wait_event(torch.cuda.current_stream(torch._C._cuda_getDevice()), fake_done)
-    if objective is None:
-        d_cost, d_real_loss, d_fake_loss, gscore = ops.d_loss(s, gp, N, iwass_epsilon)   # :48,55,62
-    else:
-        d_cost, d_real_loss, d_fake_loss, gscore = ops.gan_d_loss(s, gp, N, objective.kind, objective.drift)
+    d_cost, d_real_loss, d_fake_loss, gscore = _d_loss_block(objective, s, gp, N)
     probe('D.loss_end')
     state = saved.DLossState(D=D, ctx=ctx, sub=sub, adj=adj, u=u, gscore=gscore, N=N, scores=s, gp=gp)
     if arena_st is not None:
@@ -1434,41 +1445,58 @@ def take_early_g(G, latents):
     return eg
 
 
-def d_loss_backward(state, scale=1.0):
-    """``D_cost.backward()`` (trainer.py:98): tangent pass + batched [real|fake|mixed] adjoint sweep."""
-    D, ctx, N = state.D, state.ctx, state.N
-    D._ensure_buffers()
-    tok = state.arena_use
-    if tok is not None:
-        if state.arena_st.owner() is not tok:     # (second line of defence: a retained loss back-propagated again after a later forward)
-            raise RuntimeError('the activations of this D loss were overwritten by a later D-loss forward on the same network')
-        tok.consumed = True
-    ops.zero_(D._flat_grad)
+def _backward(net, scale, sweep, probes, linear=False, may_skip_join=False):
+    """What ``backward()`` of every loss does around its ``sweep()`` (which returns the layers that received a gradient): the flat gradient
+    zeroed, nothing travelling early and nothing pending before it; behind it the deferred contributions flushed, the weight-gradient stream
+    joined, the gradients rescaled and assigned.  ``probes``: the tags of the sweep's end on the main and on the second stream."""
+    net._ensure_buffers()
+    ops.zero_(net._flat_grad)
     if scale != 1.0:
-        D._rt.grad_hook = None                   # the gradients are rescaled after the sweep: nothing may travel early
-    for lay in _live_conv_layers(D):             # (nothing of an aborted earlier step may ride along)
+        net._rt.grad_hook = None                 # the gradients are rescaled after the sweep: nothing may travel early
+    live = _live_conv_layers(net)
+    for lay in live:                             # (nothing of an aborted earlier step may ride along)
         lay._pending_wgrad = None
-    hvp = d_tangent_wgrad(D, state.sub, state.adj, state.u)
-    probe('D.tangent_end')
-    hvp.n_head = 2 * N                           # [real | fake] take the score gradients, the mixed third the injections only
-    d_backward(D, ctx, state.gscore[:2 * N], full=True, want_gimg=False, hvp=hvp)
-    for lay in _live_conv_layers(D):             # (a deferred tangent contribution that no launch of the sweep carried)
+    active = sweep()
+    for lay in live:                             # (a deferred tangent contribution that no launch of the sweep carried)
         _flush_wgrad(lay)
-    probe('D.sweep_end')
-    if PROBES is not None and ASYNC_WGRAD and D._flat_param.is_cuda:
+    probe(probes[0])
+    if PROBES is not None and ASYNC_WGRAD and net._flat_param.is_cuda:
         with torch.cuda.stream(_side_stream()):
-            probe('D.wgrad_end')
-    if not (D._rt.skip_join and scale == 1.0):
+            probe(probes[1])
+    if not (may_skip_join and net._rt.skip_join and scale == 1.0):
         _join_side()         # default: the gradients are complete for whatever the caller does next on this stream
     # (Trainer sets skip_join when the whole D update follows on the second stream, in order behind the weight
     #  gradients: the main stream then goes straight on to the G step instead of idling under the last, largest
     #  weight-gradient launches of the 1024^2 layers)
     if scale != 1.0:
-        ops.axpby_mask(D._flat_grad, a=scale, out=D._flat_grad)
-    _assign_grads(D, d_active_params(D, ctx.depth, ctx.alpha), linear=True)
+        ops.axpby_mask(net._flat_grad, a=scale, out=net._flat_grad)
+    _assign_grads(net, active, linear=linear)
+    return active
 
 
-def d_plain_loss_forward(D, G, real, latents, objective):
+def d_loss_backward(state, scale=1.0):
+    """``D_cost.backward()`` (trainer.py:98): tangent pass + batched [real|fake|mixed] adjoint sweep; for a state without a penalty
+    (``_d_plain_loss_forward``: no ``sub`` / ``adj`` / ``u``) the adjoint sweep over [real | fake] alone."""
+    D, ctx, N = state.D, state.ctx, state.N
+    tok = state.arena_use
+    if tok is not None:
+        if state.arena_st.owner() is not tok:     # (second line of defence: a retained loss back-propagated again after a later forward)
+            raise RuntimeError('the activations of this D loss were overwritten by a later D-loss forward on the same network')
+        tok.consumed = True
+
+    def sweep():
+        if state.sub is None:
+            d_backward(D, ctx, state.gscore, full=True, want_gimg=False)
+        else:
+            hvp = d_tangent_wgrad(D, state.sub, state.adj, state.u)
+            probe('D.tangent_end')
+            hvp.n_head = 2 * N                   # [real | fake] take the score gradients, the mixed third the injections only
+            d_backward(D, ctx, state.gscore[:2 * N], full=True, want_gimg=False, hvp=hvp)
+        return d_active_params(D, ctx.depth, ctx.alpha)
+    _backward(D, scale, sweep, ('D.sweep_end', 'D.wgrad_end'), linear=True, may_skip_join=True)
+
+
+def _d_plain_loss_forward(D, G, real, latents, objective):
     """The D step of an objective without a penalty: ONE whole-batch pass over [real | fake], then the loss block.  No mixed third, no
     first backward, no tangent pass."""
     ops.require_gpu()
@@ -1480,31 +1508,12 @@ def d_plain_loss_forward(D, G, real, latents, objective):
     ops.axpby_mask(real, a=1.0, out=x2[:N])
     d_step_generator(D, G, latents, x2[N:])
     s, ctx = d_forward(D, x2, groups=2)
-    d_cost, d_real_loss, d_fake_loss, gscore = ops.gan_d_loss(s, None, N, objective.kind, objective.drift)
+    d_cost, d_real_loss, d_fake_loss, gscore = _d_loss_block(objective, s, None, N)
     return d_cost, d_real_loss, d_fake_loss, saved.DLossState(D=D, ctx=ctx, gscore=gscore, N=N, scores=s)
 
 
-def d_plain_loss_backward(state, scale=1.0):
-    """``d_cost.backward()`` of ``d_plain_loss_forward``: the adjoint sweep over [real | fake] alone, then ``d_loss_backward``'s tail."""
-    D, ctx = state.D, state.ctx
-    D._ensure_buffers()
-    ops.zero_(D._flat_grad)
-    if scale != 1.0:
-        D._rt.grad_hook = None
-    for lay in _live_conv_layers(D):
-        lay._pending_wgrad = None
-    d_backward(D, ctx, state.gscore, full=True, want_gimg=False)
-    for lay in _live_conv_layers(D):
-        _flush_wgrad(lay)
-    if not (D._rt.skip_join and scale == 1.0):
-        _join_side()
-    if scale != 1.0:
-        ops.axpby_mask(D._flat_grad, a=scale, out=D._flat_grad)
-    _assign_grads(D, d_active_params(D, ctx.depth, ctx.alpha), linear=True)
-
-
-def g_loss_forward(G, D, latents, objective=None):
-    """wgan_gp_G_loss (wgan_gp_loss.py:68-74); with an ``Objective`` its generator term in place of -s."""
+def g_loss_forward(G, D, latents, objective):
+    """wgan_gp_G_loss (wgan_gp_loss.py:68-74) with the generator term of ``objective`` (-s for the 'wgan' kind)."""
     ops.require_gpu()
     latents = _check_dev(latents, 'latents')
     D._sync_version()
@@ -1517,7 +1526,7 @@ def g_loss_forward(G, D, latents, objective=None):
         fake, gctx = generator_forward(G, latents, save=True)
     probe('G.g_fwd_end')
     s, dctx = d_forward(D, fake, 1, keep_input=False)
-    g_cost, gscore = ops.g_loss(s) if objective is None else ops.gan_g_loss(s, objective.kind)
+    g_cost, gscore = _g_loss_block(objective, s)
     probe('G.d_fwd_end')
     return g_cost, saved.GLossState(G=G, D=D, gctx=gctx, dctx=dctx, gscore=gscore)
 
@@ -1526,19 +1535,9 @@ def g_loss_backward(state, scale=1.0):
     """``G_cost.backward()`` (trainer.py:111).  D's weight gradients, which the reference computes here
     and throws away at its next D.zero_grad(), are not computed."""
     G, D = state.G, state.D
-    G._ensure_buffers()
-    ops.zero_(G._flat_grad)
-    if scale != 1.0:
-        G._rt.grad_hook = None
-    gimg, _ = d_backward(D, state.dctx, state.gscore, full=False, want_gimg=True)
-    probe('G.d_bwd_end')
-    active = generator_backward(G, state.gctx, gimg)
-    probe('G.g_bwd_end')
-    if PROBES is not None and ASYNC_WGRAD and G._flat_param.is_cuda:
-        with torch.cuda.stream(_side_stream()):
-            probe('G.wgrad_end')
-    _join_side()
-    if scale != 1.0:
-        ops.axpby_mask(G._flat_grad, a=scale, out=G._flat_grad)
-    _assign_grads(G, active)
-    state.active_g = active
+
+    def sweep():
+        gimg, _ = d_backward(D, state.dctx, state.gscore, full=False, want_gimg=True)
+        probe('G.d_bwd_end')
+        return generator_backward(G, state.gctx, gimg)
+    state.active_g = _backward(G, scale, sweep, ('G.g_bwd_end', 'G.wgrad_end'))

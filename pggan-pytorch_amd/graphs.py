@@ -33,10 +33,10 @@ def clear():
     ops.release_capture_workspaces()          # the capture streams are gone with the graphs
 
 
-def d_step(D, G, real, latents, mix, lam, eps, target, objective=None):
+def d_step(D, G, real, latents, mix, objective):
     """Graphed ``d_loss_forward`` + ``d_loss_backward``.  Returns (d_cost, d_real_loss, d_fake_loss).  ``objective`` (engine.Objective with a
-    penalty, or None: WGAN-GP) is part of the graph's key."""
-    key = ('D', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(D.depth), tuple(real.shape), tuple(latents.shape), float(lam), float(eps), float(target), objective)
+    penalty) is part of the graph's key."""
+    key = ('D', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(D.depth), tuple(real.shape), tuple(latents.shape), objective)
     g = _CACHE.get(key)
     if g is None:
         g = _CACHE[key] = _Graphed()
@@ -45,7 +45,7 @@ def d_step(D, G, real, latents, mix, lam, eps, target, objective=None):
         dst.copy_(src)
     if g.graph is None:
         def body():
-            c, rl, fl, state = engine.d_loss_forward(D, G, g.static_in[0], g.static_in[1], g.static_in[2], lam, eps, target, objective)
+            c, rl, fl, state = engine.d_loss_forward(D, G, g.static_in[0], g.static_in[1], g.static_in[2], objective)
             engine.d_loss_backward(state)
             return c, rl, fl
         if g.warm < 2:                       # eager warm-up (sets kernel attributes, fills caches, allocator pools)
@@ -69,7 +69,7 @@ def d_step(D, G, real, latents, mix, lam, eps, target, objective=None):
     return tuple(t.clone() for t in g.static_out)
 
 
-def g_step(G, D, latents, objective=None):
+def g_step(G, D, latents, objective):
     """Graphed ``g_loss_forward`` + ``g_loss_backward``.  Returns g_cost.  ``objective``: as in ``d_step``."""
     key = ('G', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(G.depth), tuple(latents.shape), objective)
     g = _CACHE.get(key)

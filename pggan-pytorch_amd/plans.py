@@ -150,11 +150,13 @@ def _replay(plan):
     STATS['replayed'] += 1
 
 
+def _key(step, D, G, stage, variant):       # -> (stage part, variant part); the variants of a stage (with / without the early generator pass, its objectives) live side by side
+    return (step, D._flat_param.data_ptr(), G._flat_param.data_ptr()) + stage, variant
+
+
 def _new_plan(key):
-    """A plan pins one step's worth of activations: when a network pair moves to another growth stage / minibatch, the plans of
-    the stage it left are dropped (one D plan and one G plan per network pair at any time)."""
-    n = 9 if key[0] == 'D' else 7           # what names the stage in a key; behind it: the variants of one stage, the objective last
-    for k in [k for k in _CACHE if k[:3] == key[:3] and k[:n] != key[:n]]:      # (the with / without early-generator-pass variants of a stage live side by side, and so do its objectives)
+    """A plan pins one step's worth of activations: when a network pair moves to another growth stage / minibatch, the plans of the stage it left go."""
+    for k in [k for k in _CACHE if k[0][:3] == key[0][:3] and k[0] != key[0]]:     # (same step and network pair, another stage)
         del _CACHE[k]
     while len(_CACHE) >= MAX_PLANS:
         _CACHE.popitem(last=False)          # least recently used
@@ -197,9 +199,8 @@ def _dp_replayed(g, ex):
         ex.dp.stats['bytes'] += nbytes
 
 
-def d_step(D, G, real, latents, mix, lam, eps, target, objective=None):
-    """Plan-replayed ``d_loss_forward`` + ``d_loss_backward``.  Returns (d_cost, d_real_loss, d_fake_loss).  ``objective``
-    (engine.Objective with a penalty, or None: WGAN-GP) is the last element of the plan's key: two objectives never share a plan."""
+def d_step(D, G, real, latents, mix, objective):
+    """Plan-replayed ``d_loss_forward`` + ``d_loss_backward`` of ``objective`` (with a penalty).  Returns (d_cost, d_real_loss, d_fake_loss)."""
     _prologue(D, G)
     dp_tag, ex = _dp_tag(D)
     # the G step's generator pass rides in this step on the second stream (engine.request_early_g): its latents are a fourth static input
@@ -207,8 +208,7 @@ def d_step(D, G, real, latents, mix, lam, eps, target, objective=None):
     if req is not None and engine.early_g_mode(req[0].depth) is None:
         req = D._rt.early_g_request = None
     zg = engine._check_dev(req[1], 'latents') if req is not None else None
-    key = ('D', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(D.depth), tuple(real.shape), tuple(latents.shape), float(lam), float(eps), float(target), dp_tag,
-           (req[0]._flat_param.data_ptr(), tuple(zg.shape)) if req is not None else 0, objective)
+    key = _key('D', D, G, (int(D.depth), tuple(real.shape), tuple(latents.shape)), (dp_tag, (req[0]._flat_param.data_ptr(), tuple(zg.shape)) if req is not None else 0, objective))
     g = _CACHE.get(key)
     if g is None:
         g = _new_plan(key)
@@ -228,7 +228,7 @@ def d_step(D, G, real, latents, mix, lam, eps, target, objective=None):
         caller = D._rt.skip_join
         D._rt.skip_join = True
         try:
-            c, rl, fl, state = engine.d_loss_forward(D, G, g.static_in[0], g.static_in[1], g.static_in[2], lam, eps, target, objective)
+            c, rl, fl, state = engine.d_loss_forward(D, G, g.static_in[0], g.static_in[1], g.static_in[2], objective)
             engine.d_loss_backward(state)
         finally:
             D._rt.skip_join = caller
@@ -271,7 +271,7 @@ def d_step(D, G, real, latents, mix, lam, eps, target, objective=None):
     return tuple(t.clone() for t in g.static_out)
 
 
-def g_step(G, D, latents, objective=None):
+def g_step(G, D, latents, objective):
     """Plan-replayed ``g_loss_forward`` + ``g_loss_backward``.  Returns g_cost.  ``objective``: as in ``d_step``."""
     dp_tag, ex = _dp_tag(G)
     # the generator pass may already be through (engine.EarlyG, left by the D step for exactly these latents): a plan of its own, whose
@@ -280,7 +280,7 @@ def g_step(G, D, latents, objective=None):
     if eg is not None and not (eg.latents is latents and eg.stamp == (G._param_version, int(G.depth), float(G.alpha))):
         eg = G._rt.early_fwd = None
         engine.EARLY_G_STATS['dropped'] += 1
-    key = ('G', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(G.depth), tuple(latents.shape), dp_tag, eg is not None, objective)
+    key = _key('G', D, G, (int(G.depth), tuple(latents.shape), dp_tag, eg is not None), (objective,))
     g = _CACHE.get(key)
     if g is None:
         g = _new_plan(key)

@@ -155,7 +155,8 @@ class Hvp(_Record):
 
 class DLossState(_Record):
     """Writer: engine.d_loss_forward; reader: d_loss_backward (and diagnostics: tools/, tests/test_fp64_adjudicator.py).
-    engine.d_plain_loss_forward (an objective without a penalty) writes D, N, ctx over [real | fake], gscore and scores only."""
+    For an objective without a penalty (engine._d_plain_loss_forward) D, N, ctx over [real | fake], gscore and scores only: the reader then
+    skips the tangent pass."""
     LAYOUT = {
         'D': None,          # the discriminator
         'N': None,          # minibatch size

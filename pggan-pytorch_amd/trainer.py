@@ -267,7 +267,7 @@ class Trainer(object):
         if os.environ.get('PGGAN_OVERLAP_D_UPDATE', '1') == '0':
             return False
         return (self.G_loss is wgan_gp_loss.wgan_gp_G_loss and hasattr(self.D, '_flat_param')
-                and not wgan_gp_loss._graphs_on(self.D) and not wgan_gp_loss._graphs_on(self.G))
+                and 'graph' not in (wgan_gp_loss._replay_mode(self.D), wgan_gp_loss._replay_mode(self.G)))
 
     def _early_g_ok(self):
         """May the generator pass that opens the G step run inside the D step (second stream, engine.request_early_g)?  The product's G loss
@@ -275,7 +275,7 @@ class Trainer(object):
         from . import wgan_gp_loss
         return (engine.early_g_mode(self.G.depth) is not None and engine.ASYNC_WGRAD and self.G_loss is wgan_gp_loss.wgan_gp_G_loss
                 and hasattr(self.D, '_flat_param') and hasattr(self.G, '_flat_param') and self.G._flat_param.is_cuda
-                and not wgan_gp_loss._graphs_on(self.D) and not wgan_gp_loss._graphs_on(self.G))
+                and 'graph' not in (wgan_gp_loss._replay_mode(self.D), wgan_gp_loss._replay_mode(self.G)))
 
     def train(self):
         """One iteration: ``D_training_repeats`` discriminator updates, then one generator update

@@ -1,4 +1,4 @@
-"""WGAN-GP losses with the reference's call signatures (/root/reference/wgan_gp_loss.py).
+"""WGAN-GP losses with the reference's call signatures (its wgan_gp_loss.py).
 
 ``wgan_gp_D_loss(D, G, real, latents, ...) -> (D_cost, D_real_loss, D_fake_loss)`` and
 ``wgan_gp_G_loss(G, D, latents) -> G_cost`` return device tensors; ``D_cost.backward()`` /
@@ -7,12 +7,14 @@ backward schedules of ``engine`` and leave the gradients in ``param.grad`` (view
 network's flat gradient buffer), exactly where ``optimizer.step()`` expects them."""
 import torch
 
-from . import engine
+from . import engine, graphs, ops, plans
 
 # wgan_gp_loss.py:4-5 keeps module-global scratch; the only state kept here is the injectable RNG.
 mixing_factors = None
 _seed = None                # [seed, draws so far, torch seed it came from] of the mixing-factor stream; None: seeded from torch's RNG at first use
 _use_graphs = 'auto'        # 'auto': launch plans; True: hipGraphs everywhere; False: eager
+_use_plans = True           # set through ``enable_plans``; tests/test_e2e_gpu.py and tests/test_collective_gpu.py flip it without dropping the recorded plans
+_zero_mix = {}              # (n, device) -> [n, 1] zeros: the mixing factors of R1 (read only)
 
 
 def enable_graphs(flag=True):
@@ -26,7 +28,6 @@ def enable_graphs(flag=True):
     global _use_graphs
     _use_graphs = 'auto' if flag == 'auto' else bool(flag)
     if not flag:
-        from . import graphs, plans
         graphs.clear()
         plans.clear()
 
@@ -38,11 +39,7 @@ def enable_plans(flag=True):
     global _use_plans
     _use_plans = bool(flag)
     if not flag:
-        from . import plans
         plans.clear()
-
-
-_use_plans = True           # set through ``enable_plans``; tests/test_e2e_gpu.py and tests/test_collective_gpu.py flip it without dropping the recorded plans
 
 
 def _replay_mode(net):
@@ -52,16 +49,6 @@ def _replay_mode(net):
     if _use_graphs is True:
         return 'graph'
     return 'plan' if _use_plans else None
-
-
-def _exchange_instrumented(net):
-    """bench.py times every collective with a fresh HIP event pair (``DataParallel.record_events``): those steps are issued eagerly."""
-    ex = net._rt.grad_exchange if net._rt.grad_hook is not None else None
-    return ex is not None and ex.dp.record_events
-
-
-def _graphs_on(net):
-    return _replay_mode(net) == 'graph'
 
 
 def set_mixing_factors(m):
@@ -86,7 +73,6 @@ def _draw_mixing_factors(n, device):
         _seed = [ts, 0, ts]
     mix = torch.empty((n, 1), device=device, dtype=torch.float32)
     if mix.is_cuda:
-        from . import ops
         ops.uniform_(mix, _seed[0], _seed[1])
     else:                                                                # (host emulation in the CPU test-suite only)
         mix.copy_(torch.rand((n, 1), generator=torch.Generator().manual_seed((_seed[0] * 1000003 + _seed[1]) % (1 << 63))))
@@ -132,58 +118,72 @@ def _replayed_backward(net):
             engine._join_side()
         net._rt.plan_unjoined = False        # joined, or the caller took over (its update is ordered behind the weight-gradient stream)
         if scale != 1.0:
-            from . import ops
             ops.axpby_mask(net._flat_grad, a=scale, out=net._flat_grad)
     return fn
 
 
-def wgan_gp_D_loss(D, G, real_images_in, fake_latents_in,
-                   iwass_lambda=10.0,
-                   iwass_epsilon=0.001,
-                   iwass_target=1.0,
-                   return_all=True):
-    """reference wgan_gp_loss.py:36-65."""
+def _mixing_factors(penalty, n, device):
+    """[n, 1] on the device for a step with a penalty.  'r1' (the penalty at the real images): cached zeros -- neither the injected tensor
+    nor the stream of draws is touched; 'gp': the injected tensor, consumed, or else a draw (:15-17, device RNG)."""
     global mixing_factors
+    if penalty == 'r1':
+        key = (n, str(device))
+        if key not in _zero_mix:
+            _zero_mix[key] = torch.zeros((n, 1), device=device, dtype=torch.float32)
+        return _zero_mix[key]
+    if mixing_factors is None:
+        return _draw_mixing_factors(n, device)
+    mix, mixing_factors = mixing_factors.to(device=device, dtype=torch.float32).reshape(n, 1), None
+    return mix
+
+
+def _step_mode(net, D, x):
+    """'graph' | 'plan' | None (eager) for a step of ``net`` on the input ``x``: THE condition under which a step may be replayed."""
+    if not (float(net.alpha) >= 1.0 and x.is_cuda and hasattr(net, '_flat_param') and D._rt.global_stddev is None):
+        return None                                                      # (exact-global stddev: collectives inside the step -> eager)
+    mode = _replay_mode(net)
+    ex = net._rt.grad_exchange if net._rt.grad_hook is not None else None
+    # (bench.py times every collective with a fresh HIP event pair, ``DataParallel.record_events``: those steps are issued eagerly)
+    return None if (mode == 'plan' and ex is not None and ex.dp.record_events) else mode
+
+
+def _d_loss(objective, D, G, real_images_in, fake_latents_in, return_all):
+    """reference wgan_gp_loss.py:36-65 with the loss block and penalty of ``objective`` (engine.Objective)."""
     D.zero_grad()                                                        # :42
     G.zero_grad()                                                        # :43
-    n = real_images_in.size(0)
-    if mixing_factors is not None:
-        mix = mixing_factors.to(device=real_images_in.device, dtype=torch.float32).reshape(n, 1)
-        mixing_factors = None
-    else:                                                                # :15-17 (device RNG)
-        mix = _draw_mixing_factors(n, real_images_in.device)
-    mode = _replay_mode(D) if (float(D.alpha) >= 1.0 and real_images_in.is_cuda and hasattr(D, '_flat_param')
-                               and D._rt.global_stddev is None) else None      # (exact-global stddev: collectives inside the step -> eager)
-    if mode == 'plan' and _exchange_instrumented(D):
-        mode = None
-    if mode is not None:
-        from . import graphs, plans
-        real_c = engine._check_dev(real_images_in, 'real images')
-        z_c = engine._check_dev(fake_latents_in, 'latents')
-        d_cost, d_real_loss, d_fake_loss = (graphs if mode == 'graph' else plans).d_step(D, G, real_c, z_c, mix.contiguous(), iwass_lambda,
-                                                                                         iwass_epsilon, iwass_target)
+    mix = mode = None                                                    # no penalty: one pass over [real | fake], eager in every mode
+    if objective.penalty is not None:
+        mix = _mixing_factors(objective.penalty, real_images_in.size(0), real_images_in.device)
+        mode = _step_mode(D, D, real_images_in)
+    if mode is None:
+        d_cost, d_real_loss, d_fake_loss, state = engine.d_loss_forward(D, G, real_images_in, fake_latents_in, mix, objective)
+        d_cost = LossTensor.wrap(d_cost, lambda scale: engine.d_loss_backward(state, scale))
+    else:
+        d_cost, d_real_loss, d_fake_loss = (graphs if mode == 'graph' else plans).d_step(
+            D, G, engine._check_dev(real_images_in, 'real images'), engine._check_dev(fake_latents_in, 'latents'), mix.contiguous(), objective)
         d_cost = LossTensor.wrap(d_cost, _replayed_backward(D))  # gradients are already in param.grad
-        if return_all:
-            return d_cost, d_real_loss, d_fake_loss
-        return d_cost
-    d_cost, d_real_loss, d_fake_loss, state = engine.d_loss_forward(
-        D, G, real_images_in, fake_latents_in, mix, iwass_lambda, iwass_epsilon, iwass_target)
-    d_cost = LossTensor.wrap(d_cost, lambda scale: engine.d_loss_backward(state, scale))
-    if return_all:
-        return d_cost, d_real_loss, d_fake_loss
-    return d_cost
+    return (d_cost, d_real_loss, d_fake_loss) if return_all else d_cost
+
+
+def _g_loss(objective, G, D, fake_latents_in):
+    """reference wgan_gp_loss.py:68-74 with the generator term of ``objective``."""
+    G.zero_grad()                                                        # :69
+    mode = _step_mode(G, D, fake_latents_in)
+    if mode is None:
+        g_cost, state = engine.g_loss_forward(G, D, fake_latents_in, objective)
+        return LossTensor.wrap(g_cost, lambda scale: engine.g_loss_backward(state, scale))
+    g_cost = (graphs if mode == 'graph' else plans).g_step(G, D, engine._check_dev(fake_latents_in, 'latents'), objective)
+    return LossTensor.wrap(g_cost, _replayed_backward(G))
+
+
+def wgan_gp_D_loss(D, G, real_images_in, fake_latents_in, iwass_lambda=10.0, iwass_epsilon=0.001, iwass_target=1.0, return_all=True):
+    """reference wgan_gp_loss.py:36-65, on the original loss kernels (the 'original' family of engine.Objective)."""
+    obj = engine.WGAN_GP                                                 # (the default arguments build nothing)
+    if iwass_lambda != obj.weight or iwass_epsilon != obj.drift or iwass_target != obj.target:
+        obj = obj._replace(drift=iwass_epsilon, weight=iwass_lambda, target=iwass_target)
+    return _d_loss(obj, D, G, real_images_in, fake_latents_in, return_all)
 
 
 def wgan_gp_G_loss(G, D, fake_latents_in):
     """reference wgan_gp_loss.py:68-74."""
-    G.zero_grad()                                                        # :69
-    mode = _replay_mode(G) if (float(G.alpha) >= 1.0 and fake_latents_in.is_cuda and hasattr(G, '_flat_param')
-                               and D._rt.global_stddev is None) else None
-    if mode == 'plan' and _exchange_instrumented(G):
-        mode = None
-    if mode is not None:
-        from . import graphs, plans
-        g_cost = (graphs if mode == 'graph' else plans).g_step(G, D, engine._check_dev(fake_latents_in, 'latents'))
-        return LossTensor.wrap(g_cost, _replayed_backward(G))
-    g_cost, state = engine.g_loss_forward(G, D, fake_latents_in)
-    return LossTensor.wrap(g_cost, lambda scale: engine.g_loss_backward(state, scale))
+    return _g_loss(engine.WGAN_GP, G, D, fake_latents_in)

@@ -739,11 +739,11 @@ def test_early_g_forward_is_the_same_pass(mode, deterministic_forward, monkeypat
         stats = dict(eng.EARLY_G_STATS)
         if early:
             eng.request_early_g(D, G, z_g)
-        c, _, _, st = eng.d_loss_forward(D, G, real, z_d, mix, 10.0, 0.001, 1.0)
+        c, _, _, st = eng.d_loss_forward(D, G, real, z_d, mix, eng.WGAN_GP)
         eng.d_loss_backward(st)
         gd = D._flat_grad.clone()
         zz = z_g.clone() if other_latents else z_g
-        gc, gst = eng.g_loss_forward(G, D, zz)
+        gc, gst = eng.g_loss_forward(G, D, zz, eng.WGAN_GP)
         eng.g_loss_backward(gst)
         torch.cuda.synchronize()
         return float(c), gd, float(gc), G._flat_grad.clone(), {k: eng.EARLY_G_STATS[k] - stats[k] for k in stats}

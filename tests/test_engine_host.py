@@ -513,9 +513,9 @@ def test_saved_records_are_closed_and_every_tensor_slot_has_a_layout(emu, monkey
     states = []
     for (G, D), res, latent in ((_pn_fade_in_nets(), 16, 32), ((G2, D2), 32, meta['cfg']['latent_size'])):
         real, z_d, z_g, mix = synthetic(7, 2, 3, res, latent)
-        _, _, _, st = pg.engine.d_loss_forward(D, G, real, z_d, mix.view(-1), 10.0, 0.001, 1.0)
+        _, _, _, st = pg.engine.d_loss_forward(D, G, real, z_d, mix.view(-1), pg.engine.WGAN_GP)
         pg.engine.d_loss_backward(st)
-        _, gst = pg.engine.g_loss_forward(G, D, z_g)
+        _, gst = pg.engine.g_loss_forward(G, D, z_g, pg.engine.WGAN_GP)
         pg.engine.g_loss_backward(gst)
         states += [st, gst]
     assert len(hvps) == 2 and hvps[0].injs is not None and hvps[0].n_head == 4

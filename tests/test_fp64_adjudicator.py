@@ -98,7 +98,7 @@ def _run(oracle, G, D, gp, dp, cfg, real, z_d, z_g, mix, depth, alpha, what):
     n = real.shape[0]
     gp64, dp64 = _double(gp), _double(dp)
     # ---- D step (wgan_gp_D_loss + backward), on the fake / interpolated images and the activation branches of the HIP pass
-    d_cost, _, _, state = eng.d_loss_forward(D, G, real.to(DEV), z_d.to(DEV), mix.to(DEV), 10.0, 0.001, 1.0)
+    d_cost, _, _, state = eng.d_loss_forward(D, G, real.to(DEV), z_d.to(DEV), mix.to(DEV), eng.WGAN_GP)
     ctx = state.ctx
     fake, mixed = ctx.x[n:2 * n].cpu(), ctx.x[2 * n:].cpu()
     signs = _d_signs(ctx, 0, n, True) + _d_signs(ctx, n, 2 * n, True) + _d_signs(ctx, 2 * n, 3 * n, True)
@@ -114,7 +114,7 @@ def _run(oracle, G, D, gp, dp, cfg, real, z_d, z_g, mix, depth, alpha, what):
     assert abs(float(d_cost) - float(r64['D_cost'])) <= 3 * abs(float(r32['D_cost']) - float(r64['D_cost'])) + 2e-6 * max(1.0, abs(float(r64['D_cost'])))
     _adjudicate(mine_d, r32['grads'], r64['grads'], what + ' D step')
     # ---- G step (wgan_gp_G_loss + backward) on the branches of the HIP pass (G's and D's)
-    g_cost, gstate = eng.g_loss_forward(G, D, z_g.to(DEV))
+    g_cost, gstate = eng.g_loss_forward(G, D, z_g.to(DEV), eng.WGAN_GP)
     signs = _g_signs(gstate.gctx) + _d_signs(gstate.dctx, 0, n, True)
     eng.g_loss_backward(gstate)
     mine_g = reference_grads(G)

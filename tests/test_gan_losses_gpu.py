@@ -196,6 +196,40 @@ def test_plain_schedule_matches_wgan_gp_with_lambda_zero(deterministic_forward):
     assert_same_contributions(mine, twin, tol=1e-2, total=2e-4)
 
 
+# ---- one path for every objective: which loss block a step launches -------------------------------------------------------------------
+@pytest.mark.parametrize('case,want', [('default', ['pg_row_sumsq', 'pg_gp_seed', 'pg_d_loss', 'pg_g_loss']),
+                                       ('lambda5', ['pg_row_sumsq', 'pg_gp_seed', 'pg_d_loss', 'pg_g_loss']),
+                                       ('wgan5', ['pg_row_sumsq', 'pg_gp_seed', 'pg_gan_d_loss', 'pg_gan_g_loss']),
+                                       ('logistic_r1', ['pg_row_sumsq', 'pg_r1_seed', 'pg_gan_d_loss', 'pg_gan_g_loss']),
+                                       ('hinge_plain', ['pg_gan_d_loss', 'pg_gan_g_loss'])])
+def test_each_objective_launches_the_loss_block_of_its_family(deterministic_forward, case, want):
+    """The device twin of the host test of this name: the C-ABI calls of one eager D step + G step (tiny16c1, depth 2, minibatch 4)."""
+    from test_gan_losses_host import FAMILY_CASES
+    meta, G, D, _, _, cfg = _fixture_nets('tiny16c1')
+    G.depth = D.depth = 2
+    G.alpha = D.alpha = 1.0
+    real, z_d, z_g, mix = synthetic(21, 4, cfg.num_channels, cfg.resolution, cfg.latent_size)
+    pair, kw = FAMILY_CASES[case]
+    D_loss, G_loss = pair()
+    names = []
+
+    def hook(fn, args, name):
+        names.append(name)
+        return fn(*args)
+    pg.wgan_gp_loss.enable_graphs(False)
+    pg.wgan_gp_loss.set_mixing_factors(mix)
+    before, pg._lib.CALL_HOOK = pg._lib.CALL_HOOK, hook
+    try:
+        D_loss(D, G, real.to(DEV), z_d.to(DEV), **kw)[0].backward()
+        G_loss(G, D, z_g.to(DEV)).backward()
+        torch.cuda.synchronize()
+    finally:
+        pg._lib.CALL_HOOK = before
+        pg.wgan_gp_loss.set_mixing_factors(None)
+    block = ('pg_d_loss', 'pg_g_loss', 'pg_gp_seed', 'pg_gan_d_loss', 'pg_gan_g_loss', 'pg_r1_seed', 'pg_row_sumsq')
+    assert [n for n in names if n in block] == want and len(names) > len(want)
+
+
 # ---- launch-plan replay ---------------------------------------------------------------------------------------------------------------
 def test_r1_replays_from_a_plan_of_its_own(deterministic_forward):
     """'logistic' + 'r1' from a launch plan against eager launches at identical weights: two eager warm-up steps, the recorded one, then
@@ -251,7 +285,7 @@ def test_r1_replays_from_a_plan_of_its_own(deterministic_forward):
         assert wl._seed[1] == 0                                                 # R1 draws no mixing factors
         keys = list(plans._CACHE)
         obj = D_loss.objective
-        assert sorted(k[0] for k in keys) == ['D', 'G'] and all(k[-1] == obj for k in keys)
+        assert sorted(k[0][0] for k in keys) == ['D', 'G'] and all(k[1][-1] == obj for k in keys)      # (stage part, variant part)
         # a second objective in the same process: plans of its own, beside the first one's
         wl._use_graphs = 'auto'
         D2, G2 = pg.gan_losses('hinge', penalty='r1', penalty_weight=1.0)
@@ -262,12 +296,12 @@ def test_r1_replays_from_a_plan_of_its_own(deterministic_forward):
         assert plans.STATS['recorded'] == 4
         by_obj = {}
         for k, plan in plans._CACHE.items():
-            by_obj.setdefault(k[-1], []).append(plan)
+            by_obj.setdefault(k[1][-1], []).append(plan)
         assert set(by_obj) == {obj, D2.objective} and all(len(v) == 2 and all(p.entries is not None for p in v) for v in by_obj.values())
         assert len({id(p) for v in by_obj.values() for p in v}) == 4
-        # ... and WGAN-GP's own key ends in None
+        # ... and WGAN-GP's own key ends in its objective on the original kernels
         pg.wgan_gp_D_loss(Da, Ga, real, z)[0].backward()
-        assert sum(1 for k in plans._CACHE if k[0] == 'D' and k[-1] is None) == 1
+        assert sum(1 for k in plans._CACHE if k[0][0] == 'D' and k[1][-1] is pg.engine.WGAN_GP) == 1
     finally:
         wl.enable_graphs(False)
 

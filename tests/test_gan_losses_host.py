@@ -180,6 +180,104 @@ def test_backward_scale_and_return_all(emu):
     assert float(base.abs().max()) > 0 and torch.allclose(D._flat_grad, 0.5 * base, rtol=1e-6, atol=0)
 
 
+# ---- one path for every objective: which loss block a step launches -------------------------------------------------------------------
+LOSS_BLOCK = ('d_loss', 'g_loss', 'gp_seed', 'gan_d_loss', 'gan_g_loss', 'r1_seed', 'row_sumsq')
+FAMILY_CASES = {                # name -> (the pair, keyword arguments of its D loss)
+    'default': (lambda: (pg.wgan_gp_D_loss, pg.wgan_gp_G_loss), {}),
+    'lambda5': (lambda: (pg.wgan_gp_D_loss, pg.wgan_gp_G_loss), dict(iwass_lambda=5.0)),
+    'wgan5': (lambda: pg.gan_losses('wgan', penalty_weight=5.0), {}),
+    'logistic_r1': (lambda: pg.gan_losses('logistic', penalty='r1'), {}),
+    'hinge_plain': (lambda: pg.gan_losses('hinge', penalty=None), {}),
+}
+
+
+class _Recording(object):
+    """Stands in for ``engine.ops``: the emulation, with the name and the arguments of every function call kept in ``calls``."""
+
+    def __init__(self, mod):
+        self._mod, self.calls = mod, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._mod, name)
+        if not callable(fn) or isinstance(fn, type):
+            return fn
+
+        def recorded(*a, **k):
+            self.calls.append((name, a, k))
+            return fn(*a, **k)
+        return recorded
+
+
+def _recorded_step(case, monkeypatch):
+    meta, G, D, gp, dp, cfg = _fixture_nets('tiny16c1')
+    G.depth = D.depth = 2
+    G.alpha = D.alpha = 1.0
+    real, z_d, z_g, mix = synthetic(21, 4, cfg.num_channels, cfg.resolution, cfg.latent_size)
+    pair, kw = FAMILY_CASES[case]
+    D_loss, G_loss = pair()
+    rec = _Recording(pg.engine.ops)
+    monkeypatch.setattr(pg.engine, 'ops', rec)
+    pg.wgan_gp_loss.set_mixing_factors(mix)
+    try:
+        d_cost = D_loss(D, G, real, z_d, **kw)[0]
+        d_cost.backward()
+        d_grad = D._flat_grad.clone()
+        G_loss(G, D, z_g).backward()
+    finally:
+        pg.wgan_gp_loss.set_mixing_factors(None)         # ('r1' and no penalty leave it where it is)
+    return [c for c in rec.calls if c[0] in LOSS_BLOCK], float(d_cost), d_grad
+
+
+@pytest.mark.parametrize('case,want', [('default', ['row_sumsq', 'gp_seed', 'd_loss', 'g_loss']),
+                                       ('lambda5', ['row_sumsq', 'gp_seed', 'd_loss', 'g_loss']),
+                                       ('wgan5', ['row_sumsq', 'gp_seed', 'gan_d_loss', 'gan_g_loss']),
+                                       ('logistic_r1', ['row_sumsq', 'r1_seed', 'gan_d_loss', 'gan_g_loss']),
+                                       ('hinge_plain', ['gan_d_loss', 'gan_g_loss'])])
+def test_each_objective_launches_the_loss_block_of_its_family(emu, monkeypatch, case, want):
+    """One D step + G step on the emulation: the default pair and ``wgan_gp_D_loss`` with another lambda stay on the original loss block
+    (no ``gan_*`` / ``r1_seed``), every ``gan_losses`` closure on the pinned one; without a penalty there is no seed and no ``row_sumsq``
+    and the loss block is handed ``pen=None``."""
+    calls, _, _ = _recorded_step(case, monkeypatch)
+    assert [c[0] for c in calls] == want
+    if case == 'hinge_plain':
+        name, a, k = calls[0]
+        assert (a[1] if len(a) > 1 else k['pen']) is None
+    if case in ('lambda5', 'wgan5'):
+        assert [c[1][2] for c in calls if c[0] == 'gp_seed'] == [5.0]
+
+
+def test_the_two_families_state_the_same_wgan_gp(emu, monkeypatch):
+    """``wgan_gp_D_loss(iwass_lambda=5)`` (original block) against ``gan_losses('wgan', penalty_weight=5)`` (pinned block): the same formula
+    over 4 scores, which the emulation evaluates in float64 -- equal up to the final cast, held to 1e-5 relative."""
+    _, cost_o, grad_o = _recorded_step('lambda5', monkeypatch)
+    _, cost_p, grad_p = _recorded_step('wgan5', monkeypatch)
+    assert abs(cost_o - cost_p) <= 1e-5 * abs(cost_o)
+    assert float(grad_o.abs().max()) > 0 and rel_err(grad_p, grad_o) <= 1e-5
+
+
+def test_plan_keys_split_into_stage_and_variants(monkeypatch):
+    """Two objectives, and two ``iwass_lambda`` values, at one stage differ in the variant part of the plan key only and live side by side;
+    a stage change of the same network pair drops both.  (The key function and the cache alone: no plan is recorded.)"""
+    plans, eng = pg.plans, pg.engine
+    meta, G, D, gp, dp, cfg = _fixture_nets('tiny16c1')
+    monkeypatch.setattr(plans, '_CACHE', type(plans._CACHE)())
+    objs = [eng.WGAN_GP, eng.WGAN_GP._replace(weight=5.0), pg.gan_losses('logistic', penalty='r1')[0].objective]
+
+    def key(depth, obj):
+        return plans._key('D', D, G, (depth, (4, 1, 16, 16), (4, cfg.latent_size)), ((0, None), 0, obj))
+    keys = [key(2, o) for o in objs]
+    assert len(set(keys)) == 3 and len({k[0] for k in keys}) == 1 and [k[1][-1] for k in keys] == objs
+    for k in keys:
+        plans._new_plan(k)
+    g_key = plans._key('G', D, G, (2, (4, cfg.latent_size), (0, None), False), (objs[0],))
+    plans._new_plan(g_key)                               # (MAX_PLANS = 4: the three D variants and a G plan)
+    assert list(plans._CACHE) == keys + [g_key]
+    moved = key(1, objs[1])
+    assert moved[0] != keys[0][0] and moved[1] == keys[1][1]
+    plans._new_plan(moved)
+    assert list(plans._CACHE) == [g_key, moved]          # every D variant of the stage it left is gone; the G plans are another step's
+
+
 # ---- the public interface -------------------------------------------------------------------------------------------------------------
 def test_default_objective_is_the_existing_pair():
     assert pg.gan_losses('wgan', penalty='gp') == (pg.wgan_gp_D_loss, pg.wgan_gp_G_loss)

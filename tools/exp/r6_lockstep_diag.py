@@ -72,7 +72,7 @@ def main():
             res = []
             for G, D, opt in ((Ga, Da, oa), (Gb, Db, ob)):
                 D.zero_grad()
-                c, _, _, state = eng.d_loss_forward(D, G, real, z, mix, 10.0, 0.001, 1.0)
+                c, _, _, state = eng.d_loss_forward(D, G, real, z, mix, eng.WGAN_GP)
                 sg = collect(state.ctx)
                 eng.d_loss_backward(state)
                 res.append((float(c), D._flat_grad.clone(), sg))

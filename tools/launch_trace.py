@@ -1,9 +1,11 @@
 """Canonical launch trace of one D step + one G step: what a refactor of the schedules in engine.py must leave byte-identical.
 
-    python tools/launch_trace.py [--emu] [--out DIR] [--list] [CONFIG ...]
+    python tools/launch_trace.py [--emu] [--loss KIND[:PENALTY]] [--out DIR] [--list] [CONFIG ...]
 
-For every named configuration (all of them by default) the networks are built from a fixed seed, ``wgan_gp_D_loss(...).backward()`` and
-``wgan_gp_G_loss(...).backward()`` run eagerly three times, and the third iteration is written to DIR/<mode>_<config>.txt:
+For every named configuration (all of them by default) the networks are built from a fixed seed, ``D_loss(...).backward()`` and
+``G_loss(...).backward()`` run eagerly three times, and the third iteration is written to DIR/<mode>_<config>.txt.  The pair is
+``wgan_gp_D_loss`` / ``wgan_gp_G_loss`` unless ``--loss`` names another objective: ``pg.gan_losses(KIND, penalty=PENALTY)`` with its
+default weights (``--loss hinge``: no penalty; ``--loss logistic:r1``).  Give every ``--loss`` a directory of its own.
 
   device mode   the iteration runs inside ``plans._Recorder`` on a fresh plan: every C-ABI call by name with all its arguments, every event
                 record / wait and the PENDING / BWD_COPIES markers, in issue order.  Scalars are printed verbatim; pointers (the stream
@@ -12,7 +14,7 @@ For every named configuration (all of them by default) the networks are built fr
   --emu         ``engine.ops`` is a proxy around tests/emu_ops.py that logs every call: name, shape and dtype of tensor arguments, scalars
                 (arguments bound to the signature, defaults filled in).  Needs no GPU.
 
-``trainer_*`` configurations (device mode) run ``Trainer.train()`` four times with launch plans instead and print ``plans.STATS`` and the
+``trainer_*`` configurations (device mode, the default pair only) run ``Trainer.train()`` four times with launch plans instead and print ``plans.STATS`` and the
 canonical entries of the recorded D and G plans.  Every trace ends with ``dict(engine.FALLBACKS)``.
 
 Comparing two commits: copy this file into a checkout of the other one (it uses only interfaces both have), run both with the same
@@ -82,11 +84,16 @@ def _batch(seed, n, C, res, latent, dev):
     return tuple(torch.from_numpy(a).to(dev) for a in (real, z_d, z_g, mix))
 
 
+LOSS = None                    # --loss: (kind, penalty); None: the WGAN-GP pair
+
+
 def _step(G, D, batch):
     real, z_d, z_g, mix = batch
-    pg.wgan_gp_loss.set_mixing_factors(mix)
-    pg.wgan_gp_D_loss(D, G, real, z_d)[0].backward()
-    pg.wgan_gp_G_loss(G, D, z_g).backward()
+    D_loss, G_loss = (pg.wgan_gp_D_loss, pg.wgan_gp_G_loss) if LOSS is None else pg.gan_losses(LOSS[0], penalty=LOSS[1])
+    if LOSS is None or LOSS[1] == 'gp':                 # ('r1' and no penalty leave an injected draw where it is)
+        pg.wgan_gp_loss.set_mixing_factors(mix)
+    D_loss(D, G, real, z_d)[0].backward()
+    G_loss(G, D, z_g).backward()
 
 
 class _Ordinals(dict):
@@ -97,7 +104,10 @@ class _Ordinals(dict):
 def canonical(entries, nets):
     """Text lines of a list of plans._Recorder entries."""
     o = _Ordinals()
-    sigs = dict(_lib.CLUSTER_SIGNATURES, **dict(_lib.DEBUG_SIGNATURES, **_lib.SIGNATURES))
+    sigs = {}
+    for k in sorted(vars(_lib)):                        # the tables of every ABI header (SIGNATURES, GAN_SIGNATURES, ...)
+        if k.endswith('SIGNATURES'):
+            sigs.update(getattr(_lib, k))
     name_of = dict((id(net), k) for k, net in nets.items())
     lines = []
     for e in entries:
@@ -162,7 +172,7 @@ def trace(name, emu):
                 torch.cuda.synchronize()
                 lines.append('plans.STATS %r' % dict((k, plans.STATS[k] - before[k]) for k in sorted(before)))
                 for key, plan in plans._CACHE.items():
-                    lines.append('-- %s plan' % key[0])
+                    lines.append('-- %s plan' % (key[0] if isinstance(key[0], str) else key[0][0]))      # (the step leads the key, or its stage part)
                     lines += canonical(plan.entries or [], dict(D=tr.D, G=tr.G))
                 continue
             G, D = _nets(spec, dev)
@@ -192,18 +202,25 @@ def trace(name, emu):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument('--emu', action='store_true', help='host mode: log the calls into tests/emu_ops.py (no GPU)')
+    ap.add_argument('--loss', metavar='KIND[:PENALTY]', help="the objective, as pg.gan_losses names it ('hinge', 'logistic:r1'); default: the WGAN-GP pair")
     ap.add_argument('--out', default='launch_trace', help='directory the traces are written to')
     ap.add_argument('--list', action='store_true')
     ap.add_argument('configs', nargs='*')
     a = ap.parse_args()
+    if a.loss:
+        global LOSS
+        LOSS = tuple((a.loss.split(':') + [None])[:2])
     cfgs = _configs()
     mode = 'e' if a.emu else 'd'
-    names = a.configs or [k for k, v in cfgs.items() if mode in v[0] or (not a.emu and v[0] == 't')]
+    names = a.configs or [k for k, v in cfgs.items() if mode in v[0] or (not a.emu and v[0] == 't' and LOSS is None)]
     if a.list:
         print('\n'.join('%-24s %s' % (k, cfgs[k][0]) for k in names))
         return
     if a.emu:
+        import emu_gan_losses
         import emu_ops
+        for name in ('gan_d_loss', 'gan_g_loss', 'r1_seed'):        # (as the ``emu`` fixture of tests/test_gan_losses_host.py does)
+            setattr(emu_ops, name, getattr(emu_gan_losses, name))
         engine.ops = emu_ops
         engine._check_dev = lambda t, what: t.contiguous()
     os.makedirs(a.out, exist_ok=True)

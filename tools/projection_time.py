@@ -144,7 +144,7 @@ def main():
         zg = torch.randn(mb, G.latent_size, device=dev, generator=g)
 
         def g_step():
-            _, st = pg.engine.g_loss_forward(G, D, zg)
+            _, st = pg.engine.g_loss_forward(G, D, zg, pg.engine.WGAN_GP)
             pg.engine.g_loss_backward(st)
         t = timed({'step': step, 'forward': lambda: G.forward(z), 'train_g_step': g_step}, args.window, args.windows)
         row = {'r': r, 'targets': n, 'step_ms': t['step'], 'forward_ms': t['forward'], 'train_g_step_ms': t['train_g_step'],

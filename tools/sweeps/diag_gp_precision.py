@@ -16,7 +16,7 @@ G.cuda(); D.cuda()
 G.depth = D.depth = depth
 cfg = oc.NetCfg(res, C)
 real, z_d, z_g, mix = oc.synthetic_batch(42 + depth, n, C, 4 * 2 ** depth, 512)
-d_cost, rl, fl, st = pg.engine.d_loss_forward(D, G, real.cuda(), z_d.cuda(), mix.cuda(), 10.0, 0.001, 1.0)
+d_cost, rl, fl, st = pg.engine.d_loss_forward(D, G, real.cuda(), z_d.cuda(), mix.cuda(), pg.engine.WGAN_GP)
 torch.cuda.synchronize()
 dbl = lambda p: {k: (v.double() if torch.is_tensor(v) else float(v)) for k, v in p.items()}
 r32 = oc.d_loss_and_grads(dp, gp, cfg, real, z_d, mix, depth, alpha)
