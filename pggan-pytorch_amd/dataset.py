@@ -5,7 +5,11 @@ stale ``dataset.alpha`` of forked DataLoader workers cannot occu
 the moment it is drawn.
 
 ``device='cpu'`` (host mode) evaluates the same definition with numpy in fp64, as the reference computes it; it backs
-``__getitem__`` and is the twin the device path is compared with, bit for bit (tests/golden/io_steps.npz pins both)."""
+``__getitem__`` and is the twin the device path is compared with, bit for bit (tests/golden/io_steps.npz pins both).
+
+``DeviceStripDataset`` (with ``StripLevel`` and ``CropStream``, at the end) is the same protocol for recordings of arbitrary length:
+every recording is one uint8 spectrogram strip in HBM and a batch item is a window at a random time offset, cut where the strip lies
+in the same single launch (``ops.crop_batch_u8`` / csrc/crop_batch.hip)."""
 import os
 
 import numpy as np
@@ -316,5 +320,359 @@ class DeviceImageDataset(object):
         def real_batch_fn(n):
             idx, _ = stream.take(n)
             return self._make(idx, None, 1.0)
+        real_batch_fn.stream = stream
+        return real_batch_fn
+
+
+# ------------------------------------------------------------------------------------------- strips: random time-crops
+def _pitch(cols):
+    """Row pitch of a strip of ``cols`` columns: rounded up to the multiple include/pggan_hip_crop.h holds pitches and offsets to."""
+    from ._lib import CROP_CONSTANTS
+    align = CROP_CONSTANTS['PG_CROP_PITCH_ALIGN']
+    return -(-int(cols) // align) * align
+
+
+class StripLevel(object):
+    """One stored level of a strip dataset on the device, what ``ops.crop_batch_u8`` reads: ``buffer``, ONE flat uint8 tensor with
+    strip m laid out [C][S rows][pitch] at byte ``offset_m``, and ``table`` [M,3] int64 = (offset, pitch, columns) on the same device.
+    Every pitch is the column count rounded up to 16 and every offset a multiple of 16; the padding bytes are zero and never reach
+    a result.  ``cols`` and ``rows`` are the host's copies of the column counts and of the table."""
+
+    def __init__(self, buffer, table, C, S, cols):
+        self.buffer, self.table, self.C, self.S, self.cols = buffer, table, int(C), int(S), [int(c) for c in cols]
+        self.rows = self.layout(self.C, self.S, self.cols)[0]             # the host's copy of the table
+
+    @staticmethod
+    def layout(C, S, cols):
+        """(rows of (offset, pitch, columns), total bytes) of strips with ``cols`` columns."""
+        rows, off = [], 0
+        for c in cols:
+            rows.append((off, _pitch(c), int(c)))
+            off += C * S * _pitch(c)
+        return rows, off
+
+    @classmethod
+    def empty(cls, C, S, cols, device):
+        rows, total = cls.layout(C, S, cols)
+        buffer = torch.zeros(total, dtype=torch.uint8, device=device)
+        return cls(buffer, torch.tensor(rows, dtype=torch.int64).to(device), C, S, cols)
+
+    @classmethod
+    def pack(cls, strips, device):
+        """The level of uint8 arrays or tensors [C,S,T_m] as they are (no truncation), each copied in one piece."""
+        C, S = int(strips[0].shape[0]), int(strips[0].shape[1])
+        level = cls.empty(C, S, [int(s.shape[2]) for s in strips], device)
+        for m, s in enumerate(strips):
+            level.strip(m).copy_(s if torch.is_tensor(s) else torch.from_numpy(np.ascontiguousarray(s)))
+        return level
+
+    def strip(self, m):
+        """View [C, S, columns] of strip m (rows ``pitch`` bytes apart: not contiguous unless the pitch is the column count)."""
+        off, pitch, cols = self.rows[m]
+        return self.buffer[off:off + self.C * self.S * pitch].view(self.C, self.S, pitch)[:, :, :cols]
+
+    @property
+    def nbytes(self):
+        return int(self.buffer.numel())
+
+
+class CropStream(object):
+    """The positions 0, 1, 2, ... of an endless sequence of crops (strip, start column) from strips of ``lengths`` columns, windows
+    ``R`` columns wide.  An epoch has P = sum(T_m // R) positions.  ``shuffle``: position by position, the strip is drawn with
+    probability proportional to its number of window starts w_m = T_m - R + 1 -- p = min(floor(g W), W - 1), W = sum(w_m), strip =
+    searchsorted(cumsum(w), p, right) -- and the start is t = min(floor(f w_m), w_m - 1): every start of every strip is equally
+    likely.  g and f are float64 from ``torch.rand(P)`` on two CPU generators seeded ``seed`` and ``seed + 1``; the mirror flags
+    (``flags=True``) are ``torch.randint(0, 2, (P,), dtype=torch.uint8)`` on a third seeded ``seed + 2``.  Without ``shuffle`` an
+    epoch enumerates the non-overlapping windows (m, i R) in strip-major order.  ``t`` counts full-resolution columns, so the stream
+    does not depend on the stage: at stored level k the start is t >> k, at most cols_k - (R >> k) when T_m and R are multiples
+    of 2^k.  An epoch's arrays are made once and moved to ``device`` once; ``take`` hands out slices (concatenated on the device
+    across an epoch boundary) with ``IndexStream``'s cursor rules: no copy and no synchronisation per batch."""
+
+    def __init__(self, lengths, R, shuffle=True, seed=0, flags=False, device='cpu'):
+        self.lengths, self.R = np.asarray([int(t) for t in lengths], dtype=np.int64), int(R)
+        if self.lengths.size < 1 or int(self.lengths.min()) < self.R or self.R < 1:
+            raise ValueError('a crop stream needs at least one strip, each of at least R = %d columns' % self.R)
+        self.P = int((self.lengths // self.R).sum())
+        self.shuffle, self.flags, self.device = bool(shuffle), bool(flags), torch.device(device)
+        self._g = [torch.Generator().manual_seed(int(seed) + k) for k in range(3)]
+        self._w = self.lengths - self.R + 1
+        self._cum = np.cumsum(self._w)
+        self._epochs = {}                # epoch number -> (idx, pos, flip or None) on ``device``
+        self._made = 0                   # epochs generated so far (they must be drawn in order)
+        self.cursor = 0
+
+    def _draw(self):
+        """(strip [P], start [P]) int64 numpy arrays of the next epoch."""
+        if not self.shuffle:
+            counts = self.lengths // self.R
+            strip = np.repeat(np.arange(self.lengths.size, dtype=np.int64), counts)
+            start = np.concatenate([np.arange(c, dtype=np.int64) * self.R for c in counts])
+            return strip, start
+        g = torch.rand(self.P, dtype=torch.float64, generator=self._g[0]).numpy()
+        f = torch.rand(self.P, dtype=torch.float64, generator=self._g[1]).numpy()
+        W = int(self._cum[-1])
+        p = np.minimum(np.floor(g * W).astype(np.int64), W - 1)
+        strip = np.searchsorted(self._cum, p, side='right').astype(np.int64)
+        w = self._w[strip]
+        return strip, np.minimum(np.floor(f * w).astype(np.int64), w - 1)
+
+    def _epoch(self, e):
+        while self._made <= e:
+            strip, start = self._draw()
+            flip = torch.randint(0, 2, (self.P,), generator=self._g[2], dtype=torch.uint8) if self.flags else None
+            self._epochs[self._made] = (torch.from_numpy(strip).to(self.device), torch.from_numpy(start).to(self.device),
+                                        None if flip is None else flip.to(self.device))
+            self._made += 1
+        return self._epochs[e]
+
+    def take(self, n, rank=0, world=1):
+        """(idx [n] int64, pos [n] int64, flip [n] uint8 or None) at positions [cursor + rank n, cursor + (rank + 1) n); the cursor
+        moves by n world."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('a draw needs at least one crop')
+        first = self.cursor + rank * n
+        self.cursor += n * world
+        for e in [k for k in self._epochs if k < first // self.P]:              # epochs every rank has left behind
+            del self._epochs[e]
+        parts, at = [], first
+        while at < first + n:
+            e, off = divmod(at, self.P)
+            m = min(self.P - off, first + n - at)
+            parts.append(tuple(None if t is None else t[off:off + m] for t in self._epoch(e)))
+            at += m
+        if self.device.type == 'cuda':
+            s = torch.cuda.current_stream()
+            for t in (t for p in parts for t in p if t is not None):
+                t.record_stream(s)                                              # (read on this stream; freed when its epoch is over)
+        if len(parts) == 1:
+            return parts[0]
+        return tuple(torch.cat([p[k] for p in parts]) if parts[0][k] is not None else None for k in range(3))
+
+
+class DeviceStripDataset(object):
+    """Random time-crops of long recordings: ``strips`` is a list of uint8 numpy arrays or torch tensors [C, R, T_m] (spectrograms,
+    time along the last axis), one C in {1, 2, 3} and one R (a power of two >= 4) for all of them, T_m >= R (ValueError otherwise,
+    naming the strip).  Every strip is TRUNCATED to R (T_m // R) columns: then every pyramid level has whole columns and the
+    non-overlapping windows tile every level.  A training image is the R x R window at a random start column t of a random strip
+    (``CropStream``): all of every recording is used and every batch is a new translation.  Each strip is stored once, uint8, in HBM
+    (``StripLevel``), and a batch -- gather of the windows where the strips lie, pyramid level, mirror, fade-in, dynamic range -- is
+    one launch (``ops.crop_batch_u8`` / csrc/crop_batch.hip): nothing crosses PCIe and nothing synchronises per batch.
+
+    The stage is dataset depth ``model_depth + model_dataset_depth_offset`` (side r = 2^depth), k = log2(R) - depth levels below the
+    source.  ``pyramid`` as in ``DeviceImageDataset``:
+
+      'chain'   level k is made from level k + 1 with ``ops.pyramid_level_u8`` per strip (a 2x2 box mean rounded to uint8 at every
+                level), once, at construction, and kept (+1/3 memory); a batch reads the window [t >> k, (t >> k) + r) of the stage's
+                level, so a stage k levels down translates in steps of 2^k full-resolution columns.
+      'direct'  only the full-resolution strips are kept; a batch takes the window [t, t + R) and subsamples it by depth
+                difference k (the top-left 2x2 of every 2^k block), at every start t.
+
+    For windows that start at a multiple of R (``dataset[i]``, ``level_stack()``, ``shuffle=False``) the two agree at the source and
+    one level below, as for images.
+
+    Protocol and methods are ``DeviceImageDataset``'s: ``model_depth`` and ``alpha`` are plain attributes (``DepthManager`` writes
+    them), ``shape`` = (P, C, R, R) and ``len()`` = P = sum(T_m // R), the windows of an epoch; ``dataset[i]`` is the host tensor
+    [C,r,r] fp32 of NON-OVERLAPPING window i (strip-major) at the current depth and alpha; ``batch(n)``, ``loader(n)``, ``cursor``,
+    ``metric_batches(seed)`` and ``close()``.  ``level_stack()`` materialises the uint8 [P,C,r,r] stack of the non-overlapping
+    windows of the current stage per call, so ``NNMonitor``, ``NDBMonitor`` and ``SWDMonitor(real_batch_fn=...)`` work unchanged.
+    Under data parallelism (``rank`` of ``world``, one seed everywhere) the ranks take disjoint positions of one stream.
+
+    ``device='cpu'``: host mode, the numpy twin -- it slices the same windows and calls ``batch_host``."""
+
+    def __init__(self, strips, model_dataset_depth_offset=2, model_initial_depth=0, alpha=1.0, range_in=(0, 255), range_out=(-1, 1),
+                 pyramid='chain', mirror_augment=False, shuffle=True, seed=0, rank=0, world=1, device='cuda'):
+        strips = list(strips)
+        if not strips:
+            raise ValueError('strips: expected at least one uint8 array [C,R,T]')
+        for m, s in enumerate(strips):
+            ok = s.dtype == torch.uint8 if torch.is_tensor(s) else isinstance(s, np.ndarray) and s.dtype == np.uint8
+            if not ok or s.ndim != 3:
+                raise ValueError('strip %d: expected a uint8 numpy array or torch tensor [C,R,T]' % m)
+        C, R = int(strips[0].shape[0]), int(strips[0].shape[1])
+        if C not in (1, 2, 3):
+            raise ValueError('strip 0: %d channels (1, 2 or 3 are supported)' % C)
+        if R < 4 or R & (R - 1):
+            raise ValueError('strip 0: %d rows (the height must be a power of two >= 4)' % R)
+        for m, s in enumerate(strips):
+            if (int(s.shape[0]), int(s.shape[1])) != (C, R):
+                raise ValueError('strip %d is [%d,%d,T], strip 0 is [%d,%d,T]' % (m, s.shape[0], s.shape[1], C, R))
+            if int(s.shape[2]) < R:
+                raise ValueError('strip %d: %d columns, a window needs %d' % (m, s.shape[2], R))
+        if pyramid not in ('chain', 'direct'):
+            raise ValueError("pyramid must be 'chain' or 'direct', got %r" % (pyramid,))
+        if int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError('rank %r of world %r' % (rank, world))
+        self.model_depth, self.alpha = model_initial_depth, alpha
+        self.model_dataset_depth_offset = int(model_dataset_depth_offset)
+        self.range_in, self.range_out = tuple(range_in), tuple(range_out)
+        self.pyramid, self.mirror_augment, self.shuffle, self.seed = pyramid, bool(mirror_augment), bool(shuffle), int(seed)
+        self.rank, self.world = int(rank), int(world)
+        self.device = torch.device(device)
+        self.lengths = [R * (int(s.shape[2]) // R) for s in strips]              # columns kept of every strip
+        self._windows = np.cumsum([0] + [t // R for t in self.lengths])         # first non-overlapping window of strip m
+        self._shape = (int(self._windows[-1]), C, R, R)
+        self.max_dataset_depth = _log2(R)
+        self.min_dataset_depth = self.max_dataset_depth if pyramid == 'direct' else min(self.max_dataset_depth, max(1, self.model_dataset_depth_offset))
+        self._levels = {self.max_dataset_depth: self._upload(strips)}
+        for depth in range(self.max_dataset_depth - 1, self.min_dataset_depth - 1, -1):       # 'chain' only
+            self._levels[depth] = self._level_below(self._levels[depth + 1])
+        self._train = CropStream(self.lengths, R, self.shuffle, self.seed, flags=self.mirror_augment, device=self.device)
+
+    # --------------------------------------------------------------------------------------------- construction
+    @classmethod
+    def from_waveforms(cls, signals, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None, **kw):
+        """The dataset of a list of waveforms of different lengths (``[nsamp]`` or ``[nsamp, channels]``, numpy arrays or tensors):
+        one strip per recording from ``sound.spectrogram_strip_u8``.  A waveform that gives fewer than n_fft/2 usable frames is a
+        ValueError naming it."""
+        from . import sound
+        strips = []
+        for m, y in enumerate(signals):
+            if sound.strip_frames(int(y.shape[0]), hop_length, img_mode) < int(n_fft) // 2:
+                raise ValueError('waveform %d: %d samples give %d usable frames, a window needs %d'
+                                 % (m, y.shape[0], sound.strip_frames(int(y.shape[0]), hop_length, img_mode), int(n_fft) // 2))
+            strips.append(sound.spectrogram_strip_u8(y, n_fft, hop_length, img_mode, mag_range))
+        return cls(strips, **kw)
+
+    def _upload(self, strips):
+        """Host mode: a list of numpy arrays [C,R,T].  Device: a ``StripLevel``, filled ``UPLOAD_CHUNK_BYTES`` of columns at a time."""
+        C, R = self._shape[1], self._shape[2]
+        if self.device.type != 'cuda':
+            return [np.ascontiguousarray((s.cpu().numpy() if torch.is_tensor(s) else s)[:, :, :t]) for s, t in zip(strips, self.lengths)]
+        from . import ops
+        ops.require_gpu()
+        level = StripLevel.empty(C, R, self.lengths, self.device)
+        step = max(1, UPLOAD_CHUNK_BYTES // (C * R))
+        for m, (s, t) in enumerate(zip(strips, self.lengths)):
+            dst = level.strip(m)
+            for a in range(0, t, step):
+                b = min(t, a + step)
+                chunk = s[:, :, a:b] if torch.is_tensor(s) else torch.from_numpy(np.array(s[:, :, a:b]))   # (a copy: a memory-mapped file is read here)
+                dst[:, :, a:b].copy_(chunk)
+        return level
+
+    def _level_below(self, level):
+        if not isinstance(level, StripLevel):
+            return [level_host(s, 1, self.range_in) for s in level]
+        from . import ops
+        below = StripLevel.empty(level.C, level.S // 2, [c // 2 for c in level.cols], self.device)
+        for m in range(len(level.cols)):
+            below.strip(m).copy_(ops.pyramid_level_u8(level.strip(m), 1, self.range_in))       # (takes H != W; makes the view contiguous)
+        return below
+
+    # ------------------------------------------------------------------------------------------------- protocol
+    @property
+    def shape(self):
+        return self._shape
+
+    def __len__(self):
+        return self._shape[0]
+
+    def close(self):
+        """Free the device buffers; the object is of no use afterwards."""
+        self._levels = {}
+        self._train = None
+
+    def level_bytes(self):
+        """{dataset depth: bytes of its stored level} (device mode: the padded buffer; host mode: the arrays)."""
+        return dict((d, lv.nbytes if isinstance(lv, StripLevel) else int(sum(s.nbytes for s in lv))) for d, lv in self._levels.items())
+
+    def _stage(self):
+        """(stored level to read, shift, depth difference) of the current ``model_depth``."""
+        if not self._levels:
+            raise RuntimeError('the dataset is closed')
+        depth = int(self.model_depth) + self.model_dataset_depth_offset
+        lowest = self.min_dataset_depth if self.pyramid == 'chain' else 1
+        if not lowest <= depth <= self.max_dataset_depth:
+            raise ValueError('model_depth %r + offset %d is dataset depth %d; this dataset has depths %d .. %d'
+                             % (self.model_depth, self.model_dataset_depth_offset, depth, lowest, self.max_dataset_depth))
+        if self.pyramid == 'chain':
+            return self._levels[depth], self.max_dataset_depth - depth, 0
+        return self._levels[self.max_dataset_depth], 0, self.max_dataset_depth - depth
+
+    @staticmethod
+    def _strip_of(level, m):
+        return level.strip(m) if isinstance(level, StripLevel) else level[m]
+
+    def level_stack(self):
+        """The uint8 stack [P,C,r,r] of the NON-OVERLAPPING windows of the current ``model_depth`` (strip-major), what
+        ``metrics.NearestNeighbours`` and ``metrics.NDB`` search: materialised at every call and NOT kept -- a caller that needs it
+        repeatedly within a stage keeps it.  'direct' below the source resolution makes the level of the windows here
+        (``ops.pyramid_level_u8`` on the device, ``level_host`` in host mode)."""
+        level, shift, dd = self._stage()
+        P, C, R, _ = self._shape
+        S = R >> shift
+        parts = []
+        for m in range(len(self.lengths)):
+            s = self._strip_of(level, m)
+            s = s if torch.is_tensor(s) else torch.from_numpy(s)
+            parts.append(s.reshape(C, S, s.shape[2] // S, S).permute(2, 0, 1, 3))
+        stack = torch.cat(parts).contiguous()
+        if dd == 0:
+            return stack
+        if stack.is_cuda:
+            from . import ops
+            return ops.pyramid_level_u8(stack, dd, self.range_in)
+        return torch.from_numpy(level_host(stack.numpy(), dd, self.range_in))
+
+    def _windows_host(self, level, idx, pos, shift):
+        """uint8 numpy stack [n,C,S,S] of the windows [pos >> shift, (pos >> shift) + S) of strips ``idx`` of a stored level."""
+        S = self._shape[2] >> shift
+        out = []
+        for m, t in zip(np.asarray(idx).tolist(), np.asarray(pos).tolist()):
+            s = self._strip_of(level, m)[:, :, (t >> shift):(t >> shift) + S]
+            out.append(s.cpu().numpy() if torch.is_tensor(s) else s)
+        return np.stack(out)
+
+    def __getitem__(self, item):
+        i = int(item)
+        if not -len(self) <= i < len(self):
+            raise IndexError('window %d of %d' % (i, len(self)))
+        i %= len(self)
+        m = int(np.searchsorted(self._windows, i, side='right')) - 1
+        level, shift, dd = self._stage()
+        window = self._windows_host(level, [m], [(i - int(self._windows[m])) * self._shape[2]], shift)[0]
+        return torch.from_numpy(prepare_host(level_host(window, dd, self.range_in), self.alpha, self.range_in, self.range_out))
+
+    # -------------------------------------------------------------------------------------------------- batches
+    def _make(self, idx, pos, flip, alpha):
+        level, shift, dd = self._stage()
+        if isinstance(level, StripLevel):
+            from . import ops
+            return ops.crop_batch_u8(level, idx, pos, flip, shift, dd, alpha, self.range_in, self.range_out)
+        windows = self._windows_host(level, idx.numpy(), pos.numpy(), shift)
+        return torch.from_numpy(batch_host(windows, np.arange(len(windows)), None if flip is None else flip.numpy(), dd, alpha,
+                                           self.range_in, self.range_out))
+
+    def draw_crops(self, n):
+        """The next ``n`` (strips, start columns at full resolution, mirror flags or None) of this rank from the training stream;
+        moves the cursor."""
+        if self._train is None:
+            raise RuntimeError('the dataset is closed')
+        return self._train.take(n, self.rank, self.world)
+
+    @property
+    def cursor(self):
+        """Next unread position of the training stream (crops drawn so far, over all ranks)."""
+        return self._train.cursor
+
+    def batch(self, n, alpha=None):
+        """fp32 batch [n,C,r,r] at the current ``model_depth``, with ``self.alpha`` unless ``alpha`` is given, on the current stream."""
+        idx, pos, flip = self.draw_crops(n)
+        return self._make(idx, pos, flip, self.alpha if alpha is None else alpha)
+
+    def loader(self, minibatch_size):
+        """Endless iterator of ``batch(minibatch_size)``; every batch is drawn with the depth and alpha of that moment."""
+        while True:
+            yield self.batch(minibatch_size)
+
+    def metric_batches(self, seed=1):
+        """``f(n)`` -> fp32 batch [n,C,r,r] at the current ``model_depth`` with alpha = 1 and no mirror, from a crop stream and a
+        cursor of its own: evaluating a metric does not move the training stream."""
+        stream = CropStream(self.lengths, self._shape[2], self.shuffle, seed, flags=False, device=self.device)
+
+        def real_batch_fn(n):
+            idx, pos, _ = stream.take(n)
+            return self._make(idx, pos, None, 1.0)
         real_batch_fn.stream = stream
         return real_batch_fn

@@ -858,6 +858,52 @@ def real_batch_u8(stack_u8, idx, flip=None, depthdiff=0, alpha=1.0, range_in=(0,
     return out
 
 
+CROP = {name[len('PG_CROP_'):]: value for name, value in _lib.CROP_CONSTANTS.items() if name.startswith('PG_CROP_')}   # the addition's own table
+CROP_TABLE_WORDS, CROP_PITCH_ALIGN = CROP['TABLE_WORDS'], CROP['PITCH_ALIGN']
+
+
+def crop_batch_u8(level, idx, pos, flip=None, shift=0, depthdiff=0, alpha=1.0, range_in=(0, 255), range_out=(-1, 1), check=False):
+    """One stored level of uint8 device strips (``dataset.StripLevel``: the flat ``buffer``, its ``table`` [M,3] int64 of (byte offset,
+    row pitch, columns), ``C`` and the rows ``S``) -> fp32 batch [n,C,r,r], r = S >> depthdiff, in one launch (pg_crop_batch_u8,
+    csrc/crop_batch.hip): image j is the window of columns [u, u + S), u = pos[j] >> shift, of strip ``idx[j]`` (int64 device tensors
+    [n]), treated as ``real_batch_u8`` treats an image of a stack -- pyramid level, mirror where ``flip[j] != 0``, fade, range -- and
+    equal to it bit for bit on the materialised windows.  The device checks neither ``idx`` nor ``pos``: ``check=True`` reads their
+    extrema back (a host synchronisation) and raises IndexError for a strip outside [0, M) or a window that leaves its strip."""
+    require_gpu()
+    buf, table = level.buffer, level.table
+    if not torch.is_tensor(buf) or not buf.is_cuda or buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.dim() != 1:
+        raise ValueError('level.buffer: expected a contiguous flat uint8 device tensor')
+    if (not torch.is_tensor(table) or table.device != buf.device or table.dtype != torch.int64 or not table.is_contiguous()
+            or table.dim() != 2 or table.shape[0] < 1 or table.shape[1] != CROP_TABLE_WORDS):
+        raise ValueError('level.table: expected a contiguous int64 tensor [M,%d] on the device of the buffer' % CROP_TABLE_WORDS)
+    M, C, S = table.shape[0], int(level.C), int(level.S)
+    for name, t in (('idx', idx), ('pos', pos)):
+        if not torch.is_tensor(t) or t.device != buf.device or t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1 or t.numel() < 1:
+            raise ValueError('%s: expected a contiguous, non-empty int64 tensor [n] on the device of the level' % name)
+    n = idx.numel()
+    if pos.numel() != n:
+        raise ValueError('idx holds %d strips, pos %d start columns' % (n, pos.numel()))
+    if flip is not None and (not torch.is_tensor(flip) or flip.device != buf.device or flip.dtype != torch.uint8
+                             or not flip.is_contiguous() or tuple(flip.shape) != (n,)):
+        raise ValueError('flip: expected None or a contiguous uint8 tensor [%d] on the device of the level' % n)
+    shift, depthdiff = int(shift), int(depthdiff)
+    if check:
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= M:
+            raise IndexError('idx holds values in [%d, %d] for a level of %d strips' % (lo, hi, M))
+        u = pos >> shift if 0 <= shift < 63 else pos
+        over = u - (table[:, 2][idx] - S)                        # > 0: the window ends past the strip's last column
+        lo, hi = int(u.min()), int(over.max())
+        if lo < 0 or hi > 0:
+            raise IndexError('pos: a window starts at column %d or ends %d columns past the end of its strip' % (lo, hi))
+    r = S >> depthdiff if 0 <= depthdiff < 31 else 0
+    out = torch.empty((n, C, r, r), device=buf.device, dtype=torch.float32)
+    _lib.call('pg_crop_batch_u8', buf.data_ptr(), table.data_ptr(), M, C, S, shift, depthdiff, idx.data_ptr(), pos.data_ptr(),
+              None if flip is None else flip.data_ptr(), n, out.data_ptr(), float(alpha), float(range_in[0]), float(range_in[1]),
+              float(range_out[0]), float(range_out[1]), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------- sliced Wasserstein distance (csrc/swd.hip)
 SWD_DESC = _C['PG_SWD_DESC']                                   # 3 channels x 7 x 7
 SWD_REDUCE_BLOCKS = _C['PG_SWD_REDUCE_BLOCKS']

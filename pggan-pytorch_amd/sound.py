@@ -67,6 +67,47 @@ def spectrogram_stack_u8(signals, n_fft=1024, hop_length=128, mag_range=None):
     return phase.spectrogram_stack_u8(t.to(device='cuda', dtype=torch.float32).contiguous(), int(n_fft), int(hop_length), mag_range)
 
 
+def strip_frames(nsamp, hop_length, img_mode='magif'):
+    """Columns of ``spectrogram_strip_u8`` for a waveform of ``nsamp`` samples: the 1 + nsamp // hop_length frames without the first."""
+    if img_mode not in ('magif', 'abslog'):
+        raise ValueError("img_mode must be 'magif' or 'abslog' (got %r)" % (img_mode,))
+    if isinstance(hop_length, bool) or int(hop_length) != hop_length or hop_length < 1:
+        raise ValueError('hop_length must be a positive integer, got %r' % (hop_length,))
+    return int(nsamp) // int(hop_length)
+
+
+def spectrogram_strip_u8(signal, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None):
+    """Waveform (numpy array or tensor, ``[nsamp]`` or ``[nsamp, channels]``, mixed down as in ``spectrogram_u8``) -> the uint8 device
+    STRIP ``[C, n_fft/2, T]`` over ALL frames of the recording, T = nsamp // hop_length, for ``dataset.DeviceStripDataset``:
+    ``phase.analyse(bins=n_fft/2, frames=all)`` and ``phase.magif_u8`` with column 0 dropped -- the first column of the second
+    channel is the phase itself, not an instantaneous frequency, and a crop from the middle of a recording never has such a column.
+
+    'magif'   both channels: log-magnitude stretched from the FIXED ``mag_range`` (default (0, log1p(n_fft/2))) and the instantaneous
+              frequency on a circle of 256 levels.
+    'abslog'  channel 0 of the same alone, ``[1, n_fft/2, T]``: log1p|S| stretched from the FIXED ``mag_range``, NOT from the per-file
+              minimum and maximum that ``spectrogram_u8(img_mode='abslog')`` (the reference's load_file) uses -- crops of one
+              recording and of different recordings share one scale, and the image can be inverted without knowing the file.
+
+    The analysis holds two float64 planes [n_fft/2, T + 1] on the device while it runs (16 n_fft/2 bytes per frame)."""
+    import torch
+    from . import phase
+    t = signal if torch.is_tensor(signal) else torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32))
+    if t.dim() not in (1, 2) or t.shape[0] < 1:
+        raise ValueError('expected a waveform [nsamp] or [nsamp, channels], got shape %s' % (tuple(t.shape),))
+    if isinstance(n_fft, bool) or int(n_fft) != n_fft:
+        raise ValueError('n_fft must be an integer, got %r' % (n_fft,))
+    T = strip_frames(t.shape[0], hop_length, img_mode)
+    if T < 1:
+        raise ValueError('%d samples every %r give no frame after the first' % (t.shape[0], hop_length))
+    mag_range = phase.check_mag_range(mag_range, int(n_fft), 'spectrogram_strip_u8')
+    t = t.to(device='cuda', dtype=torch.float32)
+    if t.dim() == 2:
+        t = t.sum(dim=1) / 2                                                  # dataset.py:287-288: s.sum(axis=1) / 2 in float32
+    logmag, ifreq = phase.analyse(t.contiguous(), int(n_fft), int(hop_length), int(n_fft) // 2, T + 1)
+    image = phase.magif_u8(logmag, ifreq, mag_range)[0]
+    return image[:1 if img_mode == 'abslog' else 2, :, 1:].contiguous()
+
+
 # ---------------------------------------------------------------------- 'magif' in numpy fp64: the host twin of csrc/phase.hip
 def _mag_range(mag_range, n_fft):
     if mag_range is None:
