@@ -16,7 +16,7 @@ from .ema import GeneratorEMA  # noqa: F401
 from .parallel import DataParallel  # noqa: F401
 from .sound import SoundSaver, DeviceSoundSaver, spectrogram_u8, spectrogram_stack_u8, spectrogram_strip_u8  # noqa: F401
 from .dataset import DeviceImageDataset, DeviceStripDataset, CropStream  # noqa: F401
-from .metrics import NearestNeighbours, NDB  # noqa: F401
+from .metrics import NearestNeighbours, NDB, ChannelSlicedWasserstein  # noqa: F401
 from .sampling import Sampler, sampler_for  # noqa: F401
 from .projection import Projector  # noqa: F401
 from .utils import project_samples  # noqa: F401
@@ -27,4 +27,5 @@ __all__ = ['Generator', 'Discriminator', 'PGConv2d', 'wgan_gp_D_loss', 'wgan_gp_
            'DepthManager', 'LRScheduler', 'RampupLR', 'TimeMonitor', 'AbsoluteTimeMonitor', 'SaverPlugin', 'OutputGenerator', 'SWDMonitor', 'MSSSIMMonitor', 'NNMonitor', 'load_models',
            'load_smoothed_generator', 'load_trainer_state', 'FusedAdam', 'GeneratorEMA', 'DataParallel', 'SoundSaver', 'DeviceSoundSaver',
            'spectrogram_u8', 'spectrogram_stack_u8', 'DeviceImageDataset', 'NearestNeighbours', 'NDB', 'NDBMonitor', 'LossMonitor', 'HealthMonitor', 'ScalarStats', 'SegmentStats',
-           'TrainingDiverged', 'Sampler', 'sampler_for', 'Projector', 'ProjectionMonitor', 'project_samples', 'DeviceStripDataset', 'CropStream', 'spectrogram_strip_u8']
+           'TrainingDiverged', 'Sampler', 'sampler_for', 'Projector', 'ProjectionMonitor', 'project_samples', 'DeviceStripDataset', 'CropStream', 'spectrogram_strip_u8',
+           'ChannelSlicedWasserstein']

@@ -4,6 +4,9 @@
 //   pg_swd_gather                            : 3x7x7 neighbourhoods around given centres -> rows of 147 floats
 //   pg_swd_channel_stats / pg_swd_normalize  : per-channel mean / population std over a whole descriptor set, applied in place
 //   pg_swd_project                           : [M,147] x [147,K] on v_mfma_f32_32x32x2_f32, written transposed [K,M]
+//   pg_swd_gather_c / pg_swd_channel_stats_c / pg_swd_normalize_c / pg_swd_project_c (include/pggan_hip_swd.h): the same four for
+//                                              C = 1..4 channels, descriptors of 49 C floats.  The kernels are templates over C and the
+//                                              four above are their C = 3 instantiation, so C = 3 gives the same bits through either.
 //   pg_swd_sort_rows                         : every row of [K,M] ascending (bitonic runs in LDS + merge-path passes)
 //   pg_swd_l1                                : mean |a - b| into one device scalar
 // All fp32 on the caller's stream; the scratch each needs is an argument (nothing here uses the registered per-stream workspace).
@@ -12,10 +15,12 @@
 #include <stdint.h>
 #include <atomic>
 #include "pggan_hip.h"
+#include "pggan_hip_swd.h"
 
 namespace {
 
-constexpr int DESC = PG_SWD_DESC;                  // 3 channels x 7 x 7
+constexpr int PATCH = PG_SWD_PATCH;                // 7 x 7: one channel of a descriptor; a descriptor of C channels is PATCH * C floats
+static_assert(PG_SWD_DESC == 3 * PATCH, "the entry points of pggan_hip.h are the three-channel instantiation");
 constexpr int RED_BLOCKS = PG_SWD_REDUCE_BLOCKS;   // most workgroups a two-stage reduction is spread over
 constexpr int RUN = PG_SWD_SORT_RUN;               // elements one workgroup sorts in LDS
 constexpr int SORT_THREADS = 1024;
@@ -24,6 +29,7 @@ constexpr int MERGE_THREADS = 256;
 constexpr int MERGE_ITEMS = TILE / MERGE_THREADS;
 constexpr int PJ_M = 128;                          // descriptors per workgroup of the projection (4 waves x 32)
 constexpr int PJ_K = 128;                          // directions per workgroup (4 accumulator tiles of 32 per wave)
+static_assert(PJ_M % 4 == 0 && PJ_M * PG_SWD_PATCH * PG_SWD_MAX_CHANNELS * 4 <= 160 * 1024, "a workgroup's descriptors are whole float4s and fit in LDS");
 static_assert(RUN % TILE == 0, "a merge tile must not straddle two pairs of runs");
 static_assert((RUN & (RUN - 1)) == 0 && TILE % MERGE_THREADS == 0, "");
 
@@ -98,9 +104,11 @@ __global__ __launch_bounds__(256) void lap_up_sub_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------------- descriptors
 // one thread per descriptor element, rows in (channel, dy, dx) order.  Centres are clamped to [3, S-4] so that no read leaves the image
 // whatever the caller passes; ops.swd_gather rejects a centre outside that range before the launch.
+template <int C>
 __global__ __launch_bounds__(256) void swd_gather_kernel(const float* __restrict__ level, const int* __restrict__ centres,
                                                          float* __restrict__ out, long long ndesc, int P, int S, long long row_offset)
 {
+    constexpr int DESC = PATCH * C;
     const long long total = ndesc * DESC;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const long long j = idx / DESC;
@@ -108,7 +116,7 @@ __global__ __launch_bounds__(256) void swd_gather_kernel(const float* __restrict
         const int c = e / 49, dy = (e % 49) / 7, dx = e % 7;
         const int cx = min(max(centres[2 * j], 3), S - 4), cy = min(max(centres[2 * j + 1], 3), S - 4);
         const size_t img = (size_t)(j / P);
-        out[(size_t)(row_offset + j) * DESC + e] = level[((img * 3 + c) * S + (cy - 3 + dy)) * S + (cx - 3 + dx)];
+        out[(size_t)(row_offset + j) * DESC + e] = level[((img * C + c) * S + (cy - 3 + dy)) * S + (cx - 3 + dx)];
     }
 }
 
@@ -129,46 +137,61 @@ __device__ __forceinline__ void block_sum(double (&v)[NV])
         for (int i = 0; i < NV; ++i) v[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
 }
 
-// stage 1: per-workgroup fp64 partials of sum and sum of squares per channel: partials[block][6]
+// stage 1: per-workgroup fp64 partials of sum and sum of squares per channel: partials[block][2 C] (the C sums, then the C sums of
+// squares).  Every value is added to every accumulator, as itself or as 0.0, so the loop has no branch on the channel.
+template <int C>
 __global__ __launch_bounds__(256) void swd_stats_partial_kernel(const float* __restrict__ desc, long long total, double* __restrict__ partials)
 {
-    double v[6] = {0, 0, 0, 0, 0, 0};
+    constexpr int DESC = PATCH * C;
+    double v[2 * C];
+#pragma unroll
+    for (int i = 0; i < 2 * C; ++i) v[i] = 0.0;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % DESC) / 49;
+        const int c = (int)(idx % DESC) / PATCH;
         const double x = (double)desc[idx], xx = x * x;
-        v[0] += c == 0 ? x : 0.0; v[1] += c == 1 ? x : 0.0; v[2] += c == 2 ? x : 0.0;
-        v[3] += c == 0 ? xx : 0.0; v[4] += c == 1 ? xx : 0.0; v[5] += c == 2 ? xx : 0.0;
+#pragma unroll
+        for (int i = 0; i < C; ++i) v[i] += c == i ? x : 0.0;
+#pragma unroll
+        for (int i = 0; i < C; ++i) v[C + i] += c == i ? xx : 0.0;
     }
     block_sum(v);
     if (threadIdx.x == 0)
-        for (int i = 0; i < 6; ++i) partials[(size_t)blockIdx.x * 6 + i] = v[i];
+        for (int i = 0; i < 2 * C; ++i) partials[(size_t)blockIdx.x * (2 * C) + i] = v[i];
 }
 
-// stage 2 (one workgroup): stats[0..2] = mean, stats[3..5] = population standard deviation
+// stage 2 (one workgroup): stats[0 .. C-1] = mean, stats[C .. 2C-1] = population standard deviation
+template <int C>
 __global__ __launch_bounds__(256) void swd_stats_final_kernel(const double* __restrict__ partials, int blocks, long long M, float* __restrict__ stats)
 {
-    double v[6] = {0, 0, 0, 0, 0, 0};
+    double v[2 * C];
+#pragma unroll
+    for (int i = 0; i < 2 * C; ++i) v[i] = 0.0;
     for (int b = threadIdx.x; b < blocks; b += blockDim.x)
-        for (int i = 0; i < 6; ++i) v[i] += partials[(size_t)b * 6 + i];
+        for (int i = 0; i < 2 * C; ++i) v[i] += partials[(size_t)b * (2 * C) + i];
     block_sum(v);
     if (threadIdx.x == 0) {
-        const double n = (double)M * 49.0;
-        for (int c = 0; c < 3; ++c) {
+        const double n = (double)M * (double)PATCH;
+        for (int c = 0; c < C; ++c) {
             const double mean = v[c] / n;
-            const double var = v[3 + c] / n - mean * mean;
+            const double var = v[C + c] / n - mean * mean;
             stats[c] = (float)mean;
-            stats[3 + c] = (float)sqrt(var > 0.0 ? var : 0.0);
+            stats[C + c] = (float)sqrt(var > 0.0 ? var : 0.0);
         }
     }
 }
 
+template <int C>
 __global__ __launch_bounds__(256) void swd_normalize_kernel(float* __restrict__ desc, long long total, const float* __restrict__ stats)
 {
-    const float mean[3] = {stats[0], stats[1], stats[2]}, sd[3] = {stats[3], stats[4], stats[5]};
+    constexpr int DESC = PATCH * C;
+    float mean[C], sd[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) { mean[i] = stats[i]; sd[i] = stats[C + i]; }
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % DESC) / 49;
-        const float m = c == 0 ? mean[0] : (c == 1 ? mean[1] : mean[2]);
-        const float s = c == 0 ? sd[0] : (c == 1 ? sd[1] : sd[2]);
+        const int c = (int)(idx % DESC) / PATCH;
+        float m = mean[C - 1], s = sd[C - 1];
+#pragma unroll
+        for (int i = C - 2; i >= 0; --i) { m = c == i ? mean[i] : m; s = c == i ? sd[i] : s; }
         desc[idx] = (desc[idx] - m) / s;
     }
 }
@@ -194,24 +217,58 @@ __global__ __launch_bounds__(256) void swd_l1_final_kernel(const double* __restr
 // ------------------------------------------------------------------------------------------------- projection
 // out[d][m] = sum_k desc[m][k] * dirs[k][d].  The MFMA's row index is the direction and its column index the descriptor, so one
 // accumulator register of a lane half is 32 consecutive floats of an output row: the transposed store is coalesced as it stands.
-//   A operand (lane l): dirs[k = 2s + (l>>5)][d = l&31]   -- read from global (the whole [147,K] block is 74 KB and stays in cache)
+//   A operand (lane l): dirs[k = 2s + (l>>5)][d = l&31]   -- read from global (the whole [49 C,K] block is at most 98 KB and stays in cache)
 //   B operand (lane l): desc[m = l&31][k = 2s + (l>>5)]   -- from LDS: the workgroup's 128 rows are one contiguous span of desc, copied
-//                                                            flat; the row stride 147 is odd, so the 32 rows of one lane half fall in
-//                                                            32 different banks (the other half reads one float further on; whether
-//                                                            the two halves collide has not been measured)
-// K = 147 is padded to 148 with zeros on both operands.  A wave owns 32 descriptors x up to 128 directions (4 accumulators).
+//                                                            flat, so the row stride is 49 C floats.  A lane half reads 32 rows at
+//                                                            one k.  Padding the even strides 98 and 196 to 99 and 197, which puts
+//                                                            those rows in 32 different banks, measured the same time to 0.1 %
+//                                                            (docs/experiments_swd.md): the B reads are not what the kernel waits on.
+// An odd descriptor length is padded to the next even one with zeros on both operands.  A wave owns 32 descriptors x up to 128
+// directions (4 accumulators).  The descriptor length is a template parameter: the k loop has a constant trip count.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// The copy of a FULL workgroup's span from a 16-byte aligned address: N4 float4 per workgroup, at least eight loads in flight per thread before
+// the first store (a load per iteration that is waited for before the next is what the plain loop compiles to: one memory latency per
+// 256 floats).  Every trip count is a constant, so the groups unroll whole.
+template <int N4>
+__device__ __forceinline__ void fill_full(float* __restrict__ sd, const float* __restrict__ src)
+{
+    const float4* s4 = reinterpret_cast<const float4*>(src);
+    float4* d4 = reinterpret_cast<float4*>(sd);
+    constexpr int IT = N4 / 256;
+#pragma unroll
+    for (int b = 0; b < IT; b += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (b + u < IT) v[u] = s4[(b + u) * 256 + threadIdx.x];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (b + u < IT) d4[(b + u) * 256 + threadIdx.x] = v[u];
+    }
+    if (N4 % 256) {
+        const int i = IT * 256 + threadIdx.x;
+        if (i < N4) d4[i] = s4[i];
+    }
+}
+
+template <int C>
 __global__ __launch_bounds__(256) void swd_project_kernel(const float* __restrict__ desc, const float* __restrict__ dirs,
                                                           float* __restrict__ out, long long M, int K)
 {
-    extern __shared__ float sd[];                       // [PJ_M][147]
+    constexpr int DESC = PATCH * C;
+    extern __shared__ float4 sd4[];                     // [PJ_M][DESC] floats (declared float4 for its alignment)
+    float* sd = reinterpret_cast<float*>(sd4);
     const long long m0 = (long long)blockIdx.x * PJ_M;
     const int d0 = blockIdx.y * PJ_K;
     const long long left = M - m0;
     const int cnt = (int)(left < PJ_M ? left : PJ_M) * DESC;
     const float* src = desc + (size_t)m0 * DESC;
-    for (int i = threadIdx.x; i < PJ_M * DESC; i += 256) sd[i] = i < cnt ? src[i] : 0.f;
+    if (left >= PJ_M && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+        fill_full<PJ_M * DESC / 4>(sd, src);
+    } else {                                            // the ragged last workgroup, or a base that is not 16-byte aligned
+        for (int i = threadIdx.x; i < PJ_M * DESC; i += 256) sd[i] = i < cnt ? src[i] : 0.f;
+    }
     __syncthreads();
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
@@ -226,7 +283,7 @@ __global__ __launch_bounds__(256) void swd_project_kernel(const float* __restric
 #pragma unroll 2
     for (int s = 0; s < (DESC + 1) / 2; ++s) {
         const int k = 2 * s + h;
-        const bool kin = k < DESC;
+        const bool kin = (DESC & 1) ? k < DESC : true;
         const float b = kin ? brow[k] : 0.f;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -357,51 +414,109 @@ extern "C" int pg_lap_up_sub(const float* fine, const float* coarse, float* out,
     return (int)hipGetLastError();
 }
 
-extern "C" int pg_swd_gather(const float* level, const int32_t* centres, float* out, int64_t ndesc, int P, int S,
-                             int64_t row_offset, int64_t out_rows, pg_stream_t stream)
+// ------------------------------------------------------------------------------------------------- descriptor entry points
+// One body per step, instantiated for C = 1..4; the entry points of pggan_hip.h are C = 3, those of pggan_hip_swd.h pick by argument.
+namespace {
+
+template <int C>
+int gather_c(const float* level, const int32_t* centres, float* out, int64_t ndesc, int P, int S, int64_t row_offset, int64_t out_rows,
+             pg_stream_t stream)
 {
     if (!level || !centres || !out || ndesc <= 0 || P <= 0 || S < 7 || row_offset < 0 || row_offset + ndesc > out_rows) return PG_E_ARG;
-    hipLaunchKernelGGL(swd_gather_kernel, dim3(grid_for(ndesc * DESC, 256, 65536)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(swd_gather_kernel<C>, dim3(grid_for(ndesc * (PATCH * C), 256, 65536)), dim3(256), 0, (hipStream_t)stream,
                        level, centres, out, (long long)ndesc, P, S, (long long)row_offset);
     return (int)hipGetLastError();
 }
 
-extern "C" int pg_swd_channel_stats(const float* desc, int64_t M, double* partials, float* stats, pg_stream_t stream)
+template <int C>
+int channel_stats_c(const float* desc, int64_t M, double* partials, float* stats, pg_stream_t stream)
 {
     if (!desc || !partials || !stats || M <= 0) return PG_E_ARG;
-    const int blocks = grid_for(M * DESC, 256 * 8, RED_BLOCKS);
-    hipLaunchKernelGGL(swd_stats_partial_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, desc, (long long)M * DESC, partials);
-    hipLaunchKernelGGL(swd_stats_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, blocks, (long long)M, stats);
+    const long long total = (long long)M * (PATCH * C);
+    const int blocks = grid_for(total, 256 * 8, RED_BLOCKS);
+    hipLaunchKernelGGL(swd_stats_partial_kernel<C>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, desc, total, partials);
+    hipLaunchKernelGGL(swd_stats_final_kernel<C>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, blocks, (long long)M, stats);
     return (int)hipGetLastError();
 }
 
-extern "C" int pg_swd_normalize(float* desc, int64_t M, const float* stats, pg_stream_t stream)
+template <int C>
+int normalize_c(float* desc, int64_t M, const float* stats, pg_stream_t stream)
 {
     if (!desc || !stats || M <= 0) return PG_E_ARG;
-    hipLaunchKernelGGL(swd_normalize_kernel, dim3(grid_for(M * DESC, 256, 65536)), dim3(256), 0, (hipStream_t)stream,
-                       desc, (long long)M * DESC, stats);
+    const long long total = (long long)M * (PATCH * C);
+    hipLaunchKernelGGL(swd_normalize_kernel<C>, dim3(grid_for(total, 256, 65536)), dim3(256), 0, (hipStream_t)stream, desc, total, stats);
     return (int)hipGetLastError();
 }
 
-extern "C" int pg_swd_project(const float* desc, const float* dirs, float* out, int64_t M, int K, pg_stream_t stream)
+template <int C>
+int project_c(const float* desc, const float* dirs, float* out, int64_t M, int K, pg_stream_t stream)
 {
     if (!desc || !dirs || !out || M <= 0 || K <= 0) return PG_E_ARG;
     const long long gx = (M + PJ_M - 1) / PJ_M, gy = (K + PJ_K - 1) / PJ_K;
     if (gx > 0x7fffffffLL || gy > 65535) return PG_E_UNSUP;
-    const size_t smem = (size_t)PJ_M * DESC * sizeof(float);
-    static std::atomic<uint64_t> smem_set{0};           // devices (by ordinal) on which the kernel's LDS limit has been raised
+    const size_t smem = (size_t)PJ_M * (PATCH * C) * sizeof(float);
+    static std::atomic<uint64_t> smem_set{0};           // devices (by ordinal) on which THIS instantiation's LDS limit has been raised
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return (int)e;
     const uint64_t bit = dev < 64 ? 1ull << dev : 0;
     if (!(smem_set.load(std::memory_order_relaxed) & bit) || !bit) {
-        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(swd_project_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(swd_project_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
             e != hipSuccess)
             return (int)e;
         smem_set.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(swd_project_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), smem, (hipStream_t)stream,
+    hipLaunchKernelGGL(swd_project_kernel<C>, dim3((unsigned)gx, (unsigned)gy), dim3(256), smem, (hipStream_t)stream,
                        desc, dirs, out, (long long)M, K);
     return (int)hipGetLastError();
+}
+
+// fn<C>(args...) for the run-time C; PG_E_ARG outside 1 .. PG_SWD_MAX_CHANNELS
+#define PG_SWD_BY_CHANNELS(C, fn, ...)                                                                                                 \
+    ((C) == 1 ? fn<1>(__VA_ARGS__) : (C) == 2 ? fn<2>(__VA_ARGS__) : (C) == 3 ? fn<3>(__VA_ARGS__) : (C) == 4 ? fn<4>(__VA_ARGS__) : PG_E_ARG)
+static_assert(PG_SWD_MAX_CHANNELS == 4, "PG_SWD_BY_CHANNELS lists the instantiations");
+
+}  // namespace
+
+extern "C" int pg_swd_gather(const float* level, const int32_t* centres, float* out, int64_t ndesc, int P, int S,
+                             int64_t row_offset, int64_t out_rows, pg_stream_t stream)
+{
+    return gather_c<3>(level, centres, out, ndesc, P, S, row_offset, out_rows, stream);
+}
+
+extern "C" int pg_swd_channel_stats(const float* desc, int64_t M, double* partials, float* stats, pg_stream_t stream)
+{
+    return channel_stats_c<3>(desc, M, partials, stats, stream);
+}
+
+extern "C" int pg_swd_normalize(float* desc, int64_t M, const float* stats, pg_stream_t stream)
+{
+    return normalize_c<3>(desc, M, stats, stream);
+}
+
+extern "C" int pg_swd_project(const float* desc, const float* dirs, float* out, int64_t M, int K, pg_stream_t stream)
+{
+    return project_c<3>(desc, dirs, out, M, K, stream);
+}
+
+extern "C" int pg_swd_gather_c(const float* level, const int32_t* centres, float* out, int64_t ndesc, int P, int C, int S,
+                               int64_t row_offset, int64_t out_rows, pg_stream_t stream)
+{
+    return PG_SWD_BY_CHANNELS(C, gather_c, level, centres, out, ndesc, P, S, row_offset, out_rows, stream);
+}
+
+extern "C" int pg_swd_channel_stats_c(const float* desc, int64_t M, int C, double* partials, float* stats, pg_stream_t stream)
+{
+    return PG_SWD_BY_CHANNELS(C, channel_stats_c, desc, M, partials, stats, stream);
+}
+
+extern "C" int pg_swd_normalize_c(float* desc, int64_t M, int C, const float* stats, pg_stream_t stream)
+{
+    return PG_SWD_BY_CHANNELS(C, normalize_c, desc, M, stats, stream);
+}
+
+extern "C" int pg_swd_project_c(const float* desc, const float* dirs, float* out, int64_t M, int C, int K, pg_stream_t stream)
+{
+    return PG_SWD_BY_CHANNELS(C, project_c, desc, dirs, out, M, K, stream);
 }
 
 extern "C" int pg_swd_sort_rows(float* buf, float* tmp, int K, int64_t M, pg_stream_t stream)

@@ -10,6 +10,11 @@ no pretrained network (``MultiScaleSSIM`` below is the other).  The reference ha
 4. ``dir_repeats`` times: project both sets on ``dirs_per_repeat`` unit directions, sort every projection, take the mean absolute
    difference of the sorted values (``ops.swd_project`` / ``swd_sort_rows_`` / ``swd_l1``); the value is the average x 1000.
 
+``ChannelSlicedWasserstein`` is the same metric for networks with C = 1 .. 4 image channels -- the one-channel (``'abslog'``) and
+two-channel (``'magif'``) spectrogram generators among them: descriptors are Cx7x7 = 49 C floats, every channel is normalised over the
+whole set, directions are unit vectors of length 49 C (``ops.swd_gather_c`` / ``swd_normalize_c_`` / ``swd_project_c``).  For C != 3 it
+is unpinned, this project's extension of the paper's 7x7x3 descriptor; with C = 3 it equals ``SlicedWasserstein`` bit for bit.
+
 All randomness (patch centres, directions) comes from the object's own seeded CPU generator: the trainer's random stream is not touched
 and the same seed gives the same metric.  The two sets use the SAME patch centres (image i of one set is sampled where image i of the
 other is), so a set measured against itself gives exactly 0.
@@ -17,7 +22,7 @@ other is), so a set measured against itself gives exactly 0.
 ``MultiScaleSSIM``: the multi-scale structural similarity (Wang, Simoncelli & Bovik 2003) between pairs of GENERATED images, which
 the paper uses to detect loss of variation: a generator that collapses onto a few images keeps a fair SWD for a while, but its
 independent samples start to resemble each other and the mean MS-SSIM rises.  It is defined per channel, so one-channel (spectrogram)
-networks, which ``SlicedWasserstein`` refuses, have a metric too.  Definition: DESIGN.md section 7 (``ops.msssim_pairs``); it draws
+networks are measured like RGB ones.  Definition: DESIGN.md section 7 (``ops.msssim_pairs``); it draws
 no random numbers, so it has no seed.  Like the SWD it is UNPINNED: no vectors of the authors' implementation are at hand, the
 values are comparable within a growth stage and between runs of this project.
 
@@ -48,21 +53,39 @@ def swd_levels(resolution):
     return levels
 
 
-class SlicedWasserstein(object):
-    """Feed ``num_images`` real and as many generated fp32 ``[n,3,R,R]`` device batches (any split), then ``result()``.
+def swd_draws(levels, rows, dir_repeats, width, dirs_per_repeat, seed):
+    """The random part of the metric, from ONE CPU generator seeded ``seed``: first the patch centres (per level an int32 tensor
+    ``[rows, 2]`` of (x, y) in [3, level - 4]), then the directions (fp32 ``[dir_repeats, width, dirs_per_repeat]``, unit columns,
+    normalised in fp64).  The centres do not depend on ``width``."""
+    gen = torch.Generator(device='cpu')
+    gen.manual_seed(int(seed))
+    centres = [torch.randint(3, s - 3, (rows, 2), generator=gen, dtype=torch.int32) for s in levels]
+    for c, s in zip(centres, levels):                            # checked here, on the host, once: _feed gathers with check_range=False
+        if int(c.min()) < 3 or int(c.max()) > s - 4:
+            raise ValueError('patch centres outside [3, %d] at level %d' % (s - 4, s))
+    d = torch.randn(dir_repeats, width, dirs_per_repeat, generator=gen, dtype=torch.float32).double()
+    return centres, (d / d.pow(2).sum(dim=1, keepdim=True).sqrt()).float().contiguous()
+
+
+class ChannelSlicedWasserstein(object):
+    """Feed ``num_images`` real and as many generated fp32 ``[n,C,R,R]`` device batches (any split), then ``result()``;
+    C = ``num_channels`` in 1 .. ``ops.SWD_MAX_CHANNELS``.  Unpinned for C != 3: this project's extension of the paper's 7x7x3
+    descriptor.
 
     ``centres``: list (one per level) of int32 CPU tensors ``[num_images * patches_per_image, 2]`` of (x, y);
-    ``directions``: fp32 CPU tensor ``[dir_repeats, 147, dirs_per_repeat]`` with unit columns.
+    ``directions``: fp32 CPU tensor ``[dir_repeats, 49 * C, dirs_per_repeat]`` with unit columns.  Centres, then directions, are
+    drawn from one CPU generator seeded ``seed``: with ``num_channels=3`` they are ``SlicedWasserstein``'s of the same seed.
     ``phase_hook``: measurement aid (tools/swd_time.py), None by default; when set, ``hook(phase, fn, *args, **kw) -> fn(*args, **kw)``
     runs every ``ops`` call of an evaluation, ``phase`` one of ``PHASES``."""
 
     PHASES = ('pyramid', 'gather', 'normalise', 'project', 'sort', 'l1')
+    _OPS = ('swd_gather_c', 'swd_normalize_c_', 'swd_project_c')          # names in ``ops`` of the three steps that see the channels
 
-    def __init__(self, resolution, num_images, patches_per_image=128, dir_repeats=4, dirs_per_repeat=128, seed=0, num_channels=3,
+    def __init__(self, resolution, num_images, num_channels, patches_per_image=128, dir_repeats=4, dirs_per_repeat=128, seed=0,
                  device=None):
         self.levels = swd_levels(resolution)
-        if int(num_channels) != 3:
-            raise ValueError('the descriptors are 3x7x7: single-channel (or any non-RGB) networks are out of contract')
+        self.num_channels = self._channels(num_channels)
+        self.desc_width = ops.SWD_PATCH * self.num_channels
         for name, v in (('num_images', num_images), ('patches_per_image', patches_per_image), ('dir_repeats', dir_repeats),
                         ('dirs_per_repeat', dirs_per_repeat)):
             if int(v) != v or v < 1:
@@ -73,20 +96,13 @@ class SlicedWasserstein(object):
         if self.rows > ops.SWD_SORT_MAX_M:
             raise ValueError('num_images * patches_per_image = %d descriptors per level; the sort takes at most %d'
                              % (self.rows, ops.SWD_SORT_MAX_M))
-        gen = torch.Generator(device='cpu')
-        gen.manual_seed(self.seed)
-        self.centres = [torch.randint(3, s - 3, (self.rows, 2), generator=gen, dtype=torch.int32) for s in self.levels]
-        for c, s in zip(self.centres, self.levels):              # checked here, on the host, once: _feed gathers with check_range=False
-            if int(c.min()) < 3 or int(c.max()) > s - 4:
-                raise ValueError('patch centres outside [3, %d] at level %d' % (s - 4, s))
-        d = torch.randn(self.dir_repeats, ops.SWD_DESC, self.dirs_per_repeat, generator=gen, dtype=torch.float32).double()
-        self.directions = (d / d.pow(2).sum(dim=1, keepdim=True).sqrt()).float().contiguous()
+        self.centres, self.directions = swd_draws(self.levels, self.rows, self.dir_repeats, self.desc_width, self.dirs_per_repeat, self.seed)
         ops.require_gpu()
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         dev = self.device
         self._centres_dev = [c.to(dev) for c in self.centres]
         self._dirs_dev = self.directions.to(dev)
-        self._desc = {which: [torch.empty((self.rows, ops.SWD_DESC), device=dev, dtype=torch.float32) for _ in self.levels]
+        self._desc = {which: [torch.empty((self.rows, self.desc_width), device=dev, dtype=torch.float32) for _ in self.levels]
                       for which in ('real', 'fake')}
         # work buffers of ONE repeat: the two projected sets and the scratch of the merge passes
         shape = (self.dirs_per_repeat, self.rows)
@@ -94,6 +110,12 @@ class SlicedWasserstein(object):
         self._tmp = torch.empty(shape, device=dev, dtype=torch.float32) if self.rows > ops.SWD_SORT_LDS_ROW else None
         self.phase_hook = None
         self.reset()
+
+    @staticmethod
+    def _channels(num_channels):
+        if isinstance(num_channels, bool) or int(num_channels) != num_channels or not 1 <= num_channels <= ops.SWD_MAX_CHANNELS:
+            raise ValueError('num_channels must be an integer in 1 .. %d, got %r' % (ops.SWD_MAX_CHANNELS, num_channels))
+        return int(num_channels)
 
     def _op(self, phase, fn, *args, **kw):
         return fn(*args, **kw) if self.phase_hook is None else self.phase_hook(phase, fn, *args, **kw)
@@ -104,17 +126,18 @@ class SlicedWasserstein(object):
         self._result = None
 
     def _feed(self, which, batch):
-        if not torch.is_tensor(batch) or batch.dim() != 4 or tuple(batch.shape[1:]) != (3, self.resolution, self.resolution):
-            raise ValueError('expected a batch [n,3,%d,%d], got %s' % (self.resolution, self.resolution,
-                                                                       tuple(batch.shape) if torch.is_tensor(batch) else type(batch)))
+        if not torch.is_tensor(batch) or batch.dim() != 4 \
+                or tuple(batch.shape[1:]) != (self.num_channels, self.resolution, self.resolution):
+            raise ValueError('expected a batch [n,%d,%d,%d], got %s' % (self.num_channels, self.resolution, self.resolution,
+                                                                        tuple(batch.shape) if torch.is_tensor(batch) else type(batch)))
         n, fed = batch.shape[0], self._fed[which]
         if n < 1 or fed + n > self.num_images:
             raise ValueError('%d %s images fed, %d more would exceed num_images = %d' % (fed, which, n, self.num_images))
         if self._result is not None:
             raise RuntimeError('result() was taken: reset() before feeding again')
-        P = self.patches
+        P, gather = self.patches, getattr(ops, self._OPS[0])
         for li, level in enumerate(self._op('pyramid', ops.lap_pyramid, batch)):
-            self._op('gather', ops.swd_gather, level, self._centres_dev[li][fed * P:(fed + n) * P], P, self._desc[which][li], fed * P,
+            self._op('gather', gather, level, self._centres_dev[li][fed * P:(fed + n) * P], P, self._desc[which][li], fed * P,
                      check_range=False)
         self._fed[which] = fed + n
 
@@ -134,19 +157,39 @@ class SlicedWasserstein(object):
             if not self.complete:
                 raise RuntimeError('fed %d real and %d fake images of %d' % (self._fed['real'], self._fed['fake'], self.num_images))
             dists = []
+            normalize_, project = getattr(ops, self._OPS[1]), getattr(ops, self._OPS[2])
             for li in range(len(self.levels)):
                 real, fake = self._desc['real'][li], self._desc['fake'][li]
-                self._op('normalise', ops.swd_normalize_, real)
-                self._op('normalise', ops.swd_normalize_, fake)
+                self._op('normalise', normalize_, real)
+                self._op('normalise', normalize_, fake)
                 for r in range(self.dir_repeats):
                     for desc, proj in ((real, self._proj[0]), (fake, self._proj[1])):
-                        self._op('project', ops.swd_project, desc, self._dirs_dev[r], out=proj)
+                        self._op('project', project, desc, self._dirs_dev[r], out=proj)
                         self._op('sort', ops.swd_sort_rows_, proj, self._tmp)
                     dists.append(self._op('l1', ops.swd_l1, self._proj[0], self._proj[1]))
             d = torch.stack(dists).cpu().double().view(len(self.levels), self.dir_repeats)
             swd = [float(v) for v in (d.mean(dim=1) * 1e3)]
             self._result = {'levels': list(self.levels), 'swd': swd, 'mean': sum(swd) / len(swd)}
         return self._result
+
+
+class SlicedWasserstein(ChannelSlicedWasserstein):
+    """The paper's form, three channels: feed ``num_images`` real and as many generated fp32 ``[n,3,R,R]`` device batches (any split),
+    then ``result()``.  ``directions`` is ``[dir_repeats, 147, dirs_per_repeat]``; everything else is ``ChannelSlicedWasserstein``'s.
+    Any other ``num_channels`` is refused here: ``ChannelSlicedWasserstein`` takes 1 .. 4."""
+
+    _OPS = ('swd_gather', 'swd_normalize_', 'swd_project')
+
+    def __init__(self, resolution, num_images, patches_per_image=128, dir_repeats=4, dirs_per_repeat=128, seed=0, num_channels=3,
+                 device=None):
+        super(SlicedWasserstein, self).__init__(resolution, num_images, num_channels, patches_per_image=patches_per_image,
+                                                dir_repeats=dir_repeats, dirs_per_repeat=dirs_per_repeat, seed=seed, device=device)
+
+    @staticmethod
+    def _channels(num_channels):
+        if int(num_channels) != 3:
+            raise ValueError('the descriptors are 3x7x7: single-channel (or any non-RGB) networks are out of contract')
+        return 3
 
 
 class MultiScaleSSIM(object):

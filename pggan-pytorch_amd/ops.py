@@ -1001,6 +1001,78 @@ def swd_project(desc, dirs, out=None):
     return out
 
 
+# The same three steps for C = 1 .. 4 channels (include/pggan_hip_swd.h): descriptors of 49 C floats.  UNPINNED for C != 3: this
+# project's extension of the paper's 7x7x3 descriptor.  C = 3 runs the kernels of the three wrappers above and gives their bits.
+_SWD_C = {name[len('PG_SWD_'):]: value for name, value in _lib.SWD_CONSTANTS.items() if name.startswith('PG_SWD_')}   # the addition's own table
+SWD_PATCH = _SWD_C['PATCH']                                    # 7 x 7: floats of one channel of a descriptor
+SWD_MAX_CHANNELS = _SWD_C['MAX_CHANNELS']
+
+
+def swd_channels(width, what='descriptor width'):
+    """The channel count C of a descriptor of ``width`` = 49 C floats, C in 1 .. SWD_MAX_CHANNELS; anything else is a ValueError."""
+    width = int(width)
+    if width % SWD_PATCH or not 1 <= width // SWD_PATCH <= SWD_MAX_CHANNELS:
+        raise ValueError('%s: %d is not %d * C for C in 1 .. %d' % (what, width, SWD_PATCH, SWD_MAX_CHANNELS))
+    return width // SWD_PATCH
+
+
+def swd_gather_c(level, centres, P, out, row_offset, check_range=True):
+    """``swd_gather`` for a level [N,C,S,S] with C in 1 .. 4: rows ``row_offset .. row_offset + N*P`` of ``out`` [M,49*C] <- the Cx7x7
+    neighbourhoods around ``centres``, rows in (channel, dy, dx) order.  The channel count is the level's; an ``out`` of another
+    width is a ValueError."""
+    _f32_dev(level, 'swd_gather_c level', 4)
+    _f32_dev(out, 'swd_gather_c out', 2)
+    N, C, S, W = level.shape
+    P, row_offset = int(P), int(row_offset)
+    if N < 1 or not 1 <= C <= SWD_MAX_CHANNELS or S != W or S < 7:
+        raise ValueError('swd_gather_c: expected a level [N,C,S,S] with N >= 1, 1 <= C <= %d and S >= 7, got %s'
+                         % (SWD_MAX_CHANNELS, tuple(level.shape)))
+    if not torch.is_tensor(centres) or not centres.is_cuda or centres.dtype != torch.int32 or not centres.is_contiguous() \
+            or P < 1 or tuple(centres.shape) != (N * P, 2):
+        raise ValueError('swd_gather_c: expected contiguous int32 device centres [%d,2]' % (N * P))
+    if out.shape[1] != SWD_PATCH * C or row_offset < 0 or row_offset + N * P > out.shape[0]:
+        raise ValueError('swd_gather_c: rows %d..%d of %d floats do not fit out %s'
+                         % (row_offset, row_offset + N * P, SWD_PATCH * C, tuple(out.shape)))
+    if check_range:
+        lo, hi = int(centres.min()), int(centres.max())
+        if lo < 3 or hi > S - 4:
+            raise ValueError('swd_gather_c: centres span %d..%d, outside [3, %d] of a %dx%d level' % (lo, hi, S - 4, S, S))
+    _lib.call('pg_swd_gather_c', _p(level), centres.data_ptr(), _p(out), N * P, P, C, S, row_offset, out.shape[0], _stream())
+    return out
+
+
+def swd_normalize_c_(desc):
+    """``swd_normalize_`` for ``desc`` [M,49*C], C in 1 .. 4 (from the width): every channel to zero mean and unit population
+    standard deviation over all rows, in place."""
+    _f32_dev(desc, 'swd_normalize_c_', 2)
+    C = swd_channels(desc.shape[1], 'swd_normalize_c_')
+    if desc.shape[0] < 1:
+        raise ValueError('swd_normalize_c_: expected [M,%d] with M >= 1, got %s' % (desc.shape[1], tuple(desc.shape)))
+    s = _stream()
+    partials = _swd_partials(desc.device, 2 * C)
+    stats = torch.empty(2 * C, device=desc.device, dtype=torch.float32)
+    _lib.call('pg_swd_channel_stats_c', _p(desc), desc.shape[0], C, partials.data_ptr(), _p(stats), s)
+    _lib.call('pg_swd_normalize_c', _p(desc), desc.shape[0], C, _p(stats), s)
+    return desc
+
+
+def swd_project_c(desc, dirs, out=None):
+    """``swd_project`` for ``desc`` [M,49*C] x ``dirs`` [49*C,K] -> [K,M], C in 1 .. 4 (from the widths, which must agree)."""
+    _f32_dev(desc, 'swd_project_c desc', 2)
+    _f32_dev(dirs, 'swd_project_c dirs', 2)
+    M, K = desc.shape[0], dirs.shape[1]
+    C = swd_channels(desc.shape[1], 'swd_project_c desc')
+    if dirs.shape[0] != desc.shape[1] or M < 1 or K < 1:
+        raise ValueError('swd_project_c: expected [M,%d] and [%d,K], got %s and %s'
+                         % (desc.shape[1], desc.shape[1], tuple(desc.shape), tuple(dirs.shape)))
+    if out is None:
+        out = torch.empty((K, M), device=desc.device, dtype=torch.float32)
+    elif tuple(_f32_dev(out, 'swd_project_c out', 2).shape) != (K, M):
+        raise ValueError('swd_project_c: out must be [%d,%d]' % (K, M))
+    _lib.call('pg_swd_project_c', _p(desc), _p(dirs), _p(out), M, C, K, _stream())
+    return out
+
+
 def swd_sort_rows_(buf, tmp=None):
     """Sort every row of ``buf`` [K,M] ascending, in place.  Rows longer than SWD_SORT_LDS_ROW need a scratch of buf's shape
     (``tmp``; allocated when not given)."""

@@ -366,17 +366,19 @@ class OutputGenerator(Evaluation):
 
 class SWDMonitor(Evaluation):
     """Quality metric per tick (``metrics.SlicedWasserstein``; the reference reports none): every ``swd_ticks`` ticks and at the end,
-    ``num_images`` real images from ``real_batch_fn(n)`` (fp32 device batches ``[n,3,R,R]`` at the current stage's resolution, e.g.
-    ``utils.prepare_real_batch`` of a dataset batch) are measured against as many of ``G.forward(sample_fn(n).cuda())``, ``minibatch``
+    ``num_images`` real images from ``real_batch_fn(n)`` (fp32 device batches ``[n,C,R,R]`` at the current stage's resolution, e.g.
+    ``utils.prepare_real_batch`` of a dataset batch or ``DeviceImageDataset.metric_batches()``) are measured against as many of ``G.forward(sample_fn(n).cuda())``, ``minibatch``
     at a time -- of the smoothed generator when the trainer keeps one, which is what the paper measures (``smoothed`` as in
     ``Evaluation``).  Writes ``stats['swd']``
     (the mean over the pyramid levels, x 1000) and one ``stats['swd_<res>']`` per level under the stat-dict convention of the other monitors.  Stages below 16x16 have no pyramid level: nothing is written there.  Rank 0
-    evaluates (replicas are identical).  ``metric_kwargs`` go to ``SlicedWasserstein`` (patches_per_image, dir_repeats,
+    evaluates (replicas are identical).  The channel count C comes from ``G.num_channels`` (3 where ``G`` has no such attribute): three
+    channels are measured by ``SlicedWasserstein``, 1, 2 and 4 -- the spectrogram networks -- by ``metrics.ChannelSlicedWasserstein``
+    (unpinned, this project's extension of the paper's 7x7x3 descriptor).  ``metric_kwargs`` go to ``SlicedWasserstein`` (patches_per_image, dir_repeats,
     dirs_per_repeat, seed).  One metric object (buffers, patch centres, directions) is alive at a time: a new stage drops the last
     stage's before it allocates its own (about 20 GB at the default size and 1024x1024).
 
-    The default period rests on an ESTIMATE, not on a measurement (docs/experiments_swd.md; no evaluation has been timed on the
-    device yet): 10-15 s per evaluation of 16384 images at the 1024x1024 stage, most of it the generator passes and the real
+    The default period rests on an ESTIMATE, not on a measurement (docs/experiments_swd.md; the metric's own kernels have been timed
+    there -- 2.6 s at 1024x1024 x 3 -- the generator passes and the real batches of an evaluation have not): 10-15 s per evaluation of 16384 images at the 1024x1024 stage, most of it the generator passes and the real
     batches.  Under 1 % of that stage's time (a tick of 1 kimg is about 3.3 s there) then needs 300-450 ticks between evaluations:
     400.  A run that wants the metric more often trades images for it (``num_images=2048, swd_ticks=50`` costs the same by the
     same estimate and is noisier).
@@ -393,11 +395,15 @@ class SWDMonitor(Evaluation):
         self.metric_kwargs = metric_kwargs
 
     def evaluate(self, tick):
-        from .metrics import SlicedWasserstein
-        resolution = 4 * 2 ** self.trainer.G.depth
+        from . import metrics
+        resolution, channels = 4 * 2 ** self.trainer.G.depth, int(getattr(self.trainer.G, 'num_channels', 3))
         if resolution < 16:
             return
-        metric = self.cached(resolution, lambda: SlicedWasserstein(resolution, self.num_images, **self.metric_kwargs))
+        if channels == 3:
+            make = lambda: metrics.SlicedWasserstein(resolution, self.num_images, **self.metric_kwargs)
+        else:
+            make = lambda: metrics.ChannelSlicedWasserstein(resolution, self.num_images, channels, **self.metric_kwargs)
+        metric = self.cached((resolution, channels), make)
         metric.reset()
         gen = self.generator()
         for start in range(0, self.num_images, self.minibatch):
