@@ -25,33 +25,11 @@
 
 #pragma clang fp contract(off)
 
-#include "fft_r2.h"
+#include "phase_common.h"
 
 namespace {
 
-using namespace fft_r2;
-
-static_assert(PG_PHASE_MIN_N == FFT_MIN_N && PG_PHASE_MAX_N == FFT_MAX_N, "the header states the transform's limits");
-
-constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_MAX_W = 1024;
-constexpr int SCAN_CHUNK = SCAN_MAX_W / SCAN_THREADS;
-
-constexpr double PI = 3.14159265358979323846;                              // numpy's np.pi
-
-__device__ __forceinline__ double phase_over_pi(double re, double im)
-{
-    return (re == 0.0 && im == 0.0) ? 0.0 : atan2(im, re) / PI;
-}
-
-__device__ __forceinline__ double wrap(double d) { return d - 2.0 * floor(d / 2.0 + 0.5); }
-
-__device__ __forceinline__ long long reflect(long long j, long long nsamp)
-{
-    if (j < 0) j = -j;                                                     // np.pad(mode='reflect'); nsamp > n_fft/2 keeps both in range
-    if (j >= nsamp) j = 2 * (nsamp - 1) - j;
-    return j;
-}
+using namespace phase_common;                                              // the frame pair, the bin separation, the row scan: shared with mel.hip
 
 // y [batch][nsamp], logmag / ifreq [batch][bins][frames]; grid (frames, batch)
 template <int MAXN>
@@ -61,26 +39,13 @@ __global__ __launch_bounds__(FFT_THREADS) void analyse_kernel(const float* __res
     __shared__ double re[MAXN], im[MAXN];
     __shared__ double twc[MAXN / 2], tws[MAXN / 2];
     const int t = blockIdx.x, b = blockIdx.y;
-    const int half = n_fft >> 1;
-    fill_twiddles(twc, tws, n_fft, half);
-    const float* yb = y + (size_t)b * nsamp;
-    for (int n = threadIdx.x; n < n_fft; n += FFT_THREADS) {
-        const double w = hann(twc, n, half);
-        const long long j = (long long)t * hop + n - half;                 // index into the unpadded signal, as gl_pieces_kernel
-        re[n] = w * (double)yb[reflect(j, nsamp)];
-        im[n] = t > 0 ? w * (double)yb[reflect(j - hop, nsamp)] : 0.0;
-    }
-    __syncthreads();
-    for (int s = logn - 1; s >= 0; --s) fft_stage<true>(re, im, twc, tws, s, logn, half);
+    transform_frame_pair(re, im, twc, tws, y + (size_t)b * nsamp, nsamp, t, n_fft, logn, hop);
     for (int k = threadIdx.x; k < bins; k += FFT_THREADS) {
-        const int p = brev_pos(k, logn), pm = brev_pos((n_fft - k) & (n_fft - 1), logn);
-        const double zr = re[p], zi = im[p], mr = re[pm], mi = im[pm];
-        const double xr = (zr + mr) * 0.5, xi = (zi - mi) * 0.5;           // frame t
-        double prev = 0.0;                                                 // phi[k][-1] = 0
-        if (t > 0) prev = phase_over_pi((zi + mi) * 0.5, (mr - zr) * 0.5); // frame t - 1
+        double mag, fr;
+        separate_bin(re, im, k, t, n_fft, logn, &mag, &fr);
         const size_t o = ((size_t)b * bins + k) * (size_t)frames + t;
-        logmag[o] = log1p(hypot(xr, xi));
-        ifreq[o] = wrap(phase_over_pi(xr, xi) - prev);
+        logmag[o] = log1p(mag);
+        ifreq[o] = fr;
     }
 }
 
@@ -99,12 +64,9 @@ __global__ __launch_bounds__(256) void quantise_kernel(const double* __restrict_
     }
 }
 
-struct Range { double lo_in, scale, lo_out; };                             // adjust_dynamic_range (utils.py:24-30), resolved on the host
-
-// img [n][2][H][W], spec [n][W][H + 1] complex; grid (H + 1, n): workgroup (k, b) owns the row of W values of bin k, the workgroup of
-// bin H writes the zero Nyquist bin.  Thread i sums its `chunk` = max(1, W / 256) consecutive IF values, the partial sums are scanned
-// in LDS (Hillis-Steele, two buffers), then every value gets the sum of the chunks before it.  csum [n][H][W] (may be NULL) receives
-// the running sum itself, the phase in units of pi before it is reduced by sincospi.
+// img [n][2][H][W], spec [n][W][H + 1] complex; grid (H + 1, n): workgroup (k, b) owns the row of W values of bin k (scan_row of
+// csrc/phase_common.h), the workgroup of bin H writes the zero Nyquist bin.  csum [n][H][W] (may be NULL) receives the running sum
+// itself, the phase in units of pi before it is reduced by sincospi.
 __global__ __launch_bounds__(SCAN_THREADS) void spectrum_kernel(const float* __restrict__ img, double* __restrict__ spec,
                                                                 double* __restrict__ csum, int H, int W, Range rm, Range rf)
 {
@@ -112,50 +74,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void spectrum_kernel(const float* __r
     const int k = blockIdx.x, b = blockIdx.y;
     double* sb = spec + (size_t)b * W * (size_t)(H + 1) * 2;
     if (k == H) {
-        for (int t = threadIdx.x; t < W; t += SCAN_THREADS) {
-            double* o = sb + ((size_t)t * (H + 1) + H) * 2;
-            o[0] = 0.0; o[1] = 0.0;
-        }
+        zero_nyquist(sb, H, W);
         return;
     }
     const float* mrow = img + (((size_t)b * 2 + 0) * H + k) * (size_t)W;
     const float* frow = img + (((size_t)b * 2 + 1) * H + k) * (size_t)W;
-    const int chunk = W > SCAN_THREADS ? W / SCAN_THREADS : 1;             // W is a power of two: 1, 2 or 4
-    const int t0 = threadIdx.x * chunk;
-    double c[SCAN_CHUNK];
-    double run = 0.0;
-#pragma unroll
-    for (int i = 0; i < SCAN_CHUNK; ++i) {
-        if (i < chunk && t0 + i < W) {
-            const double q = ((double)frow[t0 + i] - rf.lo_in) * rf.scale + rf.lo_out;
-            run = run + (q / (double)(PG_PHASE_IF_LEVELS / 2) - 1.0);
-        }
-        c[i] = run;
-    }
-    part[0][threadIdx.x] = t0 < W ? run : 0.0;
-    __syncthreads();
-    int cur = 0;
-#pragma unroll
-    for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-        const double v = part[cur][threadIdx.x];
-        part[cur ^ 1][threadIdx.x] = threadIdx.x >= d ? part[cur][threadIdx.x - d] + v : v;
-        cur ^= 1;
-        __syncthreads();
-    }
-    const double before = threadIdx.x > 0 ? part[cur][threadIdx.x - 1] : 0.0;
-#pragma unroll
-    for (int i = 0; i < SCAN_CHUNK; ++i) {
-        if (i < chunk && t0 + i < W) {
-            const double v = ((double)mrow[t0 + i] - rm.lo_in) * rm.scale + rm.lo_out;
-            const double mag = expm1(fmax(v, 0.0));                        // a generator can undershoot; a negative magnitude would flip the phase
-            const double ph = before + c[i];
-            if (csum) csum[((size_t)b * H + k) * (size_t)W + t0 + i] = ph;
-            double sn, cs;
-            sincospi(ph, &sn, &cs);
-            double* o = sb + ((size_t)(t0 + i) * (H + 1) + k) * 2;
-            o[0] = mag * cs; o[1] = mag * sn;
-        }
-    }
+    scan_row(part, sb, csum, b, k, H, W, [&](int t) { return if_of_level(rf(frow[t])); }, [&](int t) { return mag_of_value(rm(mrow[t])); });
 }
 
 // spec [batch][frames][n_fft/2 + 1] complex, pieces [batch][frames][n_fft]; grid (frames, batch).  The second half of gl_pieces_kernel

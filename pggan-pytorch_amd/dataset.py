@@ -521,17 +521,20 @@ class DeviceStripDataset(object):
 
     # --------------------------------------------------------------------------------------------- construction
     @classmethod
-    def from_waveforms(cls, signals, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None, **kw):
+    def from_waveforms(cls, signals, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None, sample_rate=None, mel_rows=None, **kw):
         """The dataset of a list of waveforms of different lengths (``[nsamp]`` or ``[nsamp, channels]``, numpy arrays or tensors):
-        one strip per recording from ``sound.spectrogram_strip_u8``.  A waveform that gives fewer than n_fft/2 usable frames is a
+        one strip per recording from ``sound.spectrogram_strip_u8``.  A waveform that gives fewer usable frames than the strip is
+        high -- n_fft/2, or ``mel_rows`` for img_mode='melif', whose ``sample_rate`` and ``mel_rows`` are passed through -- is a
         ValueError naming it."""
         from . import sound
+        table = sound._mel_arguments(img_mode, n_fft, sample_rate, mel_rows)    # (refuses sample_rate / mel_rows with another mode first)
+        side = int(n_fft) // 2 if table is None else table.rows
         strips = []
         for m, y in enumerate(signals):
-            if sound.strip_frames(int(y.shape[0]), hop_length, img_mode) < int(n_fft) // 2:
+            if sound.strip_frames(int(y.shape[0]), hop_length, img_mode) < side:
                 raise ValueError('waveform %d: %d samples give %d usable frames, a window needs %d'
-                                 % (m, y.shape[0], sound.strip_frames(int(y.shape[0]), hop_length, img_mode), int(n_fft) // 2))
-            strips.append(sound.spectrogram_strip_u8(y, n_fft, hop_length, img_mode, mag_range))
+                                 % (m, y.shape[0], sound.strip_frames(int(y.shape[0]), hop_length, img_mode), side))
+            strips.append(sound.spectrogram_strip_u8(y, n_fft, hop_length, img_mode, mag_range, sample_rate, mel_rows))
         return cls(strips, **kw)
 
     def _upload(self, strips):

@@ -10,6 +10,9 @@ post-processor with the reference's hook signature.
   * ``img_mode='magif'`` / ``mode='magif'`` — log-magnitude plus instantaneous frequency as a two-channel image (after Engel et al.
     2019, GANSynth): ``spectrogram_u8`` / ``spectrogram_stack_u8`` make the images (csrc/phase.hip), both savers
     turn them back into a waveform with one inverse STFT; the ``magif_*`` functions below are the definitions in numpy fp64.
+  * ``img_mode='melif'`` / ``mode='melif'`` — the same two channels on M mel-spaced rows made from the n_fft/2 >= M bins of a longer
+    transform (GANSynth's "IF-Mel + H"; DESIGN.md section 7, csrc/mel.hip): a 256^2 network can be fed from 1024 bins.  The warp is a
+    table of plain arrays (``phase.mel_table``); the ``melif_*`` functions below are the definitions in numpy fp64.
   * ``DeviceSoundSaver`` — the same files from the device: the spectrum, every Griffin-Lim round and the normalisation are the fp64
     HIP kernels of csrc/griffinlim.hip; only the float32 waveforms are copied back.  Opt-in: ``SoundSaver`` stays the default.
 
@@ -25,58 +28,86 @@ import numpy as np
 from .utils import adjust_dynamic_range
 
 
-def spectrogram_u8(signal, n_fft=1024, hop_length=128, img_mode='abslog', range_in=(0, 255), mag_range=None):
+MEL_SAMPLE_RATE = 16000               # the default ``sample_rate`` of img_mode='melif' (SoundSaver's default too)
+
+
+def _mel_arguments(img_mode, n_fft, sample_rate, mel_rows):
+    """The ``phase.MelTable`` of img_mode='melif' (``sample_rate`` defaults to 16000, ``mel_rows`` to n_fft/2), None for every other
+    mode -- where ``sample_rate`` and ``mel_rows`` are a ValueError, like ``mag_range``."""
+    if img_mode != 'melif':
+        if sample_rate is not None or mel_rows is not None:
+            raise ValueError("sample_rate and mel_rows belong to img_mode='melif' (got img_mode %r)" % (img_mode,))
+        return None
+    from . import phase
+    if isinstance(n_fft, bool) or int(n_fft) != n_fft:
+        raise ValueError('n_fft must be an integer, got %r' % (n_fft,))
+    return phase.mel_table(int(n_fft), int(n_fft) // 2 if mel_rows is None else mel_rows, MEL_SAMPLE_RATE if sample_rate is None else sample_rate)
+
+
+def spectrogram_u8(signal, n_fft=1024, hop_length=128, img_mode='abslog', range_in=(0, 255), mag_range=None, sample_rate=None,
+                   mel_rows=None):
     """Waveform (numpy array or tensor, ``[nsamp]`` or ``[nsamp, channels]``) -> uint8 device image: ``[1, n_fft/2, n_fft/2]``
     for the spectrogram modes 'abslog' (log(1 + |s|), dataset.py:296) and 'reallog' (log(1 + |Re s|) * sign(s), dataset.py:298,
     with numpy 1.13's complex sign = the sign of the real part), ``[1, 2^k, 2^k]`` for 'raw' (the waveform itself, dataset.py:289-291).
     Defaults as SoundImageDataset.__init__ (dataset.py:259-274).
 
     'magif' (this project's own): ``[2, n_fft/2, n_fft/2]``, log-magnitude stretched from the FIXED ``mag_range``
-    (default (0, log1p(n_fft/2))) and the instantaneous frequency on a circle of 256 levels; ``range_in`` is not used."""
+    (default (0, log1p(n_fft/2))) and the instantaneous frequency on a circle of 256 levels; ``range_in`` is not used.
+
+    'melif' (this project's own): ``[2, M, M]`` with M = ``mel_rows`` (a power of two, 4 <= M <= n_fft/2, default
+    n_fft/2) mel-spaced rows made from the n_fft/2 bins at ``sample_rate`` Hz (default 16000), the first M frames; otherwise as 'magif'."""
     import torch
     from . import ops
-    if img_mode not in ('abslog', 'reallog', 'raw', 'magif'):
-        raise ValueError("img_mode must be one of 'abslog', 'reallog', 'raw', 'magif' (got %r)" % (img_mode,))
-    if img_mode != 'magif' and mag_range is not None:
-        raise ValueError("mag_range belongs to img_mode='magif' (got img_mode %r)" % (img_mode,))
+    if img_mode not in ('abslog', 'reallog', 'raw', 'magif', 'melif'):
+        raise ValueError("img_mode must be one of 'abslog', 'reallog', 'raw', 'magif', 'melif' (got %r)" % (img_mode,))
+    if img_mode not in ('magif', 'melif') and mag_range is not None:
+        raise ValueError("mag_range belongs to img_mode='magif' and 'melif' (got img_mode %r)" % (img_mode,))
+    _mel_arguments(img_mode, n_fft, sample_rate, mel_rows)
     if range_in[0] != 0:
         raise NotImplementedError('range_in must start at 0 (uint8 images)')
     t = signal if torch.is_tensor(signal) else torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32))
-    if img_mode == 'magif':
+    if img_mode in ('magif', 'melif'):
         if t.dim() not in (1, 2) or t.shape[0] < 1:
             raise ValueError('expected a waveform [nsamp] or [nsamp, channels], got shape %s' % (tuple(t.shape),))
         t = t.to(dtype=torch.float32)
         if t.dim() == 2:
             t = t.sum(dim=1) / 2                                              # dataset.py:287-288: s.sum(axis=1) / 2 in float32
-        return spectrogram_stack_u8(t[None], n_fft, hop_length, mag_range)[0]
+        return spectrogram_stack_u8(t[None], n_fft, hop_length, mag_range, img_mode, sample_rate, mel_rows)[0]
     t = t.to(device='cuda', dtype=torch.float32).contiguous()
     return ops.spectrogram_u8(t, int(n_fft), int(hop_length), float(range_in[1]), img_mode=img_mode)
 
 
-def spectrogram_stack_u8(signals, n_fft=1024, hop_length=128, mag_range=None):
+def spectrogram_stack_u8(signals, n_fft=1024, hop_length=128, mag_range=None, img_mode='magif', sample_rate=None, mel_rows=None):
     """Mono waveforms ``[batch, nsamp]`` (numpy array or tensor) -> uint8 device images ``[batch, 2, n_fft/2, n_fft/2]`` of
     ``img_mode='magif'``, for filling a ``DeviceImageDataset`` stack: the analysis of the whole batch and the quantiser, no host
-    synchronisation (phase.spectrogram_stack_u8)."""
+    synchronisation (phase.spectrogram_stack_u8).  ``img_mode='melif'``: ``[batch, 2, M, M]``, M = ``mel_rows`` mel-spaced rows at
+    ``sample_rate`` Hz as in ``spectrogram_u8`` (phase.mel_spectrogram_stack_u8), the same two launches."""
     import torch
     from . import phase
+    if img_mode not in ('magif', 'melif'):
+        raise ValueError("img_mode must be 'magif' or 'melif' (got %r)" % (img_mode,))
     t = signals if torch.is_tensor(signals) else torch.from_numpy(np.ascontiguousarray(signals, dtype=np.float32))
     if t.dim() != 2 or t.shape[0] < 1:
         raise ValueError('signals: expected [batch, nsamp], got shape %s' % (tuple(t.shape),))
     if isinstance(n_fft, bool) or int(n_fft) != n_fft or isinstance(hop_length, bool) or int(hop_length) != hop_length:
         raise ValueError('n_fft and hop_length must be integers, got %r and %r' % (n_fft, hop_length))
-    return phase.spectrogram_stack_u8(t.to(device='cuda', dtype=torch.float32).contiguous(), int(n_fft), int(hop_length), mag_range)
+    table = _mel_arguments(img_mode, n_fft, sample_rate, mel_rows)
+    t = t.to(device='cuda', dtype=torch.float32).contiguous()
+    if table is not None:
+        return phase.mel_spectrogram_stack_u8(t, int(n_fft), int(hop_length), table, mag_range)
+    return phase.spectrogram_stack_u8(t, int(n_fft), int(hop_length), mag_range)
 
 
 def strip_frames(nsamp, hop_length, img_mode='magif'):
     """Columns of ``spectrogram_strip_u8`` for a waveform of ``nsamp`` samples: the 1 + nsamp // hop_length frames without the first."""
-    if img_mode not in ('magif', 'abslog'):
-        raise ValueError("img_mode must be 'magif' or 'abslog' (got %r)" % (img_mode,))
+    if img_mode not in ('magif', 'abslog', 'melif'):
+        raise ValueError("img_mode must be 'magif', 'abslog' or 'melif' (got %r)" % (img_mode,))
     if isinstance(hop_length, bool) or int(hop_length) != hop_length or hop_length < 1:
         raise ValueError('hop_length must be a positive integer, got %r' % (hop_length,))
     return int(nsamp) // int(hop_length)
 
 
-def spectrogram_strip_u8(signal, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None):
+def spectrogram_strip_u8(signal, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None, sample_rate=None, mel_rows=None):
     """Waveform (numpy array or tensor, ``[nsamp]`` or ``[nsamp, channels]``, mixed down as in ``spectrogram_u8``) -> the uint8 device
     STRIP ``[C, n_fft/2, T]`` over ALL frames of the recording, T = nsamp // hop_length, for ``dataset.DeviceStripDataset``:
     ``phase.analyse(bins=n_fft/2, frames=all)`` and ``phase.magif_u8`` with column 0 dropped -- the first column of the second
@@ -87,6 +118,8 @@ def spectrogram_strip_u8(signal, n_fft=1024, hop_length=128, img_mode='magif', m
     'abslog'  channel 0 of the same alone, ``[1, n_fft/2, T]``: log1p|S| stretched from the FIXED ``mag_range``, NOT from the per-file
               minimum and maximum that ``spectrogram_u8(img_mode='abslog')`` (the reference's load_file) uses -- crops of one
               recording and of different recordings share one scale, and the image can be inverted without knowing the file.
+    'melif'   ``[2, M, T]``: both channels on M = ``mel_rows`` mel-spaced rows at ``sample_rate`` Hz, as in ``spectrogram_u8``
+              (``phase.mel_analyse``: the planes of the n_fft/2 linear bins are never written).
 
     The analysis holds two float64 planes [n_fft/2, T + 1] on the device while it runs (16 n_fft/2 bytes per frame)."""
     import torch
@@ -97,13 +130,17 @@ def spectrogram_strip_u8(signal, n_fft=1024, hop_length=128, img_mode='magif', m
     if isinstance(n_fft, bool) or int(n_fft) != n_fft:
         raise ValueError('n_fft must be an integer, got %r' % (n_fft,))
     T = strip_frames(t.shape[0], hop_length, img_mode)
+    table = _mel_arguments(img_mode, n_fft, sample_rate, mel_rows)
     if T < 1:
         raise ValueError('%d samples every %r give no frame after the first' % (t.shape[0], hop_length))
     mag_range = phase.check_mag_range(mag_range, int(n_fft), 'spectrogram_strip_u8')
     t = t.to(device='cuda', dtype=torch.float32)
     if t.dim() == 2:
         t = t.sum(dim=1) / 2                                                  # dataset.py:287-288: s.sum(axis=1) / 2 in float32
-    logmag, ifreq = phase.analyse(t.contiguous(), int(n_fft), int(hop_length), int(n_fft) // 2, T + 1)
+    if table is not None:
+        logmag, ifreq = phase.mel_analyse(t.contiguous(), int(n_fft), int(hop_length), table, T + 1)
+    else:
+        logmag, ifreq = phase.analyse(t.contiguous(), int(n_fft), int(hop_length), int(n_fft) // 2, T + 1)
     image = phase.magif_u8(logmag, ifreq, mag_range)[0]
     return image[:1 if img_mode == 'abslog' else 2, :, 1:].contiguous()
 
@@ -124,7 +161,11 @@ def _mag_range(mag_range, n_fft):
 def magif_analyse(y, n_fft, hop_length):
     """Mono waveform -> ``(logmag, ifreq)`` float64 ``[n_fft/2 + 1, frames]``: log1p(|S|) and the wrapped difference of the phase of
     neighbouring frames in units of pi, in [-1, 1); the first column is the phase itself (phi[-1] = 0, phi = 0 where S == 0)."""
-    S = stft(np.asarray(y, dtype=np.float32), n_fft, hop_length)
+    return _magif_planes(stft(np.asarray(y, dtype=np.float32), n_fft, hop_length))
+
+
+def _magif_planes(S):
+    """``(logmag, ifreq)`` of a complex spectrum ``[bins, frames]``."""
     phi = np.where(np.abs(S) == 0, 0.0, np.arctan2(S.imag, S.real) / np.pi)   # (arctan2(-0.0, -0.0) is -pi)
     d = np.diff(phi, axis=1, prepend=0.0)
     return np.log1p(np.abs(S)), d - 2.0 * np.floor(d / 2.0 + 0.5)
@@ -147,6 +188,53 @@ def magif_spectrum(image, drange, mag_range):
     spec = np.zeros((img.shape[1] + 1, img.shape[2]), dtype=np.complex128)
     c = c - 2.0 * np.floor(c / 2.0 + 0.5)                                     # into [-1, 1], exactly: cos / sin see small arguments
     spec[:-1] = mag * (np.cos(np.pi * c) + 1.0j * np.sin(np.pi * c))
+    return spec
+
+
+# ------------------------------------------------------------- 'melif' in numpy fp64: the host twin of csrc/mel.hip (``table``: a
+# phase.MelTable, e.g. phase.mel_table(n_fft, rows, sample_rate))
+def melif_analyse(y, n_fft, hop_length, table):
+    """Mono waveform -> ``(logmag, ifreq)`` float64 ``[table.rows, frames]``: row m is log1p of the weighted mean of |S| over its band
+    of bins and the magnitude-weighted circular mean of their instantaneous frequencies (0 where that mean vanishes); a row whose
+    band is one bin copies the bin's two values of ``magif_analyse``."""
+    if table.n_fft != n_fft:
+        raise ValueError('melif_analyse: the table is for n_fft %d, not %d' % (table.n_fft, n_fft))
+    S = stft(np.asarray(y, dtype=np.float32), n_fft, hop_length)
+    logmag_k, ifreq_k = _magif_planes(S)                                    # (the planes of ``magif_analyse``, from the one transform)
+    mag = np.abs(S)
+    logmag, ifreq = np.empty((table.rows, S.shape[1])), np.empty((table.rows, S.shape[1]))
+    for m in range(table.rows):
+        s, n = int(table.start[m]), int(table.count[m])
+        if n == 1:
+            logmag[m], ifreq[m] = logmag_k[s], ifreq_k[s]
+            continue
+        a, zr, zi = np.zeros(S.shape[1]), np.zeros(S.shape[1]), np.zeros(S.shape[1])
+        for w, k in zip(table.row_weights(m), range(s, s + n)):              # in ascending k, as the kernel sums
+            a, zr, zi = a + w * mag[k], zr + w * (mag[k] * np.cos(np.pi * ifreq_k[k])), zi + w * (mag[k] * np.sin(np.pi * ifreq_k[k]))
+        logmag[m] = np.log1p(a)
+        ifreq[m] = np.where((zr == 0) & (zi == 0), 0.0, np.arctan2(zi, zr) / np.pi)
+    return logmag, ifreq
+
+
+def melif_spectrum(image, table, drange, mag_range):
+    """fp32 image ``[2, table.rows, W]`` -> complex spectrum ``[table.bins + 1, W]``: bin k takes its magnitude linearly and its
+    instantaneous frequency along the shorter arc between rows lower[k] and lower[k] + 1 (frac 0 / 1: from the one row alone), then
+    as ``magif_spectrum``."""
+    img = np.asarray(image, dtype=np.float64)
+    if img.ndim != 3 or img.shape[:2] != (2, table.rows):
+        raise ValueError('melif_spectrum: expected an image [2, %d, W], got shape %s' % (table.rows, tuple(img.shape)))
+    a = np.expm1(np.maximum(adjust_dynamic_range(img[0], tuple(drange), tuple(mag_range)), 0.0))
+    g = adjust_dynamic_range(img[1], tuple(drange), (0, 255)) / 128.0 - 1.0
+    i, f = table.lower.astype(np.int64), table.frac[:, None]
+    with np.errstate(invalid='ignore'):                                      # (a non-finite row is selected away below, not multiplied by 0)
+        step = g[i + 1] - g[i]
+        step = step - 2.0 * np.floor(step / 2.0 + 0.5)
+        mag = np.where(f == 0, a[i], np.where(f == 1, a[i + 1], (1.0 - f) * a[i] + f * a[i + 1]))
+        d = np.where(f == 0, g[i], np.where(f == 1, g[i + 1], g[i] + f * step))
+        c = np.cumsum(d, axis=1)
+        spec = np.zeros((table.bins + 1, img.shape[2]), dtype=np.complex128)
+        c = c - 2.0 * np.floor(c / 2.0 + 0.5)                                 # into [-1, 1], exactly: cos / sin see small arguments
+        spec[:-1] = mag * (np.cos(np.pi * c) + 1.0j * np.sin(np.pi * c))
     return spec
 
 
@@ -178,18 +266,27 @@ def istft(spec, hop_length):
 class SoundSaver(object):
     """Post-processor writing generated spectrograms / raw waveforms as WAV files (output_postprocess.py:75-153).  ``mode='magif'``
     (this project's own): channels 0 and 1 are log-magnitude over ``mag_range`` (default (0, log1p(H))) and instantaneous frequency;
-    the waveform is ONE inverse STFT of magnitude x e^{i pi cumsum(IF)}, no Griffin-Lim and no random start."""
+    the waveform is ONE inverse STFT of magnitude x e^{i pi cumsum(IF)}, no Griffin-Lim and no random start.  ``mode='melif'``: the
+    same for images whose M rows are mel-spaced rows of an ``n_fft``-point transform (default 2 M) at ``sample_rate`` Hz
+    (``phase.mel_table``): every one of the n_fft/2 bins is interpolated from its two rows first."""
 
     output_file_format = 'fakes_sound_{}_{}.wav'
 
     def __init__(self, samples_path='.', drange=(-1, 1), resolution=512, mode='abslog', sample_rate=16000,
-                 hop_length=128, create_subdirs=True, verbose=False, griffin_lim_iter=100, seed=None, mag_range=None):
+                 hop_length=128, create_subdirs=True, verbose=False, griffin_lim_iter=100, seed=None, mag_range=None, n_fft=None):
         self.samples_path = samples_path
         if mag_range is not None:
-            if mode != 'magif':
-                raise ValueError("mag_range belongs to mode='magif' (got mode %r)" % (mode,))
+            if mode not in ('magif', 'melif'):
+                raise ValueError("mag_range belongs to mode='magif' and 'melif' (got mode %r)" % (mode,))
             mag_range = _mag_range(mag_range, 0)
         self.mag_range = mag_range
+        if n_fft is not None:
+            if mode != 'melif':
+                raise ValueError("n_fft belongs to mode='melif' (got mode %r)" % (mode,))
+            if isinstance(n_fft, bool) or int(n_fft) != n_fft:
+                raise ValueError('n_fft must be an integer, got %r' % (n_fft,))
+            n_fft = int(n_fft)
+        self.n_fft = n_fft
         if create_subdirs:
             os.makedirs(self.samples_path, exist_ok=True)
         self.drange, self.mode, self.sample_rate, self.hop_length = drange, mode, sample_rate, hop_length
@@ -208,6 +305,11 @@ class SoundSaver(object):
                 print('Griffin-Lim: change of the signal in this round (L2) = %g' % np.sqrt(np.square(x - previous).sum()))
         return x
 
+    def mel_table(self, rows):
+        """mode='melif': the table between images of ``rows`` rows and the bins of ``self.n_fft`` (default 2 rows) at ``self.sample_rate``."""
+        from . import phase
+        return phase.mel_table(2 * rows if self.n_fft is None else self.n_fft, rows, self.sample_rate)
+
     def image_to_sound(self, image):
         if self.mode == 'abslog':
             mag = np.zeros((image.shape[0] + 1, image.shape[1]))               # spectrograms have 2**i + 1 frequency bins
@@ -224,8 +326,13 @@ class SoundSaver(object):
             if image.ndim != 3 or image.shape[0] != 2:
                 raise ValueError("SoundSaver mode 'magif' takes two-channel images, got shape %s" % (tuple(image.shape),))
             signal = istft(magif_spectrum(image, self.drange, _mag_range(self.mag_range, 2 * image.shape[1])), self.hop_length)
+        elif self.mode == 'melif':                                            # image [2, M, W]: the bins from the rows, then as 'magif'
+            if image.ndim != 3 or image.shape[0] != 2:
+                raise ValueError("SoundSaver mode 'melif' takes two-channel images, got shape %s" % (tuple(image.shape),))
+            table = self.mel_table(image.shape[1])
+            signal = istft(melif_spectrum(image, table, self.drange, _mag_range(self.mag_range, table.n_fft)), self.hop_length)
         else:
-            raise ValueError('SoundSaver mode %r is not one of abslog / reallog / raw / magif' % (self.mode,))
+            raise ValueError('SoundSaver mode %r is not one of abslog / reallog / raw / magif / melif' % (self.mode,))
         return signal / np.abs(signal).max()
 
     def output_wav(self, signal, samples_description, ith):
@@ -246,7 +353,7 @@ class SoundSaver(object):
         if self.mode == 'raw':
             times_smaller *= times_smaller
         for i, img in enumerate(output):
-            signal = self.image_to_sound(img[:2] if self.mode == 'magif' else img[0])
+            signal = self.image_to_sound(img[:2] if self.mode in ('magif', 'melif') else img[0])
             if times_smaller > 1:
                 signal = signal.repeat(times_smaller, axis=-1)                # utils.numpy_upsample_nearest(signal, 1, scale_factor=...)
             self.output_wav(signal, samples_description, i)
@@ -265,7 +372,8 @@ class DeviceSoundSaver(SoundSaver):
     treats its randomness the same way).  Images must be square with a power-of-two side in 4 .. 1024; there is no fallback to the
     host.  ``verbose=True`` prints the host saver's line per round and sample; it copies both signals back after every round, a slow
     debugging aid.  ``mode='magif'`` takes ``[n, 2, H, W]`` samples (further channels are ignored) through csrc/phase.hip: spectrum, pieces,
-    overlap-add and normalisation, four launches, and draws nothing from the RNG."""
+    overlap-add and normalisation, four launches, and draws nothing from the RNG.  ``mode='melif'`` is the same through csrc/mel.hip's
+    spectrum (``phase.mel_synthesise``): four launches as well."""
 
     accepts_device_tensors = True            # plugins.OutputGenerator then skips the D2H copy of the fp32 samples
 
@@ -274,11 +382,12 @@ class DeviceSoundSaver(SoundSaver):
         ``[n, nsamp * times_smaller]``: each sample's waveform, peak-normalised and stretched as ``SoundSaver.__call__`` writes it."""
         import torch
         from . import ops
-        if self.mode not in ('abslog', 'reallog', 'raw', 'magif'):
-            raise ValueError('SoundSaver mode %r is not one of abslog / reallog / raw / magif' % (self.mode,))
+        if self.mode not in ('abslog', 'reallog', 'raw', 'magif', 'melif'):
+            raise ValueError('SoundSaver mode %r is not one of abslog / reallog / raw / magif / melif' % (self.mode,))
+        two = self.mode in ('magif', 'melif')
         t = output if torch.is_tensor(output) else torch.from_numpy(np.ascontiguousarray(output, dtype=np.float32))
-        if t.dim() != 4 or t.shape[0] < 1 or (self.mode == 'magif' and t.shape[1] < 2):
-            raise ValueError('DeviceSoundSaver: expected samples [n, %d, H, W], got shape %s' % (2 if self.mode == 'magif' else 1, tuple(t.shape)))
+        if t.dim() != 4 or t.shape[0] < 1 or (two and t.shape[1] < 2):
+            raise ValueError('DeviceSoundSaver: expected samples [n, %d, H, W], got shape %s' % (2 if two else 1, tuple(t.shape)))
         n, _, H, W = t.shape
         if H != W or H < 4 or H > 1024 or H & (H - 1):
             raise ValueError('DeviceSoundSaver: images must be square with a power-of-two side in 4 .. 1024, got %dx%d' % (H, W))
@@ -286,9 +395,15 @@ class DeviceSoundSaver(SoundSaver):
         if self.mode == 'raw':
             times_smaller *= times_smaller
         nsamp = (W - 1) * self.hop_length
-        if self.mode != 'raw' and nsamp <= H:
+        table = self.mel_table(H) if self.mode == 'melif' else None
+        pad = H if table is None else table.bins
+        if self.mode != 'raw' and nsamp <= pad:
             raise ValueError('DeviceSoundSaver: %d frames every %d samples give %d samples, the reflect padding by n_fft/2 = %d '
-                             'needs more' % (W, self.hop_length, nsamp, H))
+                             'needs more' % (W, self.hop_length, nsamp, pad))
+        if table is not None:                                                 # as 'magif' below, the spectrum from csrc/mel.hip
+            from . import phase
+            x = phase.mel_synthesise(_to_device(t)[:, :2].to(torch.float32).contiguous(), self.hop_length, table, self.drange, self.mag_range)
+            return ops.wave_normalize(x, max(1, times_smaller))
         if self.mode == 'magif':                                              # spectrum, pieces, overlap-add, normalise: four launches,
             from . import phase                                               # no random draws (the RNG is not advanced)
             x = phase.synthesise(_to_device(t)[:, :2].to(torch.float32).contiguous(), self.hop_length, self.drange, self.mag_range)
