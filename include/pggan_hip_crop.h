@@ -1,5 +1,5 @@
 /*
- * pggan_hip_crop.h — C-ABI of the real-image batch cut from device-resident spectrogram STRIPS (csrc/crop_batch.hip): a training
+ * pggan_hip_crop.h — C-ABI of the real-image batch cut from device-resident spectrogram STRIPS (csrc/real_batch.hip): a training
  * batch whose images are windows at arbitrary time offsets of recordings of arbitrary length, in one launch.
  *
  * An ADDITION to the product boundary: include/pggan_hip.h, its PG_ABI_VERSION and its conventions (row-major contiguous tensors,

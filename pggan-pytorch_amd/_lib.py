@@ -128,7 +128,7 @@ _RESTYPE_OF.update(_sampling_restypes)
 # ... and the pyramid loss of the latent projection with its image gradient (csrc/projection.hip, wrapped in ops.py, used by projection.py)
 PROJECTION_SIGNATURES, _projection_restypes, PROJECTION_CONSTANTS = _read_header('pggan_hip_projection.h')
 _RESTYPE_OF.update(_projection_restypes)
-# ... and the real batch cut from spectrogram strips at random time offsets (csrc/crop_batch.hip, wrapped in ops.py, used by dataset.py)
+# ... and the real batch cut from spectrogram strips at random time offsets (csrc/real_batch.hip: the batch kernels' strip source; wrapped in ops.py, used by dataset.py)
 CROP_SIGNATURES, _crop_restypes, CROP_CONSTANTS = _read_header('pggan_hip_crop.h')
 _RESTYPE_OF.update(_crop_restypes)
 # ... and the descriptor side of the sliced Wasserstein distance for 1 .. 4 channels (csrc/swd.hip, wrapped in ops.py, used by metrics.py)

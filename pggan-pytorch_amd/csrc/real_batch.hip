@@ -1,14 +1,19 @@
-// The real-image batch of a training step in one launch, from a uint8 image stack that lives in HBM:
-//   pg_real_batch_u8 : gather by index -> pyramid level -> mirror -> fade-in blend -> dynamic range -> fp32
+// The real-image batch of a training step in one launch, from uint8 images that live in HBM:
+//   pg_real_batch_u8, pg_real_batch_2ch_u8 : gather by index from a stack [M][C][S][S]
+//   pg_crop_batch_u8                       : gather by (strip, start column) from spectrogram strips [C][S][pitch]
+//   -> pyramid level -> mirror -> fade-in blend -> dynamic range -> fp32
 // i.e. pg_pyramid_level_u8 (dataset.py:243-250), a flip of the last axis and pg_real_prepare_u8 (dataset.py:54-67,109-113,
 // utils.py:24-30) of csrc/io_steps.hip fused behind an index_select, bit for bit: the level in fp32 (sums of four bytes and
 // the division by 4 are exact, rintf is np.round), the fade and the range change in fp64 with numpy's unfused order, rounded once
 // to fp32.  The 2x2 block mean of the fade is exact in fp64 and the mirror maps 2x2 blocks onto 2x2 blocks, so mirror and fade
 // commute bit for bit: a thread of a mirrored image reads its blocks reversed and stores them straight.
+// There is one rows kernel and one blocks kernel; a SOURCE (Stack, Strips) says where a window's rows start, how far apart they are
+// and how 8 of their bytes are loaded, and nothing else.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pggan_hip.h"
 #include "pggan_hip_phase.h"
+#include "pggan_hip_crop.h"
 
 // numpy never fuses a multiply with the following add (see io_steps.hip): for the whole translation unit
 #pragma clang fp contract(off)
@@ -36,11 +41,56 @@ __device__ __forceinline__ void prepare_block(double v[4], const Prep& p)
     }
 }
 
-// depthdiff == 0, r >= 8: a thread owns two rows x 8 output columns of one plane -- two 8-byte loads, four 16-byte stores.
-// Alignment: planes are r*r >= 64 bytes, rows r >= 8 bytes, columns multiples of 8 -> every load is 8-byte aligned and every
-// store 16-byte aligned (32 bytes per 8 floats) from nothing more than 16-byte aligned bases.
-__global__ __launch_bounds__(256) void real_batch_rows_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ idx,
-                                                              const uint8_t* __restrict__ flip, float* __restrict__ out,
+// Image idx[j] of a stack [M][C][S][S], S = 1 << ls.  Planes are S*S bytes, rows S bytes and the rows kernel reads columns that are
+// multiples of 8 of an S >= 8: every load is 8-byte aligned from nothing more than an 8-byte aligned base.
+struct Stack {
+    const uint8_t* __restrict__ src;
+    const int64_t* __restrict__ idx;
+    int ls;
+    typedef int pitch_t;
+    __device__ __forceinline__ const uint8_t* row(long long j, int C, int c, int y, pitch_t& pitch) const
+    {
+        pitch = 1 << ls;
+        return src + (((long long)idx[j] * C + c) << (2 * ls)) + ((long long)y << ls);
+    }
+    static __device__ __forceinline__ uint2 load8(const uint8_t* a) { return *reinterpret_cast<const uint2*>(a); }
+};
+
+// The window of columns [u, u + S), u = pos[j] >> shift, of strip idx[j] of one stored level (include/pggan_hip_crop.h), S = 1 << ls.
+// A window row starts at ANY byte of a 16-byte aligned strip row, so the 8 source bytes of a thread are cut out of the one or two
+// aligned 8-byte words that hold them (v_alignbyte_b32).  The second word is loaded only when the window leans into it; both lie
+// inside the row's pitch, which is a multiple of 16: nothing outside the strip is read, and the padding bytes a word may bring along
+// are shifted out.
+struct Strips {
+    const uint8_t* __restrict__ src;
+    const int64_t* __restrict__ table;
+    const int64_t* __restrict__ idx;
+    const int64_t* __restrict__ pos;
+    int ls, shift;
+    typedef long long pitch_t;
+    __device__ __forceinline__ const uint8_t* row(long long j, int C, int c, int y, pitch_t& pitch) const
+    {
+        const int64_t* e = table + PG_CROP_TABLE_WORDS * idx[j];
+        pitch = e[1];
+        return src + e[0] + (((long long)c << ls) + y) * pitch + (pos[j] >> shift);
+    }
+    // the 8 bytes at `a`, which need not be aligned: the aligned 8-byte word that holds a[0], and the next one if a[7] is in it
+    static __device__ __forceinline__ uint2 load8(const uint8_t* a)
+    {
+        const unsigned s = (unsigned)(reinterpret_cast<uintptr_t>(a) & 7);
+        const uint2* w = reinterpret_cast<const uint2*>(a - s);
+        const uint2 lo = w[0];
+        uint2 hi = make_uint2(0u, 0u);
+        if (s) hi = w[1];
+        const unsigned w0 = s & 4 ? lo.y : lo.x, w1 = s & 4 ? hi.x : lo.y, w2 = s & 4 ? hi.y : hi.x;
+        return make_uint2(__builtin_amdgcn_alignbyte(w1, w0, s & 3), __builtin_amdgcn_alignbyte(w2, w1, s & 3));
+    }
+};
+
+// depthdiff == 0, r >= 8: a thread owns two rows x 8 output columns of one plane -- two 8-byte loads (Strips: two to four), four
+// 16-byte stores: out is [n][C][r][r] from a 16-byte aligned base and columns are multiples of 8 (32 bytes per 8 floats).
+template <class Source>
+__global__ __launch_bounds__(256) void real_batch_rows_kernel(Source source, const uint8_t* __restrict__ flip, float* __restrict__ out,
                                                               long long total, int C, int lr, Prep p)
 {
     const int r = 1 << lr, lx = lr - 3, ly = lr - 1;
@@ -52,9 +102,10 @@ __global__ __launch_bounds__(256) void real_batch_rows_kernel(const uint8_t* __r
         const int c = (int)(pl - j * C);
         const int mirrored = flip ? flip[j] != 0 : 0;
         const int xs = mirrored ? r - 8 - 8 * xu : 8 * xu;                   // source columns [xs, xs + 8)
-        const uint8_t* row = src + (((long long)idx[j] * C + c) << (2 * lr)) + ((long long)(2 * y2) << lr) + xs;
-        uint2 a = *reinterpret_cast<const uint2*>(row);
-        uint2 b = *reinterpret_cast<const uint2*>(row + r);
+        typename Source::pitch_t pitch;
+        const uint8_t* row = source.row(j, C, c, 2 * y2, pitch) + xs;
+        uint2 a = Source::load8(row);
+        uint2 b = Source::load8(row + pitch);
         if (mirrored) {                                                      // byte k <-> byte 7 - k
             a = make_uint2(__builtin_bswap32(a.y), __builtin_bswap32(a.x));
             b = make_uint2(__builtin_bswap32(b.y), __builtin_bswap32(b.x));
@@ -77,21 +128,23 @@ __global__ __launch_bounds__(256) void real_batch_rows_kernel(const uint8_t* __r
     }
 }
 
-// level pixel (y, x) of a source plane: the byte itself, or pyramid_level_u8_kernel's four samples with stride st = 1 << dd
-__device__ __forceinline__ double level_pixel(const uint8_t* __restrict__ plane, int S, int dd, int y, int x, float lo, float hi)
+// level pixel (y, x) of a window whose rows are `pitch` bytes apart: the byte itself, or pyramid_level_u8_kernel's four samples with
+// stride st = 1 << dd
+template <class pitch_t>
+__device__ __forceinline__ double level_pixel(const uint8_t* __restrict__ win, pitch_t pitch, int dd, int y, int x, float lo, float hi)
 {
-    if (dd == 0) return (double)plane[(long long)y * S + x];
-    const uint8_t* q = plane + ((long long)y << dd) * S + ((long long)x << dd);
-    float v = (((float)q[0] + (float)q[1]) + (float)q[S]) + (float)q[S + 1];
+    if (dd == 0) return (double)win[(long long)y * pitch + x];
+    const uint8_t* q = win + ((long long)y << dd) * pitch + ((long long)x << dd);
+    float v = (((float)q[0] + (float)q[1]) + (float)q[pitch]) + (float)q[pitch + 1];
     v = rintf(v * 0.25f);
     v = fminf(fmaxf(v, lo), hi);
     return (double)(uint8_t)v;
 }
 
 // r < 8 or depthdiff > 0 (a strided gather): a thread owns one 2x2 block of one output plane, byte loads, two 8-byte stores
-__global__ __launch_bounds__(256) void real_batch_blocks_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ idx,
-                                                                const uint8_t* __restrict__ flip, float* __restrict__ out,
-                                                                long long total, int C, int S, int dd, int lr, float lo, float hi, Prep p)
+template <class Source>
+__global__ __launch_bounds__(256) void real_batch_blocks_kernel(Source source, const uint8_t* __restrict__ flip, float* __restrict__ out,
+                                                                long long total, int C, int dd, int lr, float lo, float hi, Prep p)
 {
     const int r = 1 << lr, lh = lr - 1;
     for (long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x; u < total; u += (long long)gridDim.x * blockDim.x) {
@@ -102,9 +155,10 @@ __global__ __launch_bounds__(256) void real_batch_blocks_kernel(const uint8_t* _
         const int c = (int)(pl - j * C);
         const int mirrored = flip ? flip[j] != 0 : 0;
         const int xa = mirrored ? r - 1 - 2 * x2 : 2 * x2, xb = mirrored ? xa - 1 : xa + 1;   // level columns of output columns 2 x2, 2 x2 + 1
-        const uint8_t* plane = src + ((long long)idx[j] * C + c) * S * S;
-        double v[4] = {level_pixel(plane, S, dd, 2 * y2, xa, lo, hi), level_pixel(plane, S, dd, 2 * y2, xb, lo, hi),
-                       level_pixel(plane, S, dd, 2 * y2 + 1, xa, lo, hi), level_pixel(plane, S, dd, 2 * y2 + 1, xb, lo, hi)};
+        typename Source::pitch_t pitch;
+        const uint8_t* win = source.row(j, C, c, 0, pitch);
+        double v[4] = {level_pixel(win, pitch, dd, 2 * y2, xa, lo, hi), level_pixel(win, pitch, dd, 2 * y2, xb, lo, hi),
+                       level_pixel(win, pitch, dd, 2 * y2 + 1, xa, lo, hi), level_pixel(win, pitch, dd, 2 * y2 + 1, xb, lo, hi)};
         prepare_block(v, p);
         float* d = out + (pl << (2 * lr)) + ((long long)(2 * y2) << lr) + 2 * x2;             // even column, even r: 8-byte aligned
         *reinterpret_cast<float2*>(d) = make_float2((float)v[0], (float)v[1]);
@@ -120,8 +174,10 @@ inline int grid_for(long long total, int block = 256, int cap = 4096)
     return (int)g;
 }
 
-// src [M][C][S][S]; the kernels take any C (a plane is a plane), the entry points state which they accept
-int launch_real_batch(const uint8_t* src, int C, int S, int depthdiff, const int64_t* idx, const uint8_t* flip, int n, float* out,
+// n windows of C planes S x S from `source` (whose `ls` is filled in here); the kernels take any C (a plane is a plane), the entry
+// points state which they accept
+template <class Source>
+int launch_real_batch(Source source, int C, int S, int depthdiff, const uint8_t* flip, int n, float* out,
                       double alpha, double min_in, double max_in, double min_out, double max_out, pg_stream_t stream)
 {
     if (S & (S - 1)) return PG_E_ALIGN;
@@ -129,6 +185,7 @@ int launch_real_batch(const uint8_t* src, int C, int S, int depthdiff, const int
     if (r < 2) return PG_E_ALIGN;
     int lr = 0;
     while ((1 << lr) < r) ++lr;
+    source.ls = lr + depthdiff;
     Prep p;
     p.rescale = !(min_in == min_out && max_in == max_out);                   // utils.py:25 `if range_in != range_out`
     p.scale = p.rescale ? (max_out - min_out) / (max_in - min_in) : 1.0;
@@ -139,12 +196,12 @@ int launch_real_batch(const uint8_t* src, int C, int S, int depthdiff, const int
     const long long planes = (long long)n * C;
     if (depthdiff == 0 && r >= 8) {
         const long long total = planes * (r / 2) * (r / 8);
-        hipLaunchKernelGGL(real_batch_rows_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                           src, idx, flip, out, total, C, lr, p);
+        hipLaunchKernelGGL(real_batch_rows_kernel<Source>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+                           source, flip, out, total, C, lr, p);
     } else {
         const long long total = planes * (r / 2) * (r / 2);
-        hipLaunchKernelGGL(real_batch_blocks_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                           src, idx, flip, out, total, C, S, depthdiff, lr, (float)min_in, (float)max_in, p);
+        hipLaunchKernelGGL(real_batch_blocks_kernel<Source>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+                           source, flip, out, total, C, depthdiff, lr, (float)min_in, (float)max_in, p);
     }
     return (int)hipGetLastError();
 }
@@ -156,7 +213,7 @@ extern "C" int pg_real_batch_u8(const uint8_t* src, int64_t M, int C, int S, int
                                 pg_stream_t stream)
 {
     if (!src || !idx || !out || M <= 0 || n <= 0 || S <= 0 || depthdiff < 0 || depthdiff > 30 || (C != 1 && C != 3)) return PG_E_ARG;
-    return launch_real_batch(src, C, S, depthdiff, idx, flip, n, out, alpha, min_in, max_in, min_out, max_out, stream);
+    return launch_real_batch(Stack{src, idx, 0}, C, S, depthdiff, flip, n, out, alpha, min_in, max_in, min_out, max_out, stream);
 }
 
 // the (log-magnitude, instantaneous frequency) stacks of include/pggan_hip_phase.h
@@ -165,5 +222,16 @@ extern "C" int pg_real_batch_2ch_u8(const uint8_t* src, int64_t M, int S, int de
                                     pg_stream_t stream)
 {
     if (!src || !idx || !out || M <= 0 || n <= 0 || S <= 0 || depthdiff < 0 || depthdiff > 30) return PG_E_ARG;
-    return launch_real_batch(src, 2, S, depthdiff, idx, flip, n, out, alpha, min_in, max_in, min_out, max_out, stream);
+    return launch_real_batch(Stack{src, idx, 0}, 2, S, depthdiff, flip, n, out, alpha, min_in, max_in, min_out, max_out, stream);
+}
+
+// the strips of include/pggan_hip_crop.h
+extern "C" int pg_crop_batch_u8(const uint8_t* src, const int64_t* table, int64_t M, int C, int S, int shift, int depthdiff,
+                                const int64_t* idx, const int64_t* pos, const uint8_t* flip, int n, float* out,
+                                double alpha, double min_in, double max_in, double min_out, double max_out, pg_stream_t stream)
+{
+    if (!src || !table || !idx || !pos || !out || M <= 0 || n <= 0 || S <= 0 || depthdiff < 0 || depthdiff > 30 || shift < 0 || shift > 30
+        || C < 1 || C > 3) return PG_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out)) & 15) return PG_E_ALIGN;
+    return launch_real_batch(Strips{src, table, idx, pos, 0, shift}, C, S, depthdiff, flip, n, out, alpha, min_in, max_in, min_out, max_out, stream);
 }

@@ -1,15 +1,16 @@
-"""Device-resident real-image dataset: the reference's ``DepthDataset`` protocol (dataset.py:31-70) on a uint8 image stack
-that lives in HBM, with the whole batch -- gather, pyramid level, mirror, fade-in, dynamic range -- in one launch
-(``ops.real_batch_u8`` / csrc/real_batch.hip).  Nothing crosses PCIe per step and no host worker prepares anything, so the
-stale ``dataset.alpha`` of forked DataLoader workers cannot occur: every batch is made with the depth and alpha of
-the moment it is drawn.
+"""Device-resident real-image datasets: the reference's ``DepthDataset`` protocol (dataset.py:31-70) on uint8 images that live in
+HBM, with the whole batch -- gather, pyramid level, mirror, fade-in, dynamic range -- in one launch of csrc/real_batch.hip.  Nothing
+crosses PCIe per step and no host worker prepares anything, so the stale ``dataset.alpha`` of forked DataLoader workers
+cannot occur: every batch is made with the depth and alpha of the moment it is drawn.
+
+``DeviceImageDataset`` holds a stack [M,C,R,R] and draws image indices (``IndexStream``, ``ops.real_batch_u8``).
+``DeviceStripDataset`` holds recordings of arbitrary length, each one uint8 spectrogram strip (``StripLevel``), and draws windows at
+random time offsets, cut where the strip lies (``CropStream``, ``ops.crop_batch_u8``).  Both are a ``_DeviceDataset``, which owns the
+stage, the training stream and the batch protocol, and both streams are an ``_EpochStream``, which owns the cursor rules; the two
+batch kernels are one pair, instantiated for the two sources.
 
 ``device='cpu'`` (host mode) evaluates the same definition with numpy in fp64, as the reference computes it; it backs
-``__getitem__`` and is the twin the device path is compared with, bit for bit (tests/golden/io_steps.npz pins both).
-
-``DeviceStripDataset`` (with ``StripLevel`` and ``CropStream``, at the end) is the same protocol for recordings of arbitrary length:
-every recording is one uint8 spectrogram strip in HBM and a batch item is a window at a random time offset, cut where the strip lies
-in the same single launch (``ops.crop_batch_u8`` / csrc/crop_batch.hip)."""
+``__getitem__`` and is the twin the device path is compared with, bit for bit (tests/golden/io_steps.npz pins both)."""
 import os
 
 import numpy as np
@@ -60,48 +61,40 @@ def batch_host(stack_u8, idx, flip, depthdiff, alpha, range_in=(0, 255), range_o
     return prepare_host(level, alpha, range_in, range_out)
 
 
-# --------------------------------------------------------------------------------------------------- index stream
-class IndexStream(object):
-    """The positions 0, 1, 2, ... of an endless sequence of image indices: ``torch.randperm(M, generator=g)`` per epoch, ``g`` a
-    CPU generator seeded with ``seed`` (the reference's InfiniteRandomSampler, train.py:51-56); ``arange(M)`` per epoch without
-    ``shuffle``.  Mirror flags (``flags=True``) belong to positions too: ``torch.randint(0, 2, (M,), generator=g2,
-    dtype=torch.uint8)`` per epoch, ``g2`` seeded ``seed + 1``.  An epoch's two arrays are made once and moved to ``device`` once;
-    ``take`` hands out slices of them (concatenated on the device across an epoch boundary): no copy and no synchronisation
-    per batch.  ``cursor`` is the next unread position."""
+# -------------------------------------------------------------------------------------------------------- streams
+class _EpochStream(object):
+    """The positions 0, 1, 2, ... of an endless sequence made of epochs of ``size`` positions.  A subclass gives ``_host_epoch()``:
+    the host tensors [size] of the NEXT epoch as a tuple (``None`` for a member it does not carry); epochs are made in order.  An
+    epoch's arrays are made once and moved to ``device`` once; ``take`` hands out slices of them (concatenated on the device across
+    an epoch boundary): no copy and no synchronisation per batch.  ``cursor`` is the next unread position."""
 
-    def __init__(self, M, shuffle=True, seed=0, flags=False, device='cpu'):
-        if int(M) < 1:
-            raise ValueError('an index stream needs at least one image')
-        self.M, self.shuffle, self.flags, self.device = int(M), bool(shuffle), bool(flags), torch.device(device)
-        self._g = torch.Generator().manual_seed(int(seed))
-        self._g2 = torch.Generator().manual_seed(int(seed) + 1)
-        self._epochs = {}                # epoch number -> (idx, flip or None) on ``device``
+    def __init__(self, size, what, shuffle, flags, device):
+        self._size, self._what = int(size), what
+        self.shuffle, self.flags, self.device = bool(shuffle), bool(flags), torch.device(device)
+        self._epochs = {}                # epoch number -> its tuple on ``device``
         self._made = 0                   # epochs generated so far (they must be drawn in order)
         self.cursor = 0
 
     def _epoch(self, e):
         while self._made <= e:
-            idx = torch.randperm(self.M, generator=self._g) if self.shuffle else torch.arange(self.M)
-            flip = torch.randint(0, 2, (self.M,), generator=self._g2, dtype=torch.uint8) if self.flags else None
-            self._epochs[self._made] = (idx.to(self.device), None if flip is None else flip.to(self.device))
+            self._epochs[self._made] = tuple(None if t is None else t.to(self.device) for t in self._host_epoch())
             self._made += 1
         return self._epochs[e]
 
     def take(self, n, rank=0, world=1):
-        """(idx [n] int64, flip [n] uint8 or None) at positions [cursor + rank n, cursor + (rank + 1) n); the cursor moves by n world."""
+        """The epoch's tuple at positions [cursor + rank n, cursor + (rank + 1) n), each member [n]; the cursor moves by n world."""
         n = int(n)
         if n < 1:
-            raise ValueError('a draw needs at least one image')
+            raise ValueError('a draw needs at least one %s' % self._what)
         start = self.cursor + rank * n
         self.cursor += n * world
-        for e in [k for k in self._epochs if k < start // self.M]:              # epochs every rank has left behind
+        for e in [k for k in self._epochs if k < start // self._size]:          # epochs every rank has left behind
             del self._epochs[e]
         parts, pos = [], start
         while pos < start + n:
-            e, off = divmod(pos, self.M)
-            m = min(self.M - off, start + n - pos)
-            idx, flip = self._epoch(e)
-            parts.append((idx[off:off + m], None if flip is None else flip[off:off + m]))
+            e, off = divmod(pos, self._size)
+            m = min(self._size - off, start + n - pos)
+            parts.append(tuple(None if t is None else t[off:off + m] for t in self._epoch(e)))
             pos += m
         if self.device.type == 'cuda':
             s = torch.cuda.current_stream()
@@ -109,41 +102,201 @@ class IndexStream(object):
                 t.record_stream(s)                                              # (read on this stream; freed when its epoch is over)
         if len(parts) == 1:
             return parts[0]
-        return torch.cat([p[0] for p in parts]), (torch.cat([p[1] for p in parts]) if self.flags else None)
+        return tuple(None if parts[0][k] is None else torch.cat([p[k] for p in parts]) for k in range(len(parts[0])))
+
+
+class IndexStream(_EpochStream):
+    """An endless sequence of image indices: ``torch.randperm(M, generator=g)`` per epoch, ``g`` a CPU generator seeded with ``seed``
+    (the reference's InfiniteRandomSampler, train.py:51-56); ``arange(M)`` per epoch without ``shuffle``.  Mirror flags
+    (``flags=True``) belong to positions too: ``torch.randint(0, 2, (M,), generator=g2, dtype=torch.uint8)`` per epoch, ``g2`` seeded
+    ``seed + 1``.  ``take`` -> (idx [n] int64, flip [n] uint8 or None)."""
+
+    def __init__(self, M, shuffle=True, seed=0, flags=False, device='cpu'):
+        if int(M) < 1:
+            raise ValueError('an index stream needs at least one image')
+        super(IndexStream, self).__init__(M, 'image', shuffle, flags, device)
+        self.M = int(M)
+        self._g = torch.Generator().manual_seed(int(seed))
+        self._g2 = torch.Generator().manual_seed(int(seed) + 1)
+
+    def _host_epoch(self):
+        idx = torch.randperm(self.M, generator=self._g) if self.shuffle else torch.arange(self.M)
+        return idx, (torch.randint(0, 2, (self.M,), generator=self._g2, dtype=torch.uint8) if self.flags else None)
+
+
+def _tiles(lengths, R):
+    """(strip [P], start column [P]) int64 numpy arrays of the non-overlapping windows ``R`` columns wide of strips of ``lengths``
+    columns, strip-major: item i of a strip dataset."""
+    counts = np.asarray(lengths, dtype=np.int64) // R
+    return np.repeat(np.arange(counts.size, dtype=np.int64), counts), np.concatenate([np.arange(c, dtype=np.int64) * R for c in counts])
+
+
+class CropStream(_EpochStream):
+    """An endless sequence of crops (strip, start column) from strips of ``lengths`` columns, windows ``R`` columns wide.  An epoch
+    has P = sum(T_m // R) positions.  ``shuffle``: position by position, the strip is drawn with probability proportional to its
+    number of window starts w_m = T_m - R + 1 -- p = min(floor(g W), W - 1), W = sum(w_m), strip = searchsorted(cumsum(w), p, right)
+    -- and the start is t = min(floor(f w_m), w_m - 1): every start of every strip is equally likely.  g and f are float64 from
+    ``torch.rand(P)`` on two CPU generators seeded ``seed`` and ``seed + 1``; the mirror flags (``flags=True``) are
+    ``torch.randint(0, 2, (P,), dtype=torch.uint8)`` on a third seeded ``seed + 2``.  Without ``shuffle`` an epoch enumerates the
+    non-overlapping windows (m, i R) in strip-major order.  ``t`` counts full-resolution columns, so the stream does not depend on
+    the stage: at stored level k the start is t >> k, at most cols_k - (R >> k) when T_m and R are multiples of 2^k.
+    ``take`` -> (idx [n] int64, pos [n] int64, flip [n] uint8 or None), with ``IndexStream``'s cursor rules."""
+
+    def __init__(self, lengths, R, shuffle=True, seed=0, flags=False, device='cpu'):
+        self.lengths, self.R = np.asarray([int(t) for t in lengths], dtype=np.int64), int(R)
+        if self.lengths.size < 1 or int(self.lengths.min()) < self.R or self.R < 1:
+            raise ValueError('a crop stream needs at least one strip, each of at least R = %d columns' % self.R)
+        self.P = int((self.lengths // self.R).sum())
+        super(CropStream, self).__init__(self.P, 'crop', shuffle, flags, device)
+        self._g = [torch.Generator().manual_seed(int(seed) + k) for k in range(3)]
+        self._w = self.lengths - self.R + 1
+        self._cum = np.cumsum(self._w)
+
+    def _draw(self):
+        """(strip [P], start [P]) int64 numpy arrays of the next epoch."""
+        if not self.shuffle:
+            return _tiles(self.lengths, self.R)
+        g = torch.rand(self.P, dtype=torch.float64, generator=self._g[0]).numpy()
+        f = torch.rand(self.P, dtype=torch.float64, generator=self._g[1]).numpy()
+        W = int(self._cum[-1])
+        p = np.minimum(np.floor(g * W).astype(np.int64), W - 1)
+        strip = np.searchsorted(self._cum, p, side='right').astype(np.int64)
+        w = self._w[strip]
+        return strip, np.minimum(np.floor(f * w).astype(np.int64), w - 1)
+
+    def _host_epoch(self):
+        strip, start = self._draw()
+        flip = torch.randint(0, 2, (self.P,), generator=self._g[2], dtype=torch.uint8) if self.flags else None
+        return torch.from_numpy(strip), torch.from_numpy(start), flip
 
 
 def _log2(v):
     return int(v).bit_length() - 1
 
 
-class DeviceImageDataset(object):
-    """``images``: uint8 numpy array or torch tensor [M,C,R,R], C in {1, 3}, R a power of two >= 4 (ValueError otherwise); at most
-    ``max_images`` of them are used.  The stack is uploaded once (in chunks) and stays on ``device``.  ``two_channel=True`` announces
-    C = 2, the 'magif' images of ``sound.spectrogram_stack_u8`` (log-magnitude and instantaneous frequency); unannounced, a
-    two-channel stack stays the error it has always been (a sliced RGB stack).
+# ------------------------------------------------------------------------------------------------------- datasets
+class _DeviceDataset(object):
+    """What the two datasets share: N items [C,R,R] kept as uint8 levels on ``device``, the stage, one training stream and the batches.
 
     The stage is dataset depth ``model_depth + model_dataset_depth_offset`` (side 2^depth, so the default offset 2 starts at 4x4).
     ``pyramid`` picks which of the reference's two behaviours supplies a stage below the source resolution:
 
       'chain'   the ``preload=True`` pyramid (dataset.py:144-162): level k is made from level k + 1 with depth difference 1 -- a
-                true 2x2 box mean, rounded to uint8 at EVERY level -- once, at construction (``ops.pyramid_level_u8``), and kept
-                (+1/3 memory); batches read the stage's level.
+                true 2x2 box mean, rounded to uint8 at EVERY level -- once, at construction, and kept (+1/3 memory); batches read the
+                stage's level.
       'direct'  the ``preload=False`` path (dataset.py:201-203): nothing is stored, every batch is taken from the full-resolution
-                stack with depth difference log2(R) - depth, the reference's 4-SAMPLE SUBSAMPLING (the top-left 2x2 of every
+                level with depth difference log2(R) - depth, the reference's 4-SAMPLE SUBSAMPLING (the top-left 2x2 of every
                 2^diff block).
 
     The two give different images for stages two or more levels below the source; they agree one level below and at the source.
 
     Protocol of the reference's DepthDataset: ``model_depth`` and ``alpha`` are plain attributes (DepthManager writes them),
-    ``shape``, ``len()``, ``close()``, and ``dataset[i]`` = the reference's host tensor [C,r,r] fp32 of image i at the current depth
-    and alpha (no mirror), so a plain ``DataLoader(dataset)`` still works.
+    ``shape`` = (N,C,R,R), ``len()``, ``close()``, and ``dataset[i]`` = the reference's host tensor [C,r,r] fp32 of item i at the
+    current depth and alpha (no mirror), so a plain ``DataLoader(dataset)`` still works.
 
     Batches: ``batch(n)`` -> fp32 [n,C,r,r] on ``device``, issued on the current stream; ``loader(n)`` -> endless iterator of
     them, what ``DepthManager(create_dataloader_fun=ds.loader, ...)`` takes; ``metric_batches()`` -> ``f(n)`` for
-    ``SWDMonitor(real_batch_fn=...)``.  The training batches follow one ``IndexStream`` whose cursor belongs to the dataset: a
-    loader made at a stage change continues it, and the sequence does not depend on the batch sizes.  ``mirror_augment`` flips
-    images left-right by the stream's per-position flags.  Under data parallelism (``rank`` of ``world``, one seed everywhere) a
-    draw of n takes positions [cursor + rank n, cursor + (rank + 1) n) and moves the cursor by n world: disjoint images of one epoch.
+    ``SWDMonitor(real_batch_fn=...)``; ``items(idx)`` -> the batch of chosen items.  The training batches follow one stream whose
+    cursor belongs to the dataset: a loader made at a stage change continues it, and the sequence does not depend on the batch sizes.
+    ``mirror_augment`` flips images left-right by the stream's per-position flags.  Under data parallelism (``rank`` of ``world``, one
+    seed everywhere) a draw of n takes positions [cursor + rank n, cursor + (rank + 1) n) and moves the cursor by n world: disjoint
+    positions of one epoch.
+
+    A subclass validates its ``source`` and gives ``_upload(source)`` (the full-resolution level), ``_level_below(level)``,
+    ``_stream(seed, flags)``, ``_make(*drawn, alpha)`` for what its stream hands out, ``_locate(idx)`` (the leading members of such a
+    tuple for items ``idx``), ``level_stack()`` and ``__getitem__``."""
+
+    def __init__(self, source, shape, model_dataset_depth_offset, model_initial_depth, alpha, range_in, range_out, pyramid,
+                 mirror_augment, shuffle, seed, rank, world, device):
+        if pyramid not in ('chain', 'direct'):
+            raise ValueError("pyramid must be 'chain' or 'direct', got %r" % (pyramid,))
+        if int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError('rank %r of world %r' % (rank, world))
+        self.model_depth, self.alpha = model_initial_depth, alpha
+        self.model_dataset_depth_offset = int(model_dataset_depth_offset)
+        self.range_in, self.range_out = tuple(range_in), tuple(range_out)
+        self.pyramid, self.mirror_augment, self.shuffle, self.seed = pyramid, bool(mirror_augment), bool(shuffle), int(seed)
+        self.rank, self.world = int(rank), int(world)
+        self.device = torch.device(device)
+        self._shape = shape
+        self.max_dataset_depth = _log2(shape[2])
+        self.min_dataset_depth = self.max_dataset_depth if pyramid == 'direct' else min(self.max_dataset_depth, max(1, self.model_dataset_depth_offset))
+        self._levels = {self.max_dataset_depth: self._upload(source)}
+        for depth in range(self.max_dataset_depth - 1, self.min_dataset_depth - 1, -1):       # 'chain' only
+            self._levels[depth] = self._level_below(self._levels[depth + 1])
+        self._train = self._stream(self.seed, self.mirror_augment)
+
+    # ------------------------------------------------------------------------------------------------- protocol
+    @property
+    def shape(self):
+        return self._shape
+
+    def __len__(self):
+        return self._shape[0]
+
+    def close(self):
+        """Free the device buffers; the object is of no use afterwards."""
+        self._levels = {}
+        self._train = None
+
+    def _stage(self):
+        """(stored level to read, its levels below the source -- the shift of a start column --, depth difference left to the batch)
+        of the current ``model_depth``."""
+        if not self._levels:
+            raise RuntimeError('the dataset is closed')
+        depth = int(self.model_depth) + self.model_dataset_depth_offset
+        lowest = self.min_dataset_depth if self.pyramid == 'chain' else 1
+        if not lowest <= depth <= self.max_dataset_depth:
+            raise ValueError('model_depth %r + offset %d is dataset depth %d; this dataset has depths %d .. %d'
+                             % (self.model_depth, self.model_dataset_depth_offset, depth, lowest, self.max_dataset_depth))
+        if self.pyramid == 'chain':
+            return self._levels[depth], self.max_dataset_depth - depth, 0
+        return self._levels[self.max_dataset_depth], 0, self.max_dataset_depth - depth
+
+    # -------------------------------------------------------------------------------------------------- batches
+    def _draw(self, n):
+        if self._train is None:
+            raise RuntimeError('the dataset is closed')
+        return self._train.take(n, self.rank, self.world)
+
+    @property
+    def cursor(self):
+        """Next unread position of the training stream (items drawn so far, over all ranks)."""
+        return self._train.cursor
+
+    def batch(self, n, alpha=None):
+        """fp32 batch [n,C,r,r] at the current ``model_depth``, with ``self.alpha`` unless ``alpha`` is given, on the current stream."""
+        return self._make(*self._draw(n), alpha=self.alpha if alpha is None else alpha)
+
+    def loader(self, minibatch_size):
+        """Endless iterator of ``batch(minibatch_size)``; every batch is drawn with the depth and alpha of that moment."""
+        while True:
+            yield self.batch(minibatch_size)
+
+    def metric_batches(self, seed=1):
+        """``f(n)`` -> fp32 batch [n,C,r,r] at the current ``model_depth`` with alpha = 1 and no mirror, from a stream and a
+        cursor of its own (``f.stream``): evaluating a metric does not move the training stream."""
+        stream = self._stream(seed, False)
+
+        def real_batch_fn(n):
+            return self._make(*stream.take(n), alpha=1.0)
+        real_batch_fn.stream = stream
+        return real_batch_fn
+
+    def items(self, idx, alpha=1.0):
+        """fp32 batch [n,C,r,r] of items ``idx`` (an int64 tensor [n] on ``device``, item i as in ``dataset[i]``) at the current
+        ``model_depth``, no mirror; the training stream is not moved."""
+        return self._make(*self._locate(idx), flip=None, alpha=alpha)
+
+
+class DeviceImageDataset(_DeviceDataset):
+    """``images``: uint8 numpy array or torch tensor [M,C,R,R], C in {1, 3}, R a power of two >= 4 (ValueError otherwise); at most
+    ``max_images`` of them are used.  The stack is uploaded once (in chunks) and stays on ``device``.  ``two_channel=True`` announces
+    C = 2, the 'magif' images of ``sound.spectrogram_stack_u8`` (log-magnitude and instantaneous frequency); unannounced, a
+    two-channel stack stays the error it has always been (a sliced RGB stack).
+
+    Stage, ``pyramid`` ('chain' levels are made with ``ops.pyramid_level_u8``), protocol and batches are ``_DeviceDataset``'s; item i
+    is image i, the stream an ``IndexStream`` and a batch one launch of ``ops.real_batch_u8``.
 
     ``device='cpu'``: host mode, the same definition in numpy (fp64)."""
 
@@ -166,23 +319,8 @@ class DeviceImageDataset(object):
             if isinstance(max_images, bool) or int(max_images) != max_images or max_images < 1:
                 raise ValueError('max_images must be None or a positive integer, got %r' % (max_images,))
             M = min(M, int(max_images))
-        if pyramid not in ('chain', 'direct'):
-            raise ValueError("pyramid must be 'chain' or 'direct', got %r" % (pyramid,))
-        if int(world) < 1 or not 0 <= int(rank) < int(world):
-            raise ValueError('rank %r of world %r' % (rank, world))
-        self.model_depth, self.alpha = model_initial_depth, alpha
-        self.model_dataset_depth_offset = int(model_dataset_depth_offset)
-        self.range_in, self.range_out = tuple(range_in), tuple(range_out)
-        self.pyramid, self.mirror_augment, self.shuffle, self.seed = pyramid, bool(mirror_augment), bool(shuffle), int(seed)
-        self.rank, self.world = int(rank), int(world)
-        self.device = torch.device(device)
-        self._shape = (M, C, R, R)
-        self.max_dataset_depth = _log2(R)
-        self.min_dataset_depth = self.max_dataset_depth if pyramid == 'direct' else min(self.max_dataset_depth, max(1, self.model_dataset_depth_offset))
-        self._levels = {self.max_dataset_depth: self._upload(images, M)}
-        for depth in range(self.max_dataset_depth - 1, self.min_dataset_depth - 1, -1):       # 'chain' only
-            self._levels[depth] = self._level_below(self._levels[depth + 1])
-        self._train = IndexStream(M, self.shuffle, self.seed, flags=self.mirror_augment, device=self.device)
+        super(DeviceImageDataset, self).__init__(images, (M, C, R, R), model_dataset_depth_offset, model_initial_depth, alpha, range_in,
+                                                 range_out, pyramid, mirror_augment, shuffle, seed, rank, world, device)
 
     # --------------------------------------------------------------------------------------------- construction
     @classmethod
@@ -206,7 +344,8 @@ class DeviceImageDataset(object):
                 raise ValueError('%s is %s, %s is %s' % (files[0], ims[0].shape, f, ims[-1].shape))
         return cls(np.stack(ims), **kw)
 
-    def _upload(self, images, M):
+    def _upload(self, images):
+        M = len(self)
         if self.device.type != 'cuda':
             host = images[:M] if torch.is_tensor(images) else torch.from_numpy(np.array(images[:M]))
             return host.contiguous()
@@ -227,38 +366,16 @@ class DeviceImageDataset(object):
             return ops.pyramid_level_u8(stack, 1, self.range_in)
         return torch.from_numpy(level_host(stack.numpy(), 1, self.range_in))
 
+    def _stream(self, seed, flags):
+        return IndexStream(len(self), self.shuffle, seed, flags=flags, device=self.device)
+
     # ------------------------------------------------------------------------------------------------- protocol
-    @property
-    def shape(self):
-        return self._shape
-
-    def __len__(self):
-        return self._shape[0]
-
-    def close(self):
-        """Free the device buffers; the object is of no use afterwards."""
-        self._levels = {}
-        self._train = None
-
-    def _stage(self):
-        """(stack to read, depth difference) of the current ``model_depth``."""
-        if not self._levels:
-            raise RuntimeError('the dataset is closed')
-        depth = int(self.model_depth) + self.model_dataset_depth_offset
-        lowest = self.min_dataset_depth if self.pyramid == 'chain' else 1
-        if not lowest <= depth <= self.max_dataset_depth:
-            raise ValueError('model_depth %r + offset %d is dataset depth %d; this dataset has depths %d .. %d'
-                             % (self.model_depth, self.model_dataset_depth_offset, depth, lowest, self.max_dataset_depth))
-        if self.pyramid == 'chain':
-            return self._levels[depth], 0
-        return self._levels[self.max_dataset_depth], self.max_dataset_depth - depth
-
     def level_stack(self):
         """The uint8 stack [M,C,r,r] of the current ``model_depth``: what the batches of this stage are made from before fade-in, mirror
         and range (``metrics.NearestNeighbours`` searches it).  'chain': the stored level itself, no copy.  'direct': the stack itself at
         the source resolution; below it the level is made here, ``UPLOAD_CHUNK_BYTES`` of the stack at a time (``ops.pyramid_level_u8``
         on the device, ``level_host`` in host mode), and is NOT kept -- a caller that needs it repeatedly within a stage keeps it."""
-        stack, dd = self._stage()
+        stack, _, dd = self._stage()
         if dd == 0:
             return stack
         M, C, R, _ = self._shape
@@ -278,13 +395,16 @@ class DeviceImageDataset(object):
         i = int(item)
         if not -len(self) <= i < len(self):
             raise IndexError('image %d of %d' % (i, len(self)))
-        stack, dd = self._stage()
+        stack, _, dd = self._stage()
         image = stack[i % len(self)].cpu().numpy()
         return torch.from_numpy(prepare_host(level_host(image, dd, self.range_in), self.alpha, self.range_in, self.range_out))
 
     # -------------------------------------------------------------------------------------------------- batches
+    def _locate(self, idx):
+        return (idx,)
+
     def _make(self, idx, flip, alpha):
-        stack, dd = self._stage()
+        stack, _, dd = self._stage()
         if stack.is_cuda:
             from . import ops
             return ops.real_batch_u8(stack, idx, flip, dd, alpha, self.range_in, self.range_out)
@@ -293,35 +413,7 @@ class DeviceImageDataset(object):
 
     def draw_indices(self, n):
         """The next ``n`` (image indices, mirror flags or None) of this rank from the training stream; moves the cursor."""
-        if self._train is None:
-            raise RuntimeError('the dataset is closed')
-        return self._train.take(n, self.rank, self.world)
-
-    @property
-    def cursor(self):
-        """Next unread position of the training stream (images drawn so far, over all ranks)."""
-        return self._train.cursor
-
-    def batch(self, n, alpha=None):
-        """fp32 batch [n,C,r,r] at the current ``model_depth``, with ``self.alpha`` unless ``alpha`` is given, on the current stream."""
-        idx, flip = self.draw_indices(n)
-        return self._make(idx, flip, self.alpha if alpha is None else alpha)
-
-    def loader(self, minibatch_size):
-        """Endless iterator of ``batch(minibatch_size)``; every batch is drawn with the depth and alpha of that moment."""
-        while True:
-            yield self.batch(minibatch_size)
-
-    def metric_batches(self, seed=1):
-        """``f(n)`` -> fp32 batch [n,C,r,r] at the current ``model_depth`` with alpha = 1 and no mirror, from an index stream and a
-        cursor of its own: evaluating a metric does not move the training stream."""
-        stream = IndexStream(len(self), self.shuffle, seed, flags=False, device=self.device)
-
-        def real_batch_fn(n):
-            idx, _ = stream.take(n)
-            return self._make(idx, None, 1.0)
-        real_batch_fn.stream = stream
-        return real_batch_fn
+        return self._draw(n)
 
 
 # ------------------------------------------------------------------------------------------- strips: random time-crops
@@ -376,107 +468,28 @@ class StripLevel(object):
         return int(self.buffer.numel())
 
 
-class CropStream(object):
-    """The positions 0, 1, 2, ... of an endless sequence of crops (strip, start column) from strips of ``lengths`` columns, windows
-    ``R`` columns wide.  An epoch has P = sum(T_m // R) positions.  ``shuffle``: position by position, the strip is drawn with
-    probability proportional to its number of window starts w_m = T_m - R + 1 -- p = min(floor(g W), W - 1), W = sum(w_m), strip =
-    searchsorted(cumsum(w), p, right) -- and the start is t = min(floor(f w_m), w_m - 1): every start of every strip is equally
-    likely.  g and f are float64 from ``torch.rand(P)`` on two CPU generators seeded ``seed`` and ``seed + 1``; the mirror flags
-    (``flags=True``) are ``torch.randint(0, 2, (P,), dtype=torch.uint8)`` on a third seeded ``seed + 2``.  Without ``shuffle`` an
-    epoch enumerates the non-overlapping windows (m, i R) in strip-major order.  ``t`` counts full-resolution columns, so the stream
-    does not depend on the stage: at stored level k the start is t >> k, at most cols_k - (R >> k) when T_m and R are multiples
-    of 2^k.  An epoch's arrays are made once and moved to ``device`` once; ``take`` hands out slices (concatenated on the device
-    across an epoch boundary) with ``IndexStream``'s cursor rules: no copy and no synchronisation per batch."""
-
-    def __init__(self, lengths, R, shuffle=True, seed=0, flags=False, device='cpu'):
-        self.lengths, self.R = np.asarray([int(t) for t in lengths], dtype=np.int64), int(R)
-        if self.lengths.size < 1 or int(self.lengths.min()) < self.R or self.R < 1:
-            raise ValueError('a crop stream needs at least one strip, each of at least R = %d columns' % self.R)
-        self.P = int((self.lengths // self.R).sum())
-        self.shuffle, self.flags, self.device = bool(shuffle), bool(flags), torch.device(device)
-        self._g = [torch.Generator().manual_seed(int(seed) + k) for k in range(3)]
-        self._w = self.lengths - self.R + 1
-        self._cum = np.cumsum(self._w)
-        self._epochs = {}                # epoch number -> (idx, pos, flip or None) on ``device``
-        self._made = 0                   # epochs generated so far (they must be drawn in order)
-        self.cursor = 0
-
-    def _draw(self):
-        """(strip [P], start [P]) int64 numpy arrays of the next epoch."""
-        if not self.shuffle:
-            counts = self.lengths // self.R
-            strip = np.repeat(np.arange(self.lengths.size, dtype=np.int64), counts)
-            start = np.concatenate([np.arange(c, dtype=np.int64) * self.R for c in counts])
-            return strip, start
-        g = torch.rand(self.P, dtype=torch.float64, generator=self._g[0]).numpy()
-        f = torch.rand(self.P, dtype=torch.float64, generator=self._g[1]).numpy()
-        W = int(self._cum[-1])
-        p = np.minimum(np.floor(g * W).astype(np.int64), W - 1)
-        strip = np.searchsorted(self._cum, p, side='right').astype(np.int64)
-        w = self._w[strip]
-        return strip, np.minimum(np.floor(f * w).astype(np.int64), w - 1)
-
-    def _epoch(self, e):
-        while self._made <= e:
-            strip, start = self._draw()
-            flip = torch.randint(0, 2, (self.P,), generator=self._g[2], dtype=torch.uint8) if self.flags else None
-            self._epochs[self._made] = (torch.from_numpy(strip).to(self.device), torch.from_numpy(start).to(self.device),
-                                        None if flip is None else flip.to(self.device))
-            self._made += 1
-        return self._epochs[e]
-
-    def take(self, n, rank=0, world=1):
-        """(idx [n] int64, pos [n] int64, flip [n] uint8 or None) at positions [cursor + rank n, cursor + (rank + 1) n); the cursor
-        moves by n world."""
-        n = int(n)
-        if n < 1:
-            raise ValueError('a draw needs at least one crop')
-        first = self.cursor + rank * n
-        self.cursor += n * world
-        for e in [k for k in self._epochs if k < first // self.P]:              # epochs every rank has left behind
-            del self._epochs[e]
-        parts, at = [], first
-        while at < first + n:
-            e, off = divmod(at, self.P)
-            m = min(self.P - off, first + n - at)
-            parts.append(tuple(None if t is None else t[off:off + m] for t in self._epoch(e)))
-            at += m
-        if self.device.type == 'cuda':
-            s = torch.cuda.current_stream()
-            for t in (t for p in parts for t in p if t is not None):
-                t.record_stream(s)                                              # (read on this stream; freed when its epoch is over)
-        if len(parts) == 1:
-            return parts[0]
-        return tuple(torch.cat([p[k] for p in parts]) if parts[0][k] is not None else None for k in range(3))
-
-
-class DeviceStripDataset(object):
+class DeviceStripDataset(_DeviceDataset):
     """Random time-crops of long recordings: ``strips`` is a list of uint8 numpy arrays or torch tensors [C, R, T_m] (spectrograms,
     time along the last axis), one C in {1, 2, 3} and one R (a power of two >= 4) for all of them, T_m >= R (ValueError otherwise,
     naming the strip).  Every strip is TRUNCATED to R (T_m // R) columns: then every pyramid level has whole columns and the
     non-overlapping windows tile every level.  A training image is the R x R window at a random start column t of a random strip
     (``CropStream``): all of every recording is used and every batch is a new translation.  Each strip is stored once, uint8, in HBM
     (``StripLevel``), and a batch -- gather of the windows where the strips lie, pyramid level, mirror, fade-in, dynamic range -- is
-    one launch (``ops.crop_batch_u8`` / csrc/crop_batch.hip): nothing crosses PCIe and nothing synchronises per batch.
+    one launch (``ops.crop_batch_u8``): nothing crosses PCIe and nothing synchronises per batch.
 
-    The stage is dataset depth ``model_depth + model_dataset_depth_offset`` (side r = 2^depth), k = log2(R) - depth levels below the
-    source.  ``pyramid`` as in ``DeviceImageDataset``:
+    Stage, ``pyramid``, protocol and batches are ``_DeviceDataset``'s.  k = log2(R) - depth levels below the source,
 
-      'chain'   level k is made from level k + 1 with ``ops.pyramid_level_u8`` per strip (a 2x2 box mean rounded to uint8 at every
-                level), once, at construction, and kept (+1/3 memory); a batch reads the window [t >> k, (t >> k) + r) of the stage's
+      'chain'   level k is made per strip (``ops.pyramid_level_u8``); a batch reads the window [t >> k, (t >> k) + r) of the stage's
                 level, so a stage k levels down translates in steps of 2^k full-resolution columns.
-      'direct'  only the full-resolution strips are kept; a batch takes the window [t, t + R) and subsamples it by depth
-                difference k (the top-left 2x2 of every 2^k block), at every start t.
+      'direct'  a batch takes the window [t, t + R) of the full-resolution strip and subsamples it by depth difference k, at every
+                start t.
 
-    For windows that start at a multiple of R (``dataset[i]``, ``level_stack()``, ``shuffle=False``) the two agree at the source and
-    one level below, as for images.
+    For windows that start at a multiple of R (``dataset[i]``, ``items``, ``level_stack()``, ``shuffle=False``) the two agree at the
+    source and one level below, as for images.
 
-    Protocol and methods are ``DeviceImageDataset``'s: ``model_depth`` and ``alpha`` are plain attributes (``DepthManager`` writes
-    them), ``shape`` = (P, C, R, R) and ``len()`` = P = sum(T_m // R), the windows of an epoch; ``dataset[i]`` is the host tensor
-    [C,r,r] fp32 of NON-OVERLAPPING window i (strip-major) at the current depth and alpha; ``batch(n)``, ``loader(n)``, ``cursor``,
-    ``metric_batches(seed)`` and ``close()``.  ``level_stack()`` materialises the uint8 [P,C,r,r] stack of the non-overlapping
-    windows of the current stage per call, so ``NNMonitor``, ``NDBMonitor`` and ``SWDMonitor(real_batch_fn=...)`` work unchanged.
-    Under data parallelism (``rank`` of ``world``, one seed everywhere) the ranks take disjoint positions of one stream.
+    ``shape`` = (P, C, R, R) and ``len()`` = P = sum(T_m // R), the windows of an epoch; item i is NON-OVERLAPPING window i
+    (strip-major).  ``level_stack()`` materialises the uint8 [P,C,r,r] stack of the non-overlapping windows of the current stage per
+    call, so ``NNMonitor``, ``NDBMonitor`` and ``SWDMonitor(real_batch_fn=...)`` work unchanged.
 
     ``device='cpu'``: host mode, the numpy twin -- it slices the same windows and calls ``batch_host``."""
 
@@ -499,25 +512,11 @@ class DeviceStripDataset(object):
                 raise ValueError('strip %d is [%d,%d,T], strip 0 is [%d,%d,T]' % (m, s.shape[0], s.shape[1], C, R))
             if int(s.shape[2]) < R:
                 raise ValueError('strip %d: %d columns, a window needs %d' % (m, s.shape[2], R))
-        if pyramid not in ('chain', 'direct'):
-            raise ValueError("pyramid must be 'chain' or 'direct', got %r" % (pyramid,))
-        if int(world) < 1 or not 0 <= int(rank) < int(world):
-            raise ValueError('rank %r of world %r' % (rank, world))
-        self.model_depth, self.alpha = model_initial_depth, alpha
-        self.model_dataset_depth_offset = int(model_dataset_depth_offset)
-        self.range_in, self.range_out = tuple(range_in), tuple(range_out)
-        self.pyramid, self.mirror_augment, self.shuffle, self.seed = pyramid, bool(mirror_augment), bool(shuffle), int(seed)
-        self.rank, self.world = int(rank), int(world)
-        self.device = torch.device(device)
         self.lengths = [R * (int(s.shape[2]) // R) for s in strips]              # columns kept of every strip
-        self._windows = np.cumsum([0] + [t // R for t in self.lengths])         # first non-overlapping window of strip m
-        self._shape = (int(self._windows[-1]), C, R, R)
-        self.max_dataset_depth = _log2(R)
-        self.min_dataset_depth = self.max_dataset_depth if pyramid == 'direct' else min(self.max_dataset_depth, max(1, self.model_dataset_depth_offset))
-        self._levels = {self.max_dataset_depth: self._upload(strips)}
-        for depth in range(self.max_dataset_depth - 1, self.min_dataset_depth - 1, -1):       # 'chain' only
-            self._levels[depth] = self._level_below(self._levels[depth + 1])
-        self._train = CropStream(self.lengths, R, self.shuffle, self.seed, flags=self.mirror_augment, device=self.device)
+        self._item_at = _tiles(self.lengths, R)                                  # item i -> (strip, start column), on the host ...
+        super(DeviceStripDataset, self).__init__(strips, (len(self._item_at[0]), C, R, R), model_dataset_depth_offset, model_initial_depth,
+                                                 alpha, range_in, range_out, pyramid, mirror_augment, shuffle, seed, rank, world, device)
+        self._item_at_dev = tuple(torch.from_numpy(a).to(self.device) for a in self._item_at)      # ... and where ``items`` looks them up
 
     # --------------------------------------------------------------------------------------------- construction
     @classmethod
@@ -563,35 +562,13 @@ class DeviceStripDataset(object):
             below.strip(m).copy_(ops.pyramid_level_u8(level.strip(m), 1, self.range_in))       # (takes H != W; makes the view contiguous)
         return below
 
+    def _stream(self, seed, flags):
+        return CropStream(self.lengths, self._shape[2], self.shuffle, seed, flags=flags, device=self.device)
+
     # ------------------------------------------------------------------------------------------------- protocol
-    @property
-    def shape(self):
-        return self._shape
-
-    def __len__(self):
-        return self._shape[0]
-
-    def close(self):
-        """Free the device buffers; the object is of no use afterwards."""
-        self._levels = {}
-        self._train = None
-
     def level_bytes(self):
         """{dataset depth: bytes of its stored level} (device mode: the padded buffer; host mode: the arrays)."""
         return dict((d, lv.nbytes if isinstance(lv, StripLevel) else int(sum(s.nbytes for s in lv))) for d, lv in self._levels.items())
-
-    def _stage(self):
-        """(stored level to read, shift, depth difference) of the current ``model_depth``."""
-        if not self._levels:
-            raise RuntimeError('the dataset is closed')
-        depth = int(self.model_depth) + self.model_dataset_depth_offset
-        lowest = self.min_dataset_depth if self.pyramid == 'chain' else 1
-        if not lowest <= depth <= self.max_dataset_depth:
-            raise ValueError('model_depth %r + offset %d is dataset depth %d; this dataset has depths %d .. %d'
-                             % (self.model_depth, self.model_dataset_depth_offset, depth, lowest, self.max_dataset_depth))
-        if self.pyramid == 'chain':
-            return self._levels[depth], self.max_dataset_depth - depth, 0
-        return self._levels[self.max_dataset_depth], 0, self.max_dataset_depth - depth
 
     @staticmethod
     def _strip_of(level, m):
@@ -631,13 +608,14 @@ class DeviceStripDataset(object):
         i = int(item)
         if not -len(self) <= i < len(self):
             raise IndexError('window %d of %d' % (i, len(self)))
-        i %= len(self)
-        m = int(np.searchsorted(self._windows, i, side='right')) - 1
         level, shift, dd = self._stage()
-        window = self._windows_host(level, [m], [(i - int(self._windows[m])) * self._shape[2]], shift)[0]
+        window = self._windows_host(level, *(a[[i % len(self)]] for a in self._item_at), shift=shift)[0]
         return torch.from_numpy(prepare_host(level_host(window, dd, self.range_in), self.alpha, self.range_in, self.range_out))
 
     # -------------------------------------------------------------------------------------------------- batches
+    def _locate(self, idx):
+        return tuple(a[idx] for a in self._item_at_dev)
+
     def _make(self, idx, pos, flip, alpha):
         level, shift, dd = self._stage()
         if isinstance(level, StripLevel):
@@ -650,32 +628,4 @@ class DeviceStripDataset(object):
     def draw_crops(self, n):
         """The next ``n`` (strips, start columns at full resolution, mirror flags or None) of this rank from the training stream;
         moves the cursor."""
-        if self._train is None:
-            raise RuntimeError('the dataset is closed')
-        return self._train.take(n, self.rank, self.world)
-
-    @property
-    def cursor(self):
-        """Next unread position of the training stream (crops drawn so far, over all ranks)."""
-        return self._train.cursor
-
-    def batch(self, n, alpha=None):
-        """fp32 batch [n,C,r,r] at the current ``model_depth``, with ``self.alpha`` unless ``alpha`` is given, on the current stream."""
-        idx, pos, flip = self.draw_crops(n)
-        return self._make(idx, pos, flip, self.alpha if alpha is None else alpha)
-
-    def loader(self, minibatch_size):
-        """Endless iterator of ``batch(minibatch_size)``; every batch is drawn with the depth and alpha of that moment."""
-        while True:
-            yield self.batch(minibatch_size)
-
-    def metric_batches(self, seed=1):
-        """``f(n)`` -> fp32 batch [n,C,r,r] at the current ``model_depth`` with alpha = 1 and no mirror, from a crop stream and a
-        cursor of its own: evaluating a metric does not move the training stream."""
-        stream = CropStream(self.lengths, self._shape[2], self.shuffle, seed, flags=False, device=self.device)
-
-        def real_batch_fn(n):
-            idx, pos, _ = stream.take(n)
-            return self._make(idx, pos, None, 1.0)
-        real_batch_fn.stream = stream
-        return real_batch_fn
+        return self._draw(n)

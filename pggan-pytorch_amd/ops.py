@@ -825,6 +825,25 @@ def pyramid_level_u8(batch_u8, depthdiff, range_in=(0, 255)):
     return out
 
 
+def _batch_operands(where, device, idx, pos, flip, C, S, depthdiff, alloc=True):
+    """What ``real_batch_u8`` and ``crop_batch_u8`` share: the checks of the per-item tensors ``idx``, ``pos`` (None for a stack) and
+    ``flip`` against the ``device`` of the ``where`` ('stack', 'level'), and the fp32 output [n,C,r,r], r = S >> depthdiff (not with
+    ``alloc=False``: the callee allocates).  Returns (n, out)."""
+    for name, t in (('idx', idx),) if pos is None else (('idx', idx), ('pos', pos)):
+        if not torch.is_tensor(t) or t.device != device or t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1 or t.numel() < 1:
+            raise ValueError('%s: expected a contiguous, non-empty int64 tensor [n] on the device of the %s' % (name, where))
+    n = idx.numel()
+    if pos is not None and pos.numel() != n:
+        raise ValueError('idx holds %d strips, pos %d start columns' % (n, pos.numel()))
+    if flip is not None and (not torch.is_tensor(flip) or flip.device != device or flip.dtype != torch.uint8
+                             or not flip.is_contiguous() or tuple(flip.shape) != (n,)):
+        raise ValueError('flip: expected None or a contiguous uint8 tensor [%d] on the device of the %s' % (n, where))
+    if not alloc:
+        return n, None
+    r = S >> depthdiff if 0 <= depthdiff < 31 else 0
+    return n, torch.empty((n, C, r, r), device=device, dtype=torch.float32)
+
+
 def real_batch_u8(stack_u8, idx, flip=None, depthdiff=0, alpha=1.0, range_in=(0, 255), range_out=(-1, 1), check=False):
     """uint8 device stack [M,C,S,S] -> fp32 batch [n,C,r,r], r = S >> depthdiff, in one launch (pg_real_batch_u8, csrc/real_batch.hip):
     image ``idx[j]`` (int64 device tensor [n]), its pyramid level (``pyramid_level_u8``), mirrored where ``flip[j] != 0`` (uint8 device
@@ -837,22 +856,15 @@ def real_batch_u8(stack_u8, idx, flip=None, depthdiff=0, alpha=1.0, range_in=(0,
     M, C, S, S2 = stack_u8.shape
     if S != S2 or M < 1:
         raise ValueError('expected at least one square image, got a stack of shape %s' % (tuple(stack_u8.shape),))
-    if not torch.is_tensor(idx) or idx.device != stack_u8.device or idx.dtype != torch.int64 or not idx.is_contiguous() or idx.dim() != 1 or idx.numel() < 1:
-        raise ValueError('idx: expected a contiguous, non-empty int64 tensor [n] on the device of the stack')
-    n = idx.numel()
-    if flip is not None and (not torch.is_tensor(flip) or flip.device != stack_u8.device or flip.dtype != torch.uint8
-                             or not flip.is_contiguous() or tuple(flip.shape) != (n,)):
-        raise ValueError('flip: expected None or a contiguous uint8 tensor [%d] on the device of the stack' % n)
+    depthdiff = int(depthdiff)
+    n, out = _batch_operands('stack', stack_u8.device, idx, None, flip, C, S, depthdiff, C != 2)
     if check:
         lo, hi = int(idx.min()), int(idx.max())
         if lo < 0 or hi >= M:
             raise IndexError('idx holds values in [%d, %d] for a stack of %d images' % (lo, hi, M))
-    depthdiff = int(depthdiff)
     if C == 2:                                                   # pg_real_batch_u8 takes C in {1, 3}; two channels are an addition
         from . import phase
         return phase.real_batch_2ch_u8(stack_u8, idx, flip, depthdiff, alpha, range_in, range_out)
-    r = S >> depthdiff if 0 <= depthdiff < 31 else 0
-    out = torch.empty((n, C, r, r), device=stack_u8.device, dtype=torch.float32)
     _lib.call('pg_real_batch_u8', stack_u8.data_ptr(), M, C, S, depthdiff, idx.data_ptr(), None if flip is None else flip.data_ptr(), n,
               out.data_ptr(), float(alpha), float(range_in[0]), float(range_in[1]), float(range_out[0]), float(range_out[1]), _stream())
     return out
@@ -865,10 +877,11 @@ CROP_TABLE_WORDS, CROP_PITCH_ALIGN = CROP['TABLE_WORDS'], CROP['PITCH_ALIGN']
 def crop_batch_u8(level, idx, pos, flip=None, shift=0, depthdiff=0, alpha=1.0, range_in=(0, 255), range_out=(-1, 1), check=False):
     """One stored level of uint8 device strips (``dataset.StripLevel``: the flat ``buffer``, its ``table`` [M,3] int64 of (byte offset,
     row pitch, columns), ``C`` and the rows ``S``) -> fp32 batch [n,C,r,r], r = S >> depthdiff, in one launch (pg_crop_batch_u8,
-    csrc/crop_batch.hip): image j is the window of columns [u, u + S), u = pos[j] >> shift, of strip ``idx[j]`` (int64 device tensors
-    [n]), treated as ``real_batch_u8`` treats an image of a stack -- pyramid level, mirror where ``flip[j] != 0``, fade, range -- and
-    equal to it bit for bit on the materialised windows.  The device checks neither ``idx`` nor ``pos``: ``check=True`` reads their
-    extrema back (a host synchronisation) and raises IndexError for a strip outside [0, M) or a window that leaves its strip."""
+    csrc/real_batch.hip): image j is the window of columns [u, u + S), u = pos[j] >> shift, of strip ``idx[j]`` (int64 device tensors
+    [n]), treated as ``real_batch_u8`` treats an image of a stack -- the same two kernels, instantiated for strips: pyramid level, mirror
+    where ``flip[j] != 0``, fade, range -- and equal to it bit for bit on the materialised windows.  The device checks neither ``idx``
+    nor ``pos``: ``check=True`` reads their extrema back (a host synchronisation) and raises IndexError for a strip outside [0, M) or a
+    window that leaves its strip."""
     require_gpu()
     buf, table = level.buffer, level.table
     if not torch.is_tensor(buf) or not buf.is_cuda or buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.dim() != 1:
@@ -877,16 +890,10 @@ def crop_batch_u8(level, idx, pos, flip=None, shift=0, depthdiff=0, alpha=1.0, r
             or table.dim() != 2 or table.shape[0] < 1 or table.shape[1] != CROP_TABLE_WORDS):
         raise ValueError('level.table: expected a contiguous int64 tensor [M,%d] on the device of the buffer' % CROP_TABLE_WORDS)
     M, C, S = table.shape[0], int(level.C), int(level.S)
-    for name, t in (('idx', idx), ('pos', pos)):
-        if not torch.is_tensor(t) or t.device != buf.device or t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1 or t.numel() < 1:
-            raise ValueError('%s: expected a contiguous, non-empty int64 tensor [n] on the device of the level' % name)
-    n = idx.numel()
-    if pos.numel() != n:
-        raise ValueError('idx holds %d strips, pos %d start columns' % (n, pos.numel()))
-    if flip is not None and (not torch.is_tensor(flip) or flip.device != buf.device or flip.dtype != torch.uint8
-                             or not flip.is_contiguous() or tuple(flip.shape) != (n,)):
-        raise ValueError('flip: expected None or a contiguous uint8 tensor [%d] on the device of the level' % n)
     shift, depthdiff = int(shift), int(depthdiff)
+    if pos is None:
+        raise ValueError('pos: expected a contiguous, non-empty int64 tensor [n] on the device of the level')
+    n, out = _batch_operands('level', buf.device, idx, pos, flip, C, S, depthdiff)
     if check:
         lo, hi = int(idx.min()), int(idx.max())
         if lo < 0 or hi >= M:
@@ -896,8 +903,6 @@ def crop_batch_u8(level, idx, pos, flip=None, shift=0, depthdiff=0, alpha=1.0, r
         lo, hi = int(u.min()), int(over.max())
         if lo < 0 or hi > 0:
             raise IndexError('pos: a window starts at column %d or ends %d columns past the end of its strip' % (lo, hi))
-    r = S >> depthdiff if 0 <= depthdiff < 31 else 0
-    out = torch.empty((n, C, r, r), device=buf.device, dtype=torch.float32)
     _lib.call('pg_crop_batch_u8', buf.data_ptr(), table.data_ptr(), M, C, S, shift, depthdiff, idx.data_ptr(), pos.data_ptr(),
               None if flip is None else flip.data_ptr(), n, out.data_ptr(), float(alpha), float(range_in[0]), float(range_in[1]),
               float(range_out[0]), float(range_out[1]), _stream())

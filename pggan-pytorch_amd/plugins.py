@@ -548,8 +548,8 @@ class NDBMonitor(Evaluation):
         stage = getattr(self.dataset, '_stage', None)
         if stage is None:
             return int(self.dataset.level_stack().shape[-1])
-        stack, depthdiff = stage()                                           # (no level is made for the answer)
-        return int(stack.shape[-1]) >> depthdiff
+        _, shift, depthdiff = stage()                                        # (no level is made for the answer)
+        return int(self.dataset.shape[-1]) >> (shift + depthdiff)
 
     def evaluate(self, tick):
         from .metrics import NDB
@@ -573,9 +573,9 @@ class ProjectionMonitor(Evaluation):
     pyramid loss the search ends at says how well the generator can reproduce images it was not asked to produce.  It is defined for
     1-, 2-, 3- and 4-channel networks alike.
 
-    ``source``: a ``DeviceImageDataset`` -- the targets are its LAST ``num_images`` images at the current growth stage with alpha 1 and no
-    mirror, the same indices at every evaluation (the end of the stack, where ``metrics.NDB`` holds images out as well; the training
-    stream is not moved) -- or ``real_batch_fn(n)`` -> fp32 device batch ``[n,C,r,r]`` at the current stage's resolution, called ONCE per
+    ``source``: a ``DeviceImageDataset`` or ``DeviceStripDataset`` -- the targets are its LAST ``num_images`` items (``dataset.items``)
+    at the current growth stage with alpha 1 and no mirror, the same indices at every evaluation (the end of the stack, where
+    ``metrics.NDB`` holds images out as well; the training stream is not moved) -- or ``real_batch_fn(n)`` -> fp32 device batch ``[n,C,r,r]`` at the current stage's resolution, called ONCE per
     resolution and kept (give it a seeded stream of its own, e.g. ``dataset.metric_batches(seed)``).  ``projector_kwargs`` go to
     ``Projector`` (lr, betas, level_weights, seed).
 
@@ -602,8 +602,8 @@ class ProjectionMonitor(Evaluation):
             raise ValueError('num_images must be a positive integer, got %r' % (num_images,))
         if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
             raise ValueError('steps must be a positive integer, got %r' % (steps,))
-        if not callable(source) and not (hasattr(source, '_make') and hasattr(source, '__len__')):
-            raise ValueError('ProjectionMonitor: source must be a DeviceImageDataset or a function n -> real batch, got %s' % type(source).__name__)
+        if not callable(source) and not (hasattr(source, 'items') and hasattr(source, '__len__')):
+            raise ValueError('ProjectionMonitor: source must be a device dataset or a function n -> real batch, got %s' % type(source).__name__)
         if not callable(source) and len(source) < int(num_images):
             raise ValueError('ProjectionMonitor: %d targets from a dataset of %d images' % (num_images, len(source)))
         self.source = source
@@ -621,7 +621,7 @@ class ProjectionMonitor(Evaluation):
             ds = self.source
             M = len(ds)
             idx = torch.arange(M - self.num_images, M, dtype=torch.int64, device=getattr(ds, 'device', 'cpu'))
-            return ds._make(idx, None, 1.0)
+            return ds.items(idx)
         t = self._targets.get(resolution)
         if t is None:
             t = self.source(self.num_images)

@@ -1,11 +1,13 @@
-"""pg_crop_batch_u8 (csrc/crop_batch.hip) and ``DeviceStripDataset`` on the device.  The kernel is defined by an equality: its batch
-is, bit for bit, ``ops.real_batch_u8`` of the same windows materialised as a stack -- so every comparison here is ``==``, against
-that and against ``dataset.batch_host``.  The dataset is held against its ``device='cpu'`` twin batch for batch."""
+"""pg_crop_batch_u8 (csrc/real_batch.hip: the batch kernels with strips as their source) and ``DeviceStripDataset`` on the device.  The
+kernel is defined by an equality: its batch is, bit for bit, ``ops.real_batch_u8`` of the same windows materialised as a stack -- so
+every comparison here is ``==``, against that and against ``dataset.batch_host``.  The dataset is held against its ``device='cpu'``
+twin batch for batch, and against ``DeviceImageDataset`` on square strips."""
 import numpy as np
 import pytest
 import torch
 
-from crops_ref import all_starts, make_strips, windows
+from crops_ref import all_starts, check_items, check_square_strips_equal_the_stack, make_strips, windows
+from dataset_ref import make_stack
 
 import pggan_amd as pg
 
@@ -90,6 +92,24 @@ def test_dataset_equals_its_host_twin(C, R, pyr):
     a.close()
     with pytest.raises(RuntimeError):
         a.batch(1)
+
+
+# r = 4 and every 'direct' stage below R take the blocks kernel, r >= 8 at depth difference 0 the rows kernel: both kernels of both sources
+@pytest.mark.parametrize('pyr', ['chain', 'direct'])
+@pytest.mark.parametrize('C,R', [(1, 8), (2, 16), (3, 32)])
+def test_square_strips_are_the_image_dataset(C, R, pyr):
+    check_square_strips_equal_the_stack(pg, C, R, pyr, 'cuda')
+
+
+@pytest.mark.parametrize('pyr', ['chain', 'direct'])
+def test_items_are_the_getitem_tensors(pyr):
+    check_items(DeviceStripDataset(make_strips(2, 16, seed=8), pyramid=pyr, seed=2, device='cuda'), (0, 2))
+    images = pg.DeviceImageDataset(make_stack(5, 3, 16, seed=9), pyramid=pyr, seed=2, device='cuda')
+    idx = check_items(images, (0, 2))
+    for depth in (0, 2):                                                              # what _make(idx, None, 1.0) gave: the stage's stack
+        images.model_depth = depth
+        stack, _, dd = images._stage()
+        assert torch.equal(images.items(idx), ops.real_batch_u8(stack, idx, None, dd, 1.0, images.range_in, images.range_out))
 
 
 def _top(R):

@@ -4,7 +4,8 @@ import numpy as np
 import pytest
 import torch
 
-from crops_ref import make_strips, pyramid, windows
+from crops_ref import check_items, check_square_strips_equal_the_stack, make_strips, pyramid, windows
+from dataset_ref import make_stack
 
 import pggan_amd as pg
 
@@ -221,6 +222,34 @@ def test_metric_batches_leave_the_training_cursor_alone():
     want = ds_mod.batch_host(windows(pyramid(make_strips(1, R, seed=6), 1, ds_mod.level_host), idx.numpy(), pos.numpy() >> 1, R // 2),
                              np.arange(4), None, 0, 1.0)
     assert np.array_equal(got.numpy(), want)
+
+
+@pytest.mark.parametrize('pyr', ['chain', 'direct'])
+@pytest.mark.parametrize('C,side', [(1, 8), (2, 16), (3, 32)])
+def test_square_strips_are_the_image_dataset(C, side, pyr):
+    check_square_strips_equal_the_stack(pg, C, side, pyr, 'cpu')
+
+
+@pytest.mark.parametrize('pyr', ['chain', 'direct'])
+def test_items_are_the_getitem_tensors(pyr):
+    strips = host(make_strips(2, 16, seed=8), pyramid=pyr, seed=2)
+    check_items(strips, (0, 2))
+    images = pg.DeviceImageDataset(make_stack(5, 3, 16, seed=9), pyramid=pyr, seed=2, device='cpu')
+    idx = check_items(images, (0, 2))
+    for depth in (0, 2):                                                              # what _make(idx, None, 1.0) gave: the stage's stack
+        images.model_depth = depth
+        stack, _, dd = images._stage()
+        assert np.array_equal(images.items(idx).numpy(), ds_mod.batch_host(stack.numpy(), idx.numpy(), None, dd, 1.0))
+
+
+def test_projection_monitor_takes_a_strip_dataset():
+    ds = host(make_strips(2, 16, seed=10), model_initial_depth=1)
+    m = pg.ProjectionMonitor(source=ds, num_images=4)
+    t = m.targets(8)
+    assert t.dtype == torch.float32 and tuple(t.shape) == (4, 2, 8, 8)
+    assert torch.equal(t, torch.stack([ds[i] for i in (2, 3, 4, 5)])) and ds.cursor == 0
+    with pytest.raises(ValueError, match='7 targets'):
+        pg.ProjectionMonitor(source=ds, num_images=7)
 
 
 def test_close():

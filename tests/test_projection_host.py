@@ -250,8 +250,8 @@ def test_monitor_takes_the_tail_of_a_dataset(monkeypatch):
         def __len__(self):
             return 10
 
-        def _make(self, idx, flip, alpha):
-            assert flip is None and alpha == 1.0
+        def items(self, idx, alpha=1.0):
+            assert alpha == 1.0
             return idx.float().view(-1, 1, 1, 1).expand(-1, 3, 4, 4).contiguous()
     with pytest.raises(ValueError, match='11 targets'):
         pg.ProjectionMonitor(Dataset(), num_images=11)

@@ -62,7 +62,7 @@ def main():
             ds.model_depth = depth
             r = 4 * 2 ** depth
             n = MINIBATCH_OVERRIDES.get(depth, MINIBATCH_DEFAULT)
-            stack, dd = ds._stage()
+            stack, _, dd = ds._stage()
             for mirror in (False, True):
                 idx, flip = ds.draw_indices(n)
                 idx, flip = idx.clone(), (flip.clone() if mirror else None)
