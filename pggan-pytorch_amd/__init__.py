@@ -15,6 +15,7 @@ from .optim import FusedAdam  # noqa: F401
 from .ema import GeneratorEMA  # noqa: F401
 from .parallel import DataParallel  # noqa: F401
 from .sound import SoundSaver, DeviceSoundSaver, spectrogram_u8, spectrogram_stack_u8, spectrogram_strip_u8  # noqa: F401
+from .sound import ResampleTable, resample_table, resample, resampled_length, load_wav  # noqa: F401
 from .phase import MelTable, mel_table, mel_analyse, mel_spectrum, mel_synthesise  # noqa: F401
 from .dataset import DeviceImageDataset, DeviceStripDataset, CropStream  # noqa: F401
 from .metrics import NearestNeighbours, NDB, ChannelSlicedWasserstein  # noqa: F401
@@ -29,4 +30,5 @@ __all__ = ['Generator', 'Discriminator', 'PGConv2d', 'wgan_gp_D_loss', 'wgan_gp_
            'load_smoothed_generator', 'load_trainer_state', 'FusedAdam', 'GeneratorEMA', 'DataParallel', 'SoundSaver', 'DeviceSoundSaver',
            'spectrogram_u8', 'spectrogram_stack_u8', 'DeviceImageDataset', 'NearestNeighbours', 'NDB', 'NDBMonitor', 'LossMonitor', 'HealthMonitor', 'ScalarStats', 'SegmentStats',
            'TrainingDiverged', 'Sampler', 'sampler_for', 'Projector', 'ProjectionMonitor', 'project_samples', 'DeviceStripDataset', 'CropStream', 'spectrogram_strip_u8',
-           'ChannelSlicedWasserstein', 'MelTable', 'mel_table', 'mel_analyse', 'mel_spectrum', 'mel_synthesise']
+           'ChannelSlicedWasserstein', 'MelTable', 'mel_table', 'mel_analyse', 'mel_spectrum', 'mel_synthesise',
+           'ResampleTable', 'resample_table', 'resample', 'resampled_length', 'load_wav']

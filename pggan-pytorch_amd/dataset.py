@@ -520,21 +520,53 @@ class DeviceStripDataset(_DeviceDataset):
 
     # --------------------------------------------------------------------------------------------- construction
     @classmethod
-    def from_waveforms(cls, signals, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None, sample_rate=None, mel_rows=None, **kw):
+    def from_waveforms(cls, signals, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None, sample_rate=None, mel_rows=None,
+                       rates=None, frequency=None, **kw):
         """The dataset of a list of waveforms of different lengths (``[nsamp]`` or ``[nsamp, channels]``, numpy arrays or tensors):
         one strip per recording from ``sound.spectrogram_strip_u8``.  A waveform that gives fewer usable frames than the strip is
         high -- n_fft/2, or ``mel_rows`` for img_mode='melif', whose ``sample_rate`` and ``mel_rows`` are passed through -- is a
-        ValueError naming it."""
+        ValueError naming it.
+
+        ``rates`` and ``frequency`` (both or neither): the recordings' sample rates in Hz, one integer for all or one per waveform,
+        and the rate every one of them is brought to by ``sound.resample`` before its analysis (SoundImageDataset's ``frequency``);
+        the usable frames are those of the ``sound.resampled_length``."""
         from . import sound
+        signals = list(signals)
+        if (rates is None) != (frequency is None):
+            raise ValueError('rates and frequency belong together: got rates %r and frequency %r' % (rates, frequency))
+        if rates is None:
+            rates = [None] * len(signals)                                       # (rate_in=None, frequency=None: no conversion)
+        elif isinstance(rates, (int, np.integer)) and not isinstance(rates, bool):
+            rates = [rates] * len(signals)
+        try:
+            rates = list(rates)
+        except TypeError:
+            raise ValueError('rates must be an integer or one per waveform, got %r' % (rates,))
+        if len(rates) != len(signals):
+            raise ValueError('rates: %d values for %d waveforms' % (len(rates), len(signals)))
+        for rate in rates:                                                       # (positive integers; 'melif': sample_rate is the frequency)
+            _, sample_rate = sound._resample_arguments(rate, frequency, img_mode, sample_rate)
         table = sound._mel_arguments(img_mode, n_fft, sample_rate, mel_rows)    # (refuses sample_rate / mel_rows with another mode first)
         side = int(n_fft) // 2 if table is None else table.rows
         strips = []
-        for m, y in enumerate(signals):
-            if sound.strip_frames(int(y.shape[0]), hop_length, img_mode) < side:
-                raise ValueError('waveform %d: %d samples give %d usable frames, a window needs %d'
-                                 % (m, y.shape[0], sound.strip_frames(int(y.shape[0]), hop_length, img_mode), side))
-            strips.append(sound.spectrogram_strip_u8(y, n_fft, hop_length, img_mode, mag_range, sample_rate, mel_rows))
+        for m, (y, rate) in enumerate(zip(signals, rates)):
+            nsamp = int(y.shape[0]) if rate is None else sound.resampled_length(int(y.shape[0]), rate, frequency)
+            if sound.strip_frames(nsamp, hop_length, img_mode) < side:
+                converted = '' if rate is None else ' at %d Hz are %d samples at %d Hz and' % (rate, nsamp, frequency)
+                raise ValueError('waveform %d: %d samples%s give %d usable frames, a window needs %d'
+                                 % (m, y.shape[0], converted, sound.strip_frames(nsamp, hop_length, img_mode), side))
+            strips.append(sound.spectrogram_strip_u8(y, n_fft, hop_length, img_mode, mag_range, sample_rate, mel_rows,
+                                                     rate_in=rate, frequency=frequency))
         return cls(strips, **kw)
+
+    @classmethod
+    def from_wav_files(cls, paths, frequency=16000, **from_waveforms_kw):
+        """The dataset of a list of WAV files of any sample rates: ``sound.load_wav`` per file (int16 samples go to the device as they
+        are), then ``from_waveforms(rates=[the files' rates], frequency=frequency, **from_waveforms_kw)``.  A file that cannot be read
+        is a ValueError naming it."""
+        from . import sound
+        loaded = [sound.load_wav(path) for path in paths]
+        return cls.from_waveforms([y for _, y in loaded], rates=[rate for rate, _ in loaded], frequency=frequency, **from_waveforms_kw)
 
     def _upload(self, strips):
         """Host mode: a list of numpy arrays [C,R,T].  Device: a ``StripLevel``, filled ``UPLOAD_CHUNK_BYTES`` of columns at a time."""

@@ -21,14 +21,219 @@ its published definitions (periodic Hann window, center=True with reflect paddin
 overlap-add with the 2/3 gain that makes hop = n_fft/4 an exact inverse).  Parity is therefore UNPINNED for these two
 steps (no librosa, no reference vectors); ``oracle/sound_steps.py`` restates the same definitions independently and the
 tests hold the two against each other plus the algebraic properties (inverse round trip, Griffin-Lim consistency)."""
+import functools
+import math
 import os
 
 import numpy as np
 
+from . import _lib
 from .utils import adjust_dynamic_range
 
 
 MEL_SAMPLE_RATE = 16000               # the default ``sample_rate`` of img_mode='melif' (SoundSaver's default too)
+
+# ------------------------------------------------------------------ rate conversion (include/pggan_hip_resample.h, csrc/resample.hip)
+_RC = _lib.RESAMPLE_CONSTANTS
+RESAMPLE_MAX_PHASES, RESAMPLE_MAX_TAPS = _RC['PG_RESAMPLE_MAX_PHASES'], _RC['PG_RESAMPLE_MAX_TAPS']
+RESAMPLE_ZEROS, RESAMPLE_ROLLOFF, RESAMPLE_BETA = 64, 0.9475937167399596, 14.769656459379492     # resampy's published 'kaiser_best'
+
+
+def _ratio(rate_in, rate_out):
+    """(L, M) = (rate_out, rate_in) / gcd; the rates are positive integers (ValueError otherwise)."""
+    for name, v in (('rate_in', rate_in), ('rate_out', rate_out)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError('%s must be a positive integer (Hz), got %r' % (name, v))
+    g = math.gcd(int(rate_in), int(rate_out))
+    return int(rate_out) // g, int(rate_in) // g
+
+
+class ResampleTable(object):
+    """The polyphase filter of ``resample`` as plain data (include/pggan_hip_resample.h): ``taps`` float64 ``[L, T]``, row r the T
+    taps of phase r, T even; output n = (q L + r) / M weighs the samples q - T/2 + 1 .. q + T/2 with them.  The kernel and the numpy
+    twin take ANY finite table of this shape (``resample_table`` builds the windowed sinc).  A malformed table is a ValueError here,
+    once.  The array lives on the host (read-only numpy) and is uploaded to a device at first use there (``on``)."""
+
+    def __init__(self, L, M, taps):
+        for name, v in (('L', L), ('M', M)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError('ResampleTable: %s must be a positive integer, got %r' % (name, v))
+        try:
+            taps = np.array(taps, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('ResampleTable: taps must be an array of numbers [L, T]')
+        if taps.ndim != 2 or taps.shape[0] != L or taps.shape[1] < 2 or taps.shape[1] % 2:
+            raise ValueError('ResampleTable: taps must be [L = %d, T] with T even and >= 2, got shape %s' % (L, tuple(taps.shape)))
+        if L > RESAMPLE_MAX_PHASES or taps.shape[1] > RESAMPLE_MAX_TAPS:
+            raise ValueError('ResampleTable: %d phases of %d taps, at most %d and %d are supported (rates with a larger common divisor '
+                             'give fewer phases)' % (L, taps.shape[1], RESAMPLE_MAX_PHASES, RESAMPLE_MAX_TAPS))
+        if not np.isfinite(taps).all():
+            raise ValueError('ResampleTable: taps must be finite')
+        self.L, self.M, self.T = int(L), int(M), int(taps.shape[1])
+        self.taps = np.ascontiguousarray(taps)
+        self.taps.setflags(write=False)
+        self._on = {}
+
+    def on(self, device):
+        """``taps`` on ``device`` (uploaded once per device; a host-to-device copy from pageable memory, so call it once outside a
+        graph capture that contains ``resample``)."""
+        import torch
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if device not in self._on:
+            self._on[device] = torch.from_numpy(np.array(self.taps)).to(device)
+        return self._on[device]
+
+
+@functools.lru_cache(maxsize=None)
+def _resample_table(L, M, zeros, rolloff, beta):
+    c = rolloff * min(1.0, L / M)
+    W = zeros / c
+    half = int(math.ceil(W))
+    j = np.arange(2 * half, dtype=np.int64)
+    r = np.arange(L, dtype=np.int64)[:, None]
+    tau = (r + L * (half - 1 - j)) / L                                        # exact integers, one division
+    u = tau / W
+    with np.errstate(invalid='ignore'):                                      # (sqrt of a negative number where |u| >= 1: selected away)
+        window = np.where(np.abs(u) < 1, np.i0(beta * np.sqrt(1 - u * u)) / np.i0(beta), 0.0)
+    return ResampleTable(L, M, c * np.sinc(c * tau) * window)
+
+
+def resample_table(rate_in, rate_out, zeros=RESAMPLE_ZEROS, rolloff=RESAMPLE_ROLLOFF, beta=RESAMPLE_BETA):
+    """The ``ResampleTable`` from ``rate_in`` to ``rate_out`` Hz (positive integers), a Kaiser-windowed sinc:
+    with g = gcd, L = rate_out/g, M = rate_in/g, c = rolloff min(1, L/M), W = zeros/c, half = ceil(W), T = 2 half,
+    tau = (r + L (half - 1 - j)) / L:  taps[r][j] = c sinc(c tau) i0(beta sqrt(1 - (tau/W)^2)) / i0(beta), 0 where |tau| >= W.
+    The defaults are resampy's published 'kaiser_best'.  More than 4096 phases or taps (44100 -> 16001: L = 16001) are a ValueError.
+    Built once per set of arguments and kept."""
+    L, M = _ratio(rate_in, rate_out)
+    try:
+        zeros, rolloff, beta = float(zeros), float(rolloff), float(beta)
+    except (TypeError, ValueError):
+        zeros = rolloff = beta = float('nan')
+    if not (math.isfinite(zeros) and math.isfinite(rolloff) and math.isfinite(beta) and zeros > 0 and 0 < rolloff <= 1 and beta >= 0):
+        raise ValueError('resample_table: zeros > 0, 0 < rolloff <= 1 and beta >= 0 must be finite numbers')
+    half = int(math.ceil(zeros / (rolloff * min(1.0, L / M))))
+    if L > RESAMPLE_MAX_PHASES or 2 * half > RESAMPLE_MAX_TAPS:
+        raise ValueError('resample_table: %r -> %r Hz needs %d phases of %d taps, at most %d and %d are supported'
+                         % (rate_in, rate_out, L, 2 * half, RESAMPLE_MAX_PHASES, RESAMPLE_MAX_TAPS))
+    return _resample_table(L, M, zeros, rolloff, beta)
+
+
+def resampled_length(nsamp, rate_in, rate_out):
+    """Samples of ``resample`` for ``nsamp`` input samples: ceil(nsamp L / M)."""
+    L, M = _ratio(rate_in, rate_out)
+    return -(-int(nsamp) * L // M)
+
+
+def _mix_host(x):
+    """numpy ``[nsamp]`` or ``[nsamp, channels]`` -> float32 mono, the bits of the kernels: int16 as v / 32768 (exact), then for more
+    than one channel the float32 sum in channel order divided by 2 (dataset.py:287-288)."""
+    x = x.astype(np.float32) / np.float32(32768) if x.dtype == np.int16 else x.astype(np.float32, copy=False)
+    if x.ndim == 1 or x.shape[1] == 1:
+        return np.ascontiguousarray(x.reshape(-1))
+    acc = np.zeros(x.shape[0], dtype=np.float32)
+    for c in range(x.shape[1]):
+        acc = acc + x[:, c]
+    return acc / np.float32(2)
+
+
+def _resample_host(m, table, n_out):
+    """The numpy twin of csrc/resample.hip on the float32 mono signal ``m``: vectorised over the outputs, a loop over the taps in
+    ascending order, fp64 product then fp64 sum (numpy does not fuse), over a zero-padded fp64 copy -- adding the +-0.0 of a term
+    outside the signal leaves every bit of the sum as skipping it does (the sum starts at +0.0 and the taps are finite)."""
+    L, M, T = table.L, table.M, table.T
+    half = T // 2
+    p = np.arange(n_out, dtype=np.int64) * M
+    q, r = p // L, p % L
+    xp = np.zeros(m.shape[0] + T, dtype=np.float64)
+    xp[half:half + m.shape[0]] = m
+    acc = np.zeros(n_out, dtype=np.float64)
+    for j in range(T):
+        acc = acc + table.taps[r, j] * xp[q + 1 + j]
+    return acc.astype(np.float32)
+
+
+def resample(signal, rate_in, rate_out, table=None, device='cuda'):
+    """Waveform (numpy array or tensor, ``[nsamp]`` or ``[nsamp, channels]``) at ``rate_in`` Hz -> the float32 MONO waveform
+    ``[ceil(nsamp L / M)]`` at ``rate_out`` Hz on the device, one launch (pg_resample_mono): mix-down as in ``spectrogram_u8``, then
+    out[n] = sum_j taps[r][j] m[q - T/2 + 1 + j] with (q, r) = divmod(n M, L), fp64 in ascending j over the samples that exist, one
+    rounding.  int16 samples go to the kernel as they are (v / 32768); every other dtype is converted to float32 on the host.
+    ``table``: a ``ResampleTable`` for this L and M (default ``resample_table(rate_in, rate_out)``).  ``device='cpu'``: the numpy twin,
+    a numpy array with the same bits.  Equal rates launch nothing and return the mix-down."""
+    L, M = _ratio(rate_in, rate_out)
+    if table is None:
+        table = resample_table(rate_in, rate_out) if L != M else None
+    elif not isinstance(table, ResampleTable) or (table.L, table.M) != (L, M):
+        raise ValueError('resample: table must be a ResampleTable with L = %d and M = %d, got %r'
+                         % (L, M, (table.L, table.M) if isinstance(table, ResampleTable) else type(table).__name__))
+    is_tensor = not isinstance(signal, np.ndarray) and hasattr(signal, 'data_ptr')
+    if not is_tensor:
+        signal = np.asarray(signal)
+    if signal.ndim not in (1, 2) or signal.shape[0] < 1 or (signal.ndim == 2 and signal.shape[1] < 1):
+        raise ValueError('expected a waveform [nsamp] or [nsamp, channels], got shape %s' % (tuple(signal.shape),))
+    nsamp, channels = int(signal.shape[0]), int(signal.shape[1]) if signal.ndim == 2 else 1
+    n_out = -(-nsamp * L // M)
+    if str(device) == 'cpu':
+        m = _mix_host(signal.cpu().numpy() if is_tensor else signal)
+        return m if L == M else _resample_host(m, table, n_out)
+    import torch
+    from . import ops
+    if is_tensor:
+        t = signal
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(signal, dtype=np.int16 if signal.dtype == np.int16 else np.float32))
+    if t.dtype != torch.int16:
+        t = t.to(dtype=torch.float32)
+    t = t.to(device=device).contiguous()
+    if L == M:                                                                # the mix-down of spectrogram_u8, no launch of ours
+        t = t.to(dtype=torch.float32) / 32768 if t.dtype == torch.int16 else t
+        return (t.sum(dim=1) / 2 if channels > 1 else t.reshape(-1)).contiguous()
+    ops.require_gpu()
+    if t.data_ptr() % 16:
+        t = t.clone()                                                         # (a slice of a larger tensor: 16-byte aligned bases)
+    fmt = _RC['PG_RESAMPLE_I16'] if t.dtype == torch.int16 else _RC['PG_RESAMPLE_F32']
+    taps = table.on(t.device)
+    out = torch.empty(n_out, device=t.device, dtype=torch.float32)
+    with torch.cuda.device(t.device):
+        _lib.call('pg_resample_mono', t.data_ptr(), fmt, nsamp, channels, taps.data_ptr(), L, M, table.T, out.data_ptr(), n_out,
+                  ops._stream())
+    return out
+
+
+def load_wav(path):
+    """``(rate, samples)`` of a WAV file through scipy.io.wavfile.read: ``samples`` is ``[nsamp]`` or ``[nsamp, channels]``, int16 and
+    float32 as stored, int32 as float32 v / 2^31, uint8 as float32 (v - 128) / 128.  A file that cannot be read or holds another sample
+    type is a ValueError naming it."""
+    from scipy.io import wavfile
+    try:
+        rate, data = wavfile.read(path)
+    except Exception as e:
+        raise ValueError('%s: cannot be read as a WAV file (%s)' % (path, e))
+    data = np.asarray(data)
+    if data.dtype in (np.int16, np.float32):
+        return int(rate), data
+    if data.dtype == np.int32:
+        return int(rate), (data / 2147483648.0).astype(np.float32)
+    if data.dtype == np.uint8:
+        return int(rate), ((data.astype(np.float32) - 128) / 128).astype(np.float32)
+    raise ValueError('%s: samples of type %s (int16, float32, int32 and uint8 are supported)' % (path, data.dtype))
+
+
+def _resample_arguments(rate_in, frequency, img_mode, sample_rate):
+    """``(convert, sample_rate)`` of the sound ends' ``rate_in`` / ``frequency`` (the reference's name for the target rate,
+    dataset.py:273): both or neither; ``convert`` when they differ; with img_mode='melif' ``sample_rate`` defaults to ``frequency``."""
+    if (rate_in is None) != (frequency is None):
+        raise ValueError('rate_in and frequency belong together: got rate_in %r and frequency %r' % (rate_in, frequency))
+    if frequency is None:
+        return False, sample_rate
+    L, M = _ratio(rate_in, frequency)
+    if img_mode == 'melif':
+        if sample_rate is None:
+            sample_rate = int(frequency)
+        elif sample_rate != frequency:
+            raise ValueError("img_mode='melif': sample_rate %r is not the frequency %r the waveform is resampled to" % (sample_rate, frequency))
+    return L != M, sample_rate
 
 
 def _mel_arguments(img_mode, n_fft, sample_rate, mel_rows):
@@ -45,7 +250,7 @@ def _mel_arguments(img_mode, n_fft, sample_rate, mel_rows):
 
 
 def spectrogram_u8(signal, n_fft=1024, hop_length=128, img_mode='abslog', range_in=(0, 255), mag_range=None, sample_rate=None,
-                   mel_rows=None):
+                   mel_rows=None, rate_in=None, frequency=None):
     """Waveform (numpy array or tensor, ``[nsamp]`` or ``[nsamp, channels]``) -> uint8 device image: ``[1, n_fft/2, n_fft/2]``
     for the spectrogram modes 'abslog' (log(1 + |s|), dataset.py:296) and 'reallog' (log(1 + |Re s|) * sign(s), dataset.py:298,
     with numpy 1.13's complex sign = the sign of the real part), ``[1, 2^k, 2^k]`` for 'raw' (the waveform itself, dataset.py:289-291).
@@ -55,16 +260,23 @@ def spectrogram_u8(signal, n_fft=1024, hop_length=128, img_mode='abslog', range_
     (default (0, log1p(n_fft/2))) and the instantaneous frequency on a circle of 256 levels; ``range_in`` is not used.
 
     'melif' (this project's own): ``[2, M, M]`` with M = ``mel_rows`` (a power of two, 4 <= M <= n_fft/2, default
-    n_fft/2) mel-spaced rows made from the n_fft/2 bins at ``sample_rate`` Hz (default 16000), the first M frames; otherwise as 'magif'."""
+    n_fft/2) mel-spaced rows made from the n_fft/2 bins at ``sample_rate`` Hz (default 16000), the first M frames; otherwise as 'magif'.
+
+    ``rate_in`` and ``frequency`` (both or neither; SoundImageDataset's ``frequency``, dataset.py:273): the waveform is a recording at
+    ``rate_in`` Hz and is brought to ``frequency`` Hz by ``resample`` first; the rest runs on its mono result.  With 'melif'
+    ``sample_rate`` then defaults to ``frequency``, and another value is a ValueError."""
     import torch
     from . import ops
     if img_mode not in ('abslog', 'reallog', 'raw', 'magif', 'melif'):
         raise ValueError("img_mode must be one of 'abslog', 'reallog', 'raw', 'magif', 'melif' (got %r)" % (img_mode,))
     if img_mode not in ('magif', 'melif') and mag_range is not None:
         raise ValueError("mag_range belongs to img_mode='magif' and 'melif' (got img_mode %r)" % (img_mode,))
+    convert, sample_rate = _resample_arguments(rate_in, frequency, img_mode, sample_rate)
     _mel_arguments(img_mode, n_fft, sample_rate, mel_rows)
     if range_in[0] != 0:
         raise NotImplementedError('range_in must start at 0 (uint8 images)')
+    if convert:
+        signal = resample(signal, rate_in, frequency)
     t = signal if torch.is_tensor(signal) else torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32))
     if img_mode in ('magif', 'melif'):
         if t.dim() not in (1, 2) or t.shape[0] < 1:
@@ -77,18 +289,24 @@ def spectrogram_u8(signal, n_fft=1024, hop_length=128, img_mode='abslog', range_
     return ops.spectrogram_u8(t, int(n_fft), int(hop_length), float(range_in[1]), img_mode=img_mode)
 
 
-def spectrogram_stack_u8(signals, n_fft=1024, hop_length=128, mag_range=None, img_mode='magif', sample_rate=None, mel_rows=None):
+def spectrogram_stack_u8(signals, n_fft=1024, hop_length=128, mag_range=None, img_mode='magif', sample_rate=None, mel_rows=None,
+                         rate_in=None, frequency=None):
     """Mono waveforms ``[batch, nsamp]`` (numpy array or tensor) -> uint8 device images ``[batch, 2, n_fft/2, n_fft/2]`` of
     ``img_mode='magif'``, for filling a ``DeviceImageDataset`` stack: the analysis of the whole batch and the quantiser, no host
     synchronisation (phase.spectrogram_stack_u8).  ``img_mode='melif'``: ``[batch, 2, M, M]``, M = ``mel_rows`` mel-spaced rows at
-    ``sample_rate`` Hz as in ``spectrogram_u8`` (phase.mel_spectrogram_stack_u8), the same two launches."""
+    ``sample_rate`` Hz as in ``spectrogram_u8`` (phase.mel_spectrogram_stack_u8), the same two launches.  ``rate_in`` / ``frequency`` as
+    in ``spectrogram_u8``: every row goes through ``resample`` first, one launch per row."""
     import torch
     from . import phase
     if img_mode not in ('magif', 'melif'):
         raise ValueError("img_mode must be 'magif' or 'melif' (got %r)" % (img_mode,))
+    convert, sample_rate = _resample_arguments(rate_in, frequency, img_mode, sample_rate)
     t = signals if torch.is_tensor(signals) else torch.from_numpy(np.ascontiguousarray(signals, dtype=np.float32))
     if t.dim() != 2 or t.shape[0] < 1:
         raise ValueError('signals: expected [batch, nsamp], got shape %s' % (tuple(t.shape),))
+    if convert:
+        _mel_arguments(img_mode, n_fft, sample_rate, mel_rows)               # (the argument errors before the launches)
+        t = torch.stack([resample(row, rate_in, frequency) for row in t])
     if isinstance(n_fft, bool) or int(n_fft) != n_fft or isinstance(hop_length, bool) or int(hop_length) != hop_length:
         raise ValueError('n_fft and hop_length must be integers, got %r and %r' % (n_fft, hop_length))
     table = _mel_arguments(img_mode, n_fft, sample_rate, mel_rows)
@@ -107,7 +325,8 @@ def strip_frames(nsamp, hop_length, img_mode='magif'):
     return int(nsamp) // int(hop_length)
 
 
-def spectrogram_strip_u8(signal, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None, sample_rate=None, mel_rows=None):
+def spectrogram_strip_u8(signal, n_fft=1024, hop_length=128, img_mode='magif', mag_range=None, sample_rate=None, mel_rows=None,
+                         rate_in=None, frequency=None):
     """Waveform (numpy array or tensor, ``[nsamp]`` or ``[nsamp, channels]``, mixed down as in ``spectrogram_u8``) -> the uint8 device
     STRIP ``[C, n_fft/2, T]`` over ALL frames of the recording, T = nsamp // hop_length, for ``dataset.DeviceStripDataset``:
     ``phase.analyse(bins=n_fft/2, frames=all)`` and ``phase.magif_u8`` with column 0 dropped -- the first column of the second
@@ -121,9 +340,17 @@ def spectrogram_strip_u8(signal, n_fft=1024, hop_length=128, img_mode='magif', m
     'melif'   ``[2, M, T]``: both channels on M = ``mel_rows`` mel-spaced rows at ``sample_rate`` Hz, as in ``spectrogram_u8``
               (``phase.mel_analyse``: the planes of the n_fft/2 linear bins are never written).
 
+    ``rate_in`` / ``frequency`` as in ``spectrogram_u8``: the recording goes through ``resample`` first and T counts the frames of
+    its ``resampled_length``.
+
     The analysis holds two float64 planes [n_fft/2, T + 1] on the device while it runs (16 n_fft/2 bytes per frame)."""
     import torch
     from . import phase
+    convert, sample_rate = _resample_arguments(rate_in, frequency, img_mode, sample_rate)
+    if convert:
+        strip_frames(0, hop_length, img_mode)                                 # (the argument errors before the launch)
+        _mel_arguments(img_mode, n_fft, sample_rate, mel_rows)
+        signal = resample(signal, rate_in, frequency)
     t = signal if torch.is_tensor(signal) else torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32))
     if t.dim() not in (1, 2) or t.shape[0] < 1:
         raise ValueError('expected a waveform [nsamp] or [nsamp, channels], got shape %s' % (tuple(t.shape),))
