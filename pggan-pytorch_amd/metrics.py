@@ -30,6 +30,9 @@ values are comparable within a growth stage and between runs of this project.
 image -- the paper's answer to "is that a new image or a copy of a training image?", which neither metric above can give (a generator
 that memorises keeps a fine SWD, and MS-SSIM only sees collapse between samples).  Integer arithmetic: exact, the same from run to run.
 
+``ShiftNearestNeighbours``: the same question for strip data sets, whose training images are windows at EVERY start column of long recordings:
+the nearest window over all starts, segment by segment, without the per-start distances ever existing in memory.  Integer arithmetic as well.
+
 ``NDB``: the number of statistically different bins and the Jensen-Shannon divergence over k-means bins of the training images (Richardson &
 Weiss 2018) -- does the generator cover the modes of the training set in the data's proportions, which none of the three above says.  Integer
 k-means on the device-resident stack: exact and reproducible; UNPINNED like the SWD and MS-SSIM."""
@@ -360,6 +363,169 @@ class NearestNeighbours(object):
             from .dataset import batch_host
             out = torch.from_numpy(batch_host(stack.numpy(), idx.numpy(), flip.numpy(), 0, 1.0, (0, 255), self.drange))
         return out.view(tuple(result['index'].shape) + tuple(stack.shape[1:]))
+
+
+# ------------------------------------------------------------------------- nearest windows at every start column of strips
+def _shift_keys_host(strips, queries, seg):
+    """``ops.shift_l2min_u8`` in numpy int64: ``strips`` a list of uint8 arrays [C,S,T_m], ``queries`` uint8 [K,C,S,S] -> keys [K,G].
+    The distances of one strip at all starts are accumulated column by column of the query (never as materialised windows)."""
+    K, C, S, _ = queries.shape
+    q = queries.astype(np.int64)
+    keys = []
+    for s in strips:
+        n = s.shape[2] - S + 1
+        x = np.asarray(s).astype(np.int64)
+        d = np.zeros((K, n), dtype=np.int64)
+        for j in range(S):
+            diff = x[None, :, :, j:j + n] - q[:, :, :, j, None]              # [K,C,S,n]: column j of every query against columns j + u
+            d += (diff * diff).sum(axis=(1, 2))
+        for g0 in range(0, n, seg):
+            part = (d[:, g0:g0 + seg] << ops.SHIFT_POS_BITS) + np.arange(min(seg, n - g0), dtype=np.int64)[None]
+            keys.append(part.min(axis=1))
+    return np.stack(keys, axis=1)
+
+
+def _topk_host(keys, k):
+    """``ops.topk_smallest_i64`` in numpy: (values [K,k], indices [K,k]), ascending by (value, index)."""
+    order = np.stack([np.lexsort((np.arange(row.size), row))[:k] for row in keys])
+    return np.take_along_axis(keys, order, axis=1), order.astype(np.int64)
+
+
+class ShiftNearestNeighbours(object):
+    """``search(samples)``: the ``k`` nearest training WINDOWS of every generated sample over every start column of the recordings --
+    what ``NearestNeighbours`` on ``level_stack()`` cannot see, because that stack holds only the windows whose start is a multiple
+    of the window width.
+
+    ``source``: a ``DeviceStripDataset`` (its ``range_in`` must be (0, 255)) or a ``dataset.StripLevel``.  With a data set the search
+    follows the growth stage (``_stage()``): for ``pyramid='chain'`` the stage's stored level is searched with windows S = R >> shift
+    at every STORED column, so a reported start is ``u << shift`` full-resolution columns; for ``'direct'`` below the source resolution
+    a level is made per strip with ``ops.pyramid_level_u8(strip, dd)``, once per stage and kept until the stage moves, which gives
+    the translations that are multiples of 2^dd full-resolution columns (the training crops of 'direct' start at every column: the
+    others are not searched).
+
+    The samples (fp32 [K,C,S,S] in ``drange``) are rounded to the 0..255 levels (``ops.quantize_u8``) and compared byte for byte:
+    ``sqdist = sum (x - q)^2`` exact.  The starts of every strip are cut into segments of ``seg`` starts (default S;
+    ``ops.shift_segments``); ``ops.shift_l2min_u8`` gives the nearest start of every segment and ``ops.topk_smallest_i64`` the ``k``
+    nearest SEGMENTS, ascending by (sqdist, start within the segment, segment).  One neighbour per segment: two adjacent segments may
+    report nearly the same place (starts seg - 1 and seg are one column apart); that is accepted, not suppressed.  The distances of
+    the individual starts never exist in memory.  ``mirror``: the queries are doubled with their time-reversed copies and the two
+    lists of a sample merged on the host by (sqdist, segment, start, mirrored).  1 <= k <= min(G, ops.NN_MAX_TOPK).
+
+    ``device``: None = where the source is; 'cpu' = the numpy twin in int64 (the same definition, no device)."""
+
+    def __init__(self, source, k=1, mirror=False, drange=(-1, 1), seg=None, device=None):
+        from .dataset import StripLevel
+        if isinstance(source, StripLevel):
+            src_device, S, cols = source.buffer.device, source.S, source.cols
+        elif hasattr(source, '_stage') and hasattr(source, 'lengths'):
+            if tuple(source.range_in) != (0, 255):
+                raise ValueError('source: the data set holds range_in = %r; the search compares 0..255 levels' % (tuple(source.range_in),))
+            src_device, S, cols = source.device, source.shape[2], source.lengths
+        else:
+            raise ValueError('source: expected a DeviceStripDataset or a StripLevel, got %s' % type(source))
+        if seg is not None:
+            ops._shift_seg(S, seg)
+        G = len(ops.shift_segments(cols, S, seg)[0])                     # (the same at every stage when seg is None: T and S shrink together)
+        if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(G, ops.NN_MAX_TOPK):
+            raise ValueError('k = %r for %d segments (1 <= k <= min(G, %d))' % (k, G, ops.NN_MAX_TOPK))
+        if not float(drange[1]) > float(drange[0]):
+            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
+        self.source, self.k, self.mirror, self.seg = source, int(k), bool(mirror), None if seg is None else int(seg)
+        self.drange = (float(drange[0]), float(drange[1]))
+        self.device = torch.device(src_device if device is None else device)
+        self._made = (None, None)                                        # ('direct' below the source: (stage key, the level made for it))
+
+    # ------------------------------------------------------------------------------------------------- the level
+    def level(self):
+        """(the level a search made now would read, log2 of the full-resolution columns per column of it): a ``StripLevel`` on the
+        device, a list of uint8 numpy arrays [C,S,T] in host mode."""
+        from .dataset import StripLevel, level_host
+        if isinstance(self.source, StripLevel):
+            level, shift, dd = self.source, 0, 0
+        else:
+            level, shift, dd = self.source._stage()
+        host = self.device.type != 'cuda'
+        if dd == 0 and host == (not isinstance(level, StripLevel)):
+            return level, shift
+        key = (id(level), dd, host)
+        if self._made[0] != key:
+            self._made = (None, None)                                    # (drop the last stage's before making this one's)
+            M = len(level.cols) if isinstance(level, StripLevel) else len(level)
+            strips = [level.strip(m) if isinstance(level, StripLevel) else level[m] for m in range(M)]
+            if host:
+                strips = [s.cpu().numpy() if torch.is_tensor(s) else s for s in strips]
+                made = [level_host(s, dd, self.source.range_in) for s in strips] if dd else strips
+            else:
+                made = StripLevel.pack([ops.pyramid_level_u8(s if torch.is_tensor(s) else torch.from_numpy(s).to(self.device), dd,
+                                                             self.source.range_in) for s in strips], self.device)
+            self._made = (key, made)
+        return self._made[1], shift + dd
+
+    @staticmethod
+    def _dims(level):
+        """(C, S, columns per strip) of a device or host level."""
+        if isinstance(level, list):
+            return level[0].shape[0], level[0].shape[1], [s.shape[2] for s in level]
+        return level.C, level.S, level.cols
+
+    def _seg(self, S):
+        return ops._shift_seg(S, self.seg)[1]
+
+    # ------------------------------------------------------------------------------------------------ the search
+    def search(self, samples):
+        """{'strip': int64 [K,k], 'start': int64 [K,k] (full-resolution start column of the window), 'sqdist': int64 [K,k],
+        'rms': float64 [K,k] = sqrt(sqdist / D) in 0..255 levels (fp64, host), 'mirrored': bool [K,k] (the window matches the sample
+        reversed in time)} as host tensors.  One device synchronisation."""
+        level, scale = self.level()
+        C, S, cols = self._dims(level)
+        if not torch.is_tensor(samples) or samples.dtype != torch.float32 or samples.dim() != 4 or samples.shape[0] < 1 \
+                or tuple(samples.shape[1:]) != (C, S, S):
+            raise ValueError('expected float32 samples [K,%d,%d,%d], got %s'
+                             % (C, S, S, tuple(samples.shape) if torch.is_tensor(samples) else type(samples)))
+        seg = self._seg(S)
+        seg_strip, seg_start, _ = ops.shift_segments(cols, S, seg)
+        K, k = samples.shape[0], self.k
+        if k > seg_strip.size:
+            raise ValueError('k = %d for %d segments at this stage' % (k, seg_strip.size))
+        if self.device.type == 'cuda':
+            q = ops.quantize_u8(samples.to(self.device).contiguous(), self.drange)
+            if self.mirror:
+                q = torch.cat([q, q.flip(-1)])
+            val, ix = ops.topk_smallest_i64(ops.shift_l2min_u8(level, q, seg), k)
+            both = torch.stack([val, ix]).cpu().numpy()
+            val, ix = both[0], both[1]
+        else:
+            q = _quantise_host(samples.cpu().numpy(), self.drange)
+            if self.mirror:
+                q = np.concatenate([q, q[..., ::-1]])
+            val, ix = _topk_host(_shift_keys_host(level, q, seg), k)
+        sq, off = val >> ops.SHIFT_POS_BITS, val & (ops.SHIFT_MAX_SEG - 1)
+        mirrored = np.zeros((K, k), dtype=bool)
+        if self.mirror:                                                  # two sorted lists of k per sample -> the k smallest of both
+            sq2, ix2, off2 = (np.concatenate([a[:K], a[K:]], axis=1) for a in (sq, ix, off))
+            mr2 = np.concatenate([np.zeros((K, k), dtype=bool), np.ones((K, k), dtype=bool)], axis=1)
+            order = np.stack([np.lexsort((mr2[i], off2[i], ix2[i], sq2[i]))[:k] for i in range(K)])
+            sq, ix, off, mirrored = (np.take_along_axis(a, order, axis=1) for a in (sq2, ix2, off2, mr2))
+        D = C * S * S
+        start = (seg_start[ix] + off) << scale
+        return {'strip': torch.from_numpy(np.ascontiguousarray(seg_strip[ix])), 'start': torch.from_numpy(np.ascontiguousarray(start)),
+                'sqdist': torch.from_numpy(np.ascontiguousarray(sq)), 'rms': torch.from_numpy(np.sqrt(sq.astype(np.float64) / D)),
+                'mirrored': torch.from_numpy(np.ascontiguousarray(mirrored))}
+
+    def neighbours(self, result):
+        """The windows a ``search`` result names: fp32 [K,k,C,S,S] in ``drange`` on ``device``, reversed in time where the result says
+        so (``ops.crop_batch_u8`` with alpha 1)."""
+        level, scale = self.level()
+        C, S, _ = self._dims(level)
+        idx, pos = result['strip'].reshape(-1).contiguous(), result['start'].reshape(-1).contiguous()
+        flip = result['mirrored'].reshape(-1).to(torch.uint8).contiguous()
+        if self.device.type == 'cuda':
+            out = ops.crop_batch_u8(level, idx.to(self.device), pos.to(self.device), flip.to(self.device), scale, 0, 1.0, (0, 255), self.drange)
+        else:
+            from .dataset import batch_host
+            windows = np.stack([level[m][:, :, (t >> scale):(t >> scale) + S] for m, t in zip(idx.tolist(), pos.tolist())])
+            out = torch.from_numpy(batch_host(windows, np.arange(len(windows)), flip.numpy(), 0, 1.0, (0, 255), self.drange))
+        return out.view(tuple(result['strip'].shape) + (C, S, S))
 
 
 # ------------------------------------------------------------------------------------------------ NDB/k and JSD (k-means bins)

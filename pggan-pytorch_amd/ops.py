@@ -1283,6 +1283,109 @@ def nn_search_u8(stack_u8, queries_u8, k=1):
     return topk_smallest_i64(l2dist_u8(stack_u8, queries_u8), k)
 
 
+# ------------------------------------------------------------------------- nearest windows at every start column (csrc/shift_search.hip)
+SHIFT = {name[len('PG_SHIFT_'):]: value for name, value in _lib.SHIFT_CONSTANTS.items() if name.startswith('PG_SHIFT_')}   # the addition's own table
+SHIFT_POS_BITS, SHIFT_MAX_QUERIES, SHIFT_TILE = SHIFT['POS_BITS'], SHIFT['MAX_QUERIES'], SHIFT['TILE']
+SHIFT_MAX_SEG = 1 << SHIFT_POS_BITS                            # a key holds the start relative to its segment in POS_BITS bits
+SHIFT_MIN_S, SHIFT_MAX_S = 4, 1024
+
+
+def _shift_seg(S, seg):
+    S = int(S)
+    if S < SHIFT_MIN_S or S > SHIFT_MAX_S or S & (S - 1):
+        raise ValueError('windows of %d rows (a power of two in %d .. %d is required)' % (S, SHIFT_MIN_S, SHIFT_MAX_S))
+    if seg is None:
+        seg = S
+    if isinstance(seg, bool) or int(seg) != seg or not 1 <= seg <= SHIFT_MAX_SEG:
+        raise ValueError('seg = %r (1 <= seg <= %d starts per segment)' % (seg, SHIFT_MAX_SEG))
+    return S, int(seg)
+
+
+def shift_segments(cols, S, seg=None):
+    """The segment table of strips with ``cols`` columns searched with S x S windows: the starts 0 .. T_m - S of strip m are cut into
+    segments of ``seg`` consecutive starts (default S), numbered strip-major.  Returns numpy int64 arrays ``(strip [G], first_start
+    [G], first_segment [M + 1])``: the strip and the first start of every segment, and the first segment of every strip
+    (``first_segment[M]`` = G).  Host arithmetic only."""
+    import numpy as np
+    S, seg = _shift_seg(S, seg)
+    cols = [int(c) for c in cols]
+    if not cols:
+        raise ValueError('shift_segments: no strips')
+    strip, start, first = [], [], [0]
+    for m, T in enumerate(cols):
+        if T < S:
+            raise ValueError('strip %d: %d columns, a window needs %d' % (m, T, S))
+        n = -(-(T - S + 1) // seg)
+        strip.append(np.full(n, m, dtype=np.int64))
+        start.append(np.arange(n, dtype=np.int64) * seg)
+        first.append(first[-1] + n)
+    return np.concatenate(strip), np.concatenate(start), np.asarray(first, dtype=np.int64)
+
+
+def _shift_level(level, what):
+    buf, table = level.buffer, level.table
+    if not torch.is_tensor(buf) or not buf.is_cuda or buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.dim() != 1:
+        raise ValueError('%s: level.buffer: expected a contiguous flat uint8 device tensor' % what)
+    if (not torch.is_tensor(table) or table.device != buf.device or table.dtype != torch.int64 or not table.is_contiguous()
+            or table.dim() != 2 or table.shape[0] != len(level.cols) or table.shape[0] < 1 or table.shape[1] != CROP_TABLE_WORDS):
+        raise ValueError('%s: level.table: expected a contiguous int64 tensor [%d,%d] on the device of the buffer'
+                         % (what, len(level.cols), CROP_TABLE_WORDS))
+
+
+def shift_table(level, seg=None):
+    """The int64 device table [M + 1, 2] that ``shift_l2min_u8`` hands to pg_shift_l2min_u8 for a ``dataset.StripLevel`` and a segment
+    length: (first segment, first tile of ``SHIFT_TILE`` starts) of every strip, row M = (G, tiles).  Built on the host from
+    ``level.cols`` and kept on the level: once per (level, seg)."""
+    _shift_level(level, 'shift_table')
+    S, seg = _shift_seg(level.S, seg)
+    cache = level.__dict__.setdefault('_shift_tables', {})
+    if seg not in cache:
+        first = shift_segments(level.cols, S, seg)[2].tolist()
+        tiles = [0]
+        for T in level.cols:
+            tiles.append(tiles[-1] + -(-(T - S + 1) // SHIFT_TILE))
+        cache[seg] = torch.tensor(list(zip(first, tiles)), dtype=torch.int64).to(level.buffer.device)
+    return cache[seg]
+
+
+def shift_l2min_u8(level, queries_u8, seg=None, table=None):
+    """One stored level of uint8 device strips (``dataset.StripLevel``, C channels, S rows) against uint8 device queries [K,C,S,S] ->
+    int64 keys [K,G] (pg_shift_l2min_u8, on the int8 MFMA for S >= 32):
+
+        key[k, g] = min over the starts u of segment g of  (d[k, m, u] << SHIFT_POS_BITS) + (u - first start of g),
+        d[k, m, u] = sum_{c,r,j} (strip_m[c, r, u + j] - q_k[c, r, j])^2          (exact)
+
+    with the segments of ``shift_segments(level.cols, S, seg)``: the minimum by (distance, start) over EVERY start column of the
+    segment, so ``key >> SHIFT_POS_BITS`` is the squared distance and ``key & (SHIFT_MAX_SEG - 1)`` the start within the segment.
+    The per-start distances are never stored: the only result is [K,G].  Every pass reads the level once for up to
+    ``SHIFT_MAX_QUERIES`` queries; more take several passes, each into its own rows.  ``table``: the device table of
+    ``shift_table(level, seg)`` if the caller keeps it.  No host synchronisation."""
+    _shift_level(level, 'shift_l2min_u8')
+    _u8_images(queries_u8, 'shift_l2min_u8 queries')
+    S, seg = _shift_seg(level.S, seg)
+    C, M = int(level.C), len(level.cols)
+    if queries_u8.device != level.buffer.device or tuple(queries_u8.shape[1:]) != (C, S, S):
+        raise ValueError('shift_l2min_u8: queries %s on %s do not match windows [%d,%d,%d] of the level on %s'
+                         % (tuple(queries_u8.shape), queries_u8.device, C, S, S, level.buffer.device))
+    if table is None:
+        table = shift_table(level, seg)
+    elif (not torch.is_tensor(table) or table.device != level.buffer.device or table.dtype != torch.int64 or not table.is_contiguous()
+          or tuple(table.shape) != (M + 1, SHIFT['SEGTAB_WORDS'])):
+        raise ValueError('shift_l2min_u8: table must be the int64 tensor [%d,%d] of shift_table on the device of the level'
+                         % (M + 1, SHIFT['SEGTAB_WORDS']))
+    tiles = sum(-(-(T - S + 1) // SHIFT_TILE) for T in level.cols)
+    G = sum(-(-(T - S + 1) // seg) for T in level.cols)
+    K = queries_u8.shape[0]
+    require_gpu()
+    key = torch.empty((K, G), device=level.buffer.device, dtype=torch.int64)
+    s = _stream()
+    for k0 in range(0, K, SHIFT_MAX_QUERIES):
+        k1 = min(K, k0 + SHIFT_MAX_QUERIES)
+        _lib.call('pg_shift_l2min_u8', level.buffer.data_ptr(), level.table.data_ptr(), M, C, S, queries_u8[k0:k1].data_ptr(), k1 - k0, seg,
+                  table.data_ptr(), tiles, G, key[k0:k1].data_ptr(), s)
+    return key
+
+
 # ------------------------------------------------------------------------- Griffin-Lim on the device (csrc/griffinlim.hip)
 GL_MIN_N, GL_MAX_N = 8, 2048       # n_fft = 2 H: a power of two in this range (image heights 4 .. 1024)
 

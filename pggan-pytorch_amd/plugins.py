@@ -512,6 +512,61 @@ class NNMonitor(Evaluation):
         run_postprocessors(batch, 'nn_%06d' % (self.trainer.cur_nimg // 1000), self.postprocessors)
 
 
+class ShiftNNMonitor(Evaluation):
+    """``NNMonitor`` for strip data sets (``metrics.ShiftNearestNeighbours``): every ``nn_ticks`` ticks and at the end, ``num_samples``
+    generated images are searched for their ``k`` nearest training windows over EVERY start column of the recordings of ``dataset`` (a
+    ``DeviceStripDataset``; the level of the current growth stage is searched), not only the non-overlapping windows ``NNMonitor``
+    sees through ``level_stack()``: a generator that has memorised a passage starting anywhere in a recording reads as a copy.
+    Writes ``stats['nn_shift_rms']``, the mean over the samples of the distance to the nearest window as an RMS difference per byte in
+    levels, and ``stats['nn_shift_rms_min']``, the smallest of them.  ``mirror``: also match time-reversed windows; None takes
+    ``dataset.mirror_augment``.  ``seg``: starts per segment (one neighbour is reported per segment; default the window width).
+    Rank 0 evaluates (replicas are identical; every rank's shard is NOT searched).
+
+    Every post-processor gets ONE batch of (k + 1)^2 images as ``proc(batch, 'nnshift_%06d' % kimg)``, laid out as ``NNMonitor``'s
+    sheet: a row is a sample and, to its right, its nearest training windows in ascending distance.  A sound saver among the
+    post-processors therefore also writes the neighbours' audio.
+
+    The default period follows docs/experiments_shiftnn.md: a pass of 64 queries over 10 minutes of two-channel sound (10 strips x 75 000
+    columns) measured 195 ms at S = 1024 (12.7 ms at S = 256), 64 samples are one pass (two with mirror matching), and the 64 generator
+    passes are bounded by 64/3 measured train steps of 10.1 ms = 0.22 s; an evaluation is under 0.61 s even with mirror matching, and
+    under 1 % of a 3.3 s tick of 1 kimg (the rule of docs/experiments_swd.md) needs ticks >= 100 x 0.61 / 3.3 = 18.5: 20.  The search
+    is proportional to the length of the recordings: an hour of them costs six times as much, and ``nn_ticks`` should grow with it.
+
+    ``precision``: 'fp32' (default) or 'bf16', as in ``Evaluation``."""
+
+    def __init__(self, dataset, sample_fn, num_samples=64, k=3, nn_ticks=20, postprocessors=(), smoothed=None, mirror=None,
+                 drange=(-1, 1), precision='fp32', seg=None):
+        super(ShiftNNMonitor, self).__init__(nn_ticks, smoothed, precision)
+        if isinstance(k, bool) or int(k) != k or int(k) < 1:
+            raise ValueError('k must be a positive integer, got %r' % (k,))
+        if int(num_samples) != num_samples or int(num_samples) < int(k) + 1:
+            raise ValueError('num_samples = %r: the sheet shows k + 1 = %d samples' % (num_samples, int(k) + 1))
+        self.dataset, self.sample_fn = dataset, sample_fn
+        self.num_samples, self.k = int(num_samples), int(k)
+        self.postprocessors = postprocessors
+        self.mirror = bool(getattr(dataset, 'mirror_augment', False)) if mirror is None else bool(mirror)
+        self.drange, self.seg = drange, seg
+
+    def evaluate(self, tick):
+        import torch
+        from .metrics import ShiftNearestNeighbours
+        from .utils import run_postprocessors
+        nn = self.cached('all stages', lambda: ShiftNearestNeighbours(self.dataset, k=self.k, mirror=self.mirror, drange=self.drange,
+                                                                      seg=self.seg))
+        samples = self.generator().forward(self.sample_fn(self.num_samples).cuda())
+        res = nn.search(samples)
+        nearest = res['rms'][:, 0].numpy()                                 # fp64 on the host
+        self.stat('nn_shift_rms', float(nearest.mean()))
+        self.stat('nn_shift_rms_min', float(nearest.min()))
+        if not self.postprocessors:
+            return
+        rows = self.k + 1
+        near = nn.neighbours({name: res[name][:rows] for name in ('strip', 'start', 'mirrored')})   # [rows, k, C, r, r]
+        shown = samples[:rows].to(near.device)
+        batch = torch.cat([shown.unsqueeze(1), near], dim=1).reshape((rows * rows,) + tuple(shown.shape[1:]))
+        run_postprocessors(batch, 'nnshift_%06d' % (self.trainer.cur_nimg // 1000), self.postprocessors)
+
+
 class NDBMonitor(Evaluation):
     """Mode-coverage metric per tick (``metrics.NDB``: NDB/k and the JS divergence over k-means bins of the training images; the
     reference reports none): every ``ndb_ticks`` ticks and at the end, ``num_samples`` images of ``G.forward(sample_fn(n).cuda())``,
