@@ -2,11 +2,11 @@
 
 include/pggan_hip.h (the product boundary), include/pggan_hip_debug.h (thread-local diagnostic exports) and
 include/pggan_hip_cluster.h, include/pggan_hip_gan.h, include/pggan_hip_phase.h, include/pggan_hip_sampling.h,
-include/pggan_hip_projection.h, include/pggan_hip_crop.h, include/pggan_hip_swd.h, include/pggan_hip_mel.h, include/pggan_hip_resample.h and include/pggan_hip_shift.h (the k-means, the GAN-objective, the magnitude +
-instantaneous-frequency, the bf16 sampling, the projection-loss, the strip-crop, the C-channel sliced-Wasserstein, the warped-row sound, the rate-conversion and the shift-search additions to the boundary) are the one statement
+include/pggan_hip_projection.h, include/pggan_hip_crop.h, include/pggan_hip_swd.h, include/pggan_hip_mel.h, include/pggan_hip_resample.h, include/pggan_hip_shift.h and include/pggan_hip_prd.h (the k-means, the GAN-objective, the magnitude +
+instantaneous-frequency, the bf16 sampling, the projection-loss, the strip-crop, the C-channel sliced-Wasserstein, the warped-row sound, the rate-conversion, the shift-search and the k-NN-ball additions to the boundary) are the one statement
 of the ABI: the compiler holds every definition in csrc/*.hip against them, and this module parses them once into SIGNATURES /
-DEBUG_SIGNATURES / CLUSTER_SIGNATURES / GAN_SIGNATURES / PHASE_SIGNATURES / SAMPLING_SIGNATURES / PROJECTION_SIGNATURES / CROP_SIGNATURES / SWD_SIGNATURES / MEL_SIGNATURES / RESAMPLE_SIGNATURES / SHIFT_SIGNATURES (name -> argtypes), the
-return types, and CONSTANTS / CLUSTER_CONSTANTS / GAN_CONSTANTS / PHASE_CONSTANTS / SAMPLING_CONSTANTS / PROJECTION_CONSTANTS / CROP_CONSTANTS / SWD_CONSTANTS / MEL_CONSTANTS / RESAMPLE_CONSTANTS / SHIFT_CONSTANTS (every
+DEBUG_SIGNATURES / CLUSTER_SIGNATURES / GAN_SIGNATURES / PHASE_SIGNATURES / SAMPLING_SIGNATURES / PROJECTION_SIGNATURES / CROP_SIGNATURES / SWD_SIGNATURES / MEL_SIGNATURES / RESAMPLE_SIGNATURES / SHIFT_SIGNATURES / PRD_SIGNATURES (name -> argtypes), the
+return types, and CONSTANTS / CLUSTER_CONSTANTS / GAN_CONSTANTS / PHASE_CONSTANTS / SAMPLING_CONSTANTS / PROJECTION_CONSTANTS / CROP_CONSTANTS / SWD_CONSTANTS / MEL_CONSTANTS / RESAMPLE_CONSTANTS / SHIFT_CONSTANTS / PRD_CONSTANTS (every
 ``#define PG_*`` of the product header / of an addition as an integer).  A new entry point is
 declared in the header, defined in csrc/ and wrapped in ops.py; nothing is restated here.
 
@@ -143,6 +143,9 @@ _RESTYPE_OF.update(_resample_restypes)
 # ... and the nearest windows at every start column of the strips (csrc/shift_search.hip, wrapped in ops.py, used by metrics.py)
 SHIFT_SIGNATURES, _shift_restypes, SHIFT_CONSTANTS = _read_header('pggan_hip_shift.h')
 _RESTYPE_OF.update(_shift_restypes)
+# ... and the tile kernel of precision / recall / density / coverage over k-NN balls (csrc/prd.hip, wrapped in ops.py, used by metrics.py)
+PRD_SIGNATURES, _prd_restypes, PRD_CONSTANTS = _read_header('pggan_hip_prd.h')
+_RESTYPE_OF.update(_prd_restypes)
 ABI_VERSION = CONSTANTS['PG_ABI_VERSION']          # load() holds the library's pg_abi_version() against it: a stale .so is refused
 
 _lib = None
@@ -164,7 +167,8 @@ def load():
     for name, argtypes in (list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())
                            + list(GAN_SIGNATURES.items()) + list(PHASE_SIGNATURES.items()) + list(SAMPLING_SIGNATURES.items())
                            + list(PROJECTION_SIGNATURES.items()) + list(CROP_SIGNATURES.items()) + list(SWD_SIGNATURES.items())
-                           + list(MEL_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(SHIFT_SIGNATURES.items())):
+                           + list(MEL_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(SHIFT_SIGNATURES.items())
+                           + list(PRD_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

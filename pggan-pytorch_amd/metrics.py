@@ -35,7 +35,11 @@ the nearest window over all starts, segment by segment, without the per-start di
 
 ``NDB``: the number of statistically different bins and the Jensen-Shannon divergence over k-means bins of the training images (Richardson &
 Weiss 2018) -- does the generator cover the modes of the training set in the data's proportions, which none of the three above says.  Integer
-k-means on the device-resident stack: exact and reproducible; UNPINNED like the SWD and MS-SSIM."""
+k-means on the device-resident stack: exact and reproducible; UNPINNED like the SWD and MS-SSIM.
+
+``PrecisionRecall``: improved precision and recall with density and coverage over k-NN balls in uint8 image space (Kynkaanniemi et al.
+2019, Naeem et al. 2020) -- fidelity and coverage as separate numbers on one scale.  Three tile passes of exact integer distances of which
+no distance is stored; UNPINNED as well."""
 import math
 
 import numpy as np
@@ -754,5 +758,181 @@ class NDB(object):
             res = ndb_statistic(self.ref, self.gen, self.z_threshold)
             res.update(ref=self.ref.copy(), gen=self.gen.copy(), k=self.k, num_samples=self._fed, iterations=self.iterations,
                        converged=self.converged)
+            self._result = res
+        return self._result
+
+
+# ------------------------------------------------------------------------- precision / recall / density / coverage (k-NN balls)
+def _d2_host(a, b):
+    """int64 [Na,Nb]: the exact squared L2 distances between the rows of two uint8 arrays [n,D]."""
+    a64, b64 = a.astype(np.int64), b.astype(np.int64)
+    return (a64 * a64).sum(axis=1)[:, None] - 2 * (a64 @ b64.T) + (b64 * b64).sum(axis=1)[None]
+
+
+def _radii_host(x, k):
+    """``ops.prd_kth_u8`` in numpy int64: x [N,D] uint8 -> int64 [N], the k-th smallest distance to an image at ANOTHER INDEX."""
+    d = _d2_host(x, x)
+    np.fill_diagonal(d, np.iinfo(np.int64).max)
+    return np.partition(d, k - 1, axis=1)[:, k - 1].copy()
+
+
+def _ball_host(a, b, rad_a=None, rad_b=None):
+    """``ops.prd_ball_u8`` in numpy int64: (a_cnt, a_hit, b_cnt, b_hit) int32, None where the radius vector is."""
+    d = _d2_host(a, b)
+    a_cnt = b_hit = b_cnt = a_hit = None
+    if rad_b is not None:
+        inside = d <= np.asarray(rad_b, dtype=np.int64)[None]
+        a_cnt, b_hit = inside.sum(axis=1).astype(np.int32), inside.sum(axis=0).astype(np.int32)
+    if rad_a is not None:
+        inside = d <= np.asarray(rad_a, dtype=np.int64)[:, None]
+        b_cnt, a_hit = inside.sum(axis=0).astype(np.int32), inside.sum(axis=1).astype(np.int32)
+    return a_cnt, a_hit, b_cnt, b_hit
+
+
+def prd_statistic(fake_cnt, real_hit, real_cnt, k):
+    """The four numbers from the counts of one pass with a = fakes and b = reals (``ops.prd_ball_u8``): ``fake_cnt[g]`` real balls
+    fake g is inside, ``real_hit[r]`` fakes inside the ball of real r, ``real_cnt[r]`` fake balls real r is inside; integer counts, one
+    fp64 division each."""
+    fake_cnt, real_hit, real_cnt = (np.asarray(v, dtype=np.int64) for v in (fake_cnt, real_hit, real_cnt))
+    ng, nr = fake_cnt.size, real_hit.size
+    return {'precision': int((fake_cnt > 0).sum()) / float(ng), 'density': int(fake_cnt.sum()) / float(int(k) * ng),
+            'coverage': int((real_hit > 0).sum()) / float(nr), 'recall': int((real_cnt > 0).sum()) / float(nr)}
+
+
+class PrecisionRecall(object):
+    """Improved precision and recall (Kynkaanniemi et al. 2019) with density and coverage (Naeem et al. 2020) in uint8 image space:
+    fidelity and coverage as separate numbers on one scale.  Every image carries the ball whose radius is the distance to its ``k``-th
+    nearest neighbour in its own set (``rad_k``: the k-th smallest exact squared L2 distance to an image at another index; a probe ON
+    the boundary of a ball is inside).  With reals R and fakes G,
+
+        precision = the fraction of fakes inside at least one real ball      density  = sum over fakes of #real balls it is in / (k |G|)
+        recall    = the fraction of reals inside at least one fake ball      coverage = the fraction of reals whose ball holds a fake
+
+    Defined per image vector: 1-, 2-, 3- and 4-channel networks are measured alike, and no feature network is involved.  Integer
+    arithmetic: exact, the same bits from run to run, and ``device='cpu'`` (the numpy twin in int64) equals the device bit for bit.
+
+    ``source``: a ``DeviceImageDataset`` or a ``DeviceStripDataset`` (``fit()`` takes ``level_stack()`` of the current ``model_depth``;
+    ``range_in`` must be (0, 255)) or a uint8 tensor [M,C,r,r].  ``fit()`` keeps ``num_real`` images (None: all) -- the first entries of
+    ``torch.randperm(M)`` from a CPU generator seeded ``seed`` -- reduced to ``max_resolution`` when the stage is finer (``ops.pyramid_
+    level_u8``; None keeps the stage's resolution; the fakes are reduced alike), and their radii.  ``feed(samples_fp32)`` rounds to the
+    0..255 levels of the saved image (``ops.quantize_u8`` with ``drange``); ``feed_u8`` takes levels; batches of any size >= 1, at the
+    stage's resolution.  ``result()`` needs at least k + 1 fakes.  An evaluation is three tile passes (``ops.prd_kth_u8`` over the reals
+    at ``fit()``, over the fakes, and one ``ops.prd_ball_u8`` with a = fakes, b = reals) and one host read.  D = C r^2 after the
+    reduction must be a multiple of 16.  UNPINNED, like the SWD, MS-SSIM and NDB: comparable between runs of this project, not with
+    published tables (those are over VGG features)."""
+
+    def __init__(self, source, k=3, num_real=None, max_resolution=None, seed=0, drange=(-1, 1), device=None):
+        if torch.is_tensor(source):
+            if source.dtype != torch.uint8 or source.dim() != 4 or source.shape[0] < 1:
+                raise ValueError('source: expected a device dataset or a uint8 tensor [M,C,r,r]')
+            src_device = source.device
+        elif hasattr(source, 'level_stack'):
+            if tuple(source.range_in) != (0, 255):
+                raise ValueError('source: the data set holds range_in = %r; the balls are over 0..255 levels' % (tuple(source.range_in),))
+            src_device = source.device
+        else:
+            raise ValueError('source: expected a device dataset or a uint8 tensor [M,C,r,r], got %s' % type(source))
+        if isinstance(k, bool) or int(k) != k or not 1 <= k <= ops.NN_MAX_TOPK:
+            raise ValueError('k = %r (1 <= k <= %d)' % (k, ops.NN_MAX_TOPK))
+        if num_real is not None and (isinstance(num_real, bool) or int(num_real) != num_real or num_real < int(k) + 1):
+            raise ValueError('num_real = %r for k = %d (at least k + 1 images)' % (num_real, k))
+        if max_resolution is not None and (isinstance(max_resolution, bool) or int(max_resolution) != max_resolution
+                                           or max_resolution < 1 or max_resolution & (max_resolution - 1)):
+            raise ValueError('max_resolution must be a power of two, got %r' % (max_resolution,))
+        if not float(drange[1]) > float(drange[0]):
+            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
+        self.source, self.k, self.seed = source, int(k), int(seed)
+        self.num_real = None if num_real is None else int(num_real)
+        self.max_resolution = None if max_resolution is None else int(max_resolution)
+        self.drange = (float(drange[0]), float(drange[1]))
+        self.device = torch.device(src_device if device is None else device)
+        self.reals = self.radii = self.resolution = self.shape = self.indices = None
+        self.reset()
+
+    def stack(self):
+        """The uint8 stack [M,C,r,r] a fit made now would draw from, on ``device``."""
+        s = self.source if torch.is_tensor(self.source) else self.source.level_stack()
+        return s if s.device == self.device else s.to(self.device)
+
+    def _reduce(self, images):
+        """uint8 [n,C,r,r] at the stage's resolution -> at min(r, max_resolution), on ``device``."""
+        r = int(images.shape[-1])
+        if self.max_resolution is None or r <= self.max_resolution:
+            return images.contiguous()
+        depthdiff = (r // self.max_resolution).bit_length() - 1
+        if self.device.type == 'cuda':
+            return ops.pyramid_level_u8(images.contiguous(), depthdiff)
+        from .dataset import level_host
+        return torch.from_numpy(np.ascontiguousarray(level_host(images.numpy(), depthdiff)))
+
+    def fit(self):
+        """Take the reals of the current stage and their radii; stores ``reals`` uint8 [num_real,C,r',r'] and ``radii`` int64
+        [num_real] (on ``device``), ``indices`` (int64, host: the images taken), ``resolution`` (the STAGE's, what ``feed`` expects);
+        forgets what was fed.  Returns self."""
+        stack = self.stack()
+        M = stack.shape[0]
+        n = M if self.num_real is None else self.num_real
+        if not self.k + 1 <= n <= M:
+            raise ValueError('%d of %d images for k = %d (k + 1 <= num_real <= M)' % (n, M, self.k))
+        self.indices = torch.randperm(M, generator=torch.Generator().manual_seed(self.seed))[:n]
+        reals = self._reduce(stack.index_select(0, self.indices.to(self.device)))
+        if (reals.numel() // n) % 16:
+            raise ValueError('an image of %d bytes (a multiple of 16 is required)' % (reals.numel() // n))
+        if self.device.type == 'cuda':
+            self.radii = ops.prd_kth_u8(reals, self.k)
+        else:
+            self.radii = torch.from_numpy(_radii_host(reals.numpy().reshape(n, -1), self.k))
+        self.reals, self.shape, self.resolution = reals, tuple(stack.shape[1:]), int(stack.shape[-1])
+        self.reset()
+        return self
+
+    def reset(self):
+        """Forget what was fed; the fit is kept."""
+        self._fakes, self._fed, self._result = [], 0, None
+
+    def _fitted(self, images, dtype, what):
+        if self.reals is None:
+            raise RuntimeError('fit() first')
+        if not torch.is_tensor(images) or images.dtype != dtype or images.dim() != 4 or images.shape[0] < 1 \
+                or tuple(images.shape[1:]) != self.shape:
+            raise ValueError('%s: expected %s images [n,%d,%d,%d] (the fitted stage), got %s'
+                             % ((what, str(dtype).replace('torch.', '')) + self.shape
+                                + (tuple(images.shape) if torch.is_tensor(images) else type(images),)))
+        if self._result is not None:
+            raise RuntimeError('result() was taken: reset() before feeding again')
+
+    def feed(self, samples):
+        """Generated fp32 images [n,C,r,r] in ``drange``, n >= 1."""
+        self._fitted(samples, torch.float32, 'feed')
+        if self.device.type == 'cuda':
+            self.feed_u8(ops.quantize_u8(samples.to(self.device).contiguous(), self.drange))
+        else:
+            self.feed_u8(torch.from_numpy(_quantise_host(samples.cpu().numpy(), self.drange)))
+
+    def feed_u8(self, images):
+        """Generated images as 0..255 levels, uint8 [n,C,r,r], n >= 1."""
+        self._fitted(images, torch.uint8, 'feed_u8')
+        self._fakes.append(self._reduce(images.to(self.device)))
+        self._fed += images.shape[0]
+
+    def result(self):
+        """{'precision', 'recall', 'density', 'coverage' (fp64), 'num_real', 'num_fake', 'k'}.  One device synchronisation."""
+        if self._result is None:
+            if self.reals is None:
+                raise RuntimeError('fit() first')
+            if self._fed < self.k + 1:
+                raise RuntimeError('%d images were fed; the radii of the fakes need k + 1 = %d' % (self._fed, self.k + 1))
+            fakes = self._fakes[0] if len(self._fakes) == 1 else torch.cat(self._fakes)
+            if self.device.type == 'cuda':
+                fakes = fakes.contiguous()
+                fake_cnt, _, real_cnt, real_hit = ops.prd_ball_u8(fakes, self.reals, ops.prd_kth_u8(fakes, self.k), self.radii)
+                counts = torch.cat([fake_cnt, real_hit, real_cnt]).cpu().numpy()
+            else:
+                f, r = fakes.numpy().reshape(self._fed, -1), self.reals.numpy().reshape(self.reals.shape[0], -1)
+                fake_cnt, _, real_cnt, real_hit = _ball_host(f, r, _radii_host(f, self.k), self.radii.numpy())
+                counts = np.concatenate([fake_cnt, real_hit, real_cnt])
+            nr = self.reals.shape[0]
+            res = prd_statistic(counts[:self._fed], counts[self._fed:self._fed + nr], counts[self._fed + nr:], self.k)
+            res.update(num_real=nr, num_fake=self._fed, k=self.k)
             self._result = res
         return self._result

@@ -1283,6 +1283,74 @@ def nn_search_u8(stack_u8, queries_u8, k=1):
     return topk_smallest_i64(l2dist_u8(stack_u8, queries_u8), k)
 
 
+# ------------------------------------------------------------------------- k-NN balls: precision / recall / density / coverage (csrc/prd.hip)
+PRD = {name[len('PG_PRD_'):]: value for name, value in _lib.PRD_CONSTANTS.items() if name.startswith('PG_PRD_')}   # the addition's own table
+PRD_TILE = PRD['TILE']                                         # columns of one candidate block of pg_prd_kth_u8
+
+
+def _prd_radii(rad, n, device, what):
+    if rad is None:
+        return None
+    if not torch.is_tensor(rad) or rad.device != device or rad.dtype != torch.int64 or not rad.is_contiguous() or tuple(rad.shape) != (n,):
+        raise ValueError('prd_ball_u8: %s must be a contiguous int64 tensor [%d] on the device of the images' % (what, n))
+    return rad
+
+
+def prd_kth_u8(x_u8, k):
+    """The k-NN radii of a set of uint8 device images ``x_u8`` [N,C,r,r]: int64 [N], ``rad[i]`` = the ``k``-th smallest of the exact
+    squared L2 distances ``sum_d (x[i, d] - x[j, d])^2`` over j != i -- the exclusion is by index, a duplicate of image i elsewhere counts
+    with distance 0.  pg_prd_kth_u8 leaves the ``k`` smallest of every block of ``PRD_TILE`` columns ([N, ceil(N / PRD_TILE), k] int64:
+    nothing of size N x N exists), ``topk_smallest_i64`` takes the ``k``-th of those.  N >= k + 1, 1 <= k <= NN_MAX_TOPK.  No host
+    synchronisation."""
+    _u8_images(x_u8, 'prd_kth_u8')
+    N = x_u8.shape[0]
+    D = x_u8.numel() // N
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(N - 1, NN_MAX_TOPK):
+        raise ValueError('prd_kth_u8: k = %r for %d images (1 <= k <= min(N - 1, %d))' % (k, N, NN_MAX_TOPK))
+    if D % 16:
+        raise ValueError('prd_kth_u8: an image of %d bytes (a multiple of 16 is required)' % D)
+    k = int(k)
+    require_gpu()
+    blocks = (N + PRD_TILE - 1) // PRD_TILE
+    cand = torch.empty((N, blocks, k), device=x_u8.device, dtype=torch.int64)
+    _lib.call('pg_prd_kth_u8', x_u8.data_ptr(), N, D, k, cand.data_ptr(), _stream())
+    values, _ = topk_smallest_i64(cand.view(N, blocks * k), k)
+    return values[:, k - 1].contiguous()
+
+
+def prd_ball_u8(a_u8, b_u8, rad_a=None, rad_b=None):
+    """One pass over the pairs (p, c) of uint8 device images ``a_u8`` [Na,C,r,r] and ``b_u8`` [Nb,C,r,r] (pg_prd_ball_u8), with
+    ``d2 = sum_d (a[p, d] - b[c, d])^2`` exact: ``(a_cnt, a_hit, b_cnt, b_hit)``, int32 device tensors,
+    ``a_cnt[p] = #{c : d2 <= rad_b[c]}``, ``b_hit[c] = #{p : d2 <= rad_b[c]}`` (None without ``rad_b``) and
+    ``b_cnt[c] = #{p : d2 <= rad_a[p]}``, ``a_hit[p] = #{c : d2 <= rad_a[p]}`` (None without ``rad_a``).  ``rad_a`` [Na], ``rad_b`` [Nb]:
+    contiguous int64 device tensors, at least one of them.  No distance is written; no host synchronisation."""
+    _u8_images(a_u8, 'prd_ball_u8 a')
+    _u8_images(b_u8, 'prd_ball_u8 b')
+    if b_u8.device != a_u8.device or tuple(b_u8.shape[1:]) != tuple(a_u8.shape[1:]):
+        raise ValueError('prd_ball_u8: b %s on %s does not match a %s on %s'
+                         % (tuple(b_u8.shape), b_u8.device, tuple(a_u8.shape), a_u8.device))
+    Na, Nb = a_u8.shape[0], b_u8.shape[0]
+    D = a_u8.numel() // Na
+    if D % 16:
+        raise ValueError('prd_ball_u8: an image of %d bytes (a multiple of 16 is required)' % D)
+    rad_a = _prd_radii(rad_a, Na, a_u8.device, 'rad_a')
+    rad_b = _prd_radii(rad_b, Nb, a_u8.device, 'rad_b')
+    if rad_a is None and rad_b is None:
+        raise ValueError('prd_ball_u8: neither rad_a nor rad_b')
+    require_gpu()
+    a_cnt = b_hit = b_cnt = a_hit = None
+    if rad_b is not None:
+        a_cnt = torch.empty((Na,), device=a_u8.device, dtype=torch.int32)
+        b_hit = torch.empty((Nb,), device=a_u8.device, dtype=torch.int32)
+    if rad_a is not None:
+        b_cnt = torch.empty((Nb,), device=a_u8.device, dtype=torch.int32)
+        a_hit = torch.empty((Na,), device=a_u8.device, dtype=torch.int32)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.call('pg_prd_ball_u8', a_u8.data_ptr(), Na, b_u8.data_ptr(), Nb, D, ptr(rad_a), ptr(rad_b), ptr(a_cnt), ptr(a_hit), ptr(b_cnt),
+              ptr(b_hit), _stream())
+    return a_cnt, a_hit, b_cnt, b_hit
+
+
 # ------------------------------------------------------------------------- nearest windows at every start column (csrc/shift_search.hip)
 SHIFT = {name[len('PG_SHIFT_'):]: value for name, value in _lib.SHIFT_CONSTANTS.items() if name.startswith('PG_SHIFT_')}   # the addition's own table
 SHIFT_POS_BITS, SHIFT_MAX_QUERIES, SHIFT_TILE = SHIFT['POS_BITS'], SHIFT['MAX_QUERIES'], SHIFT['TILE']

@@ -621,6 +621,68 @@ class NDBMonitor(Evaluation):
         self.stat('jsd', res['jsd'], '{val:.4f}')
 
 
+class PRDMonitor(Evaluation):
+    """Fidelity and coverage per tick as separate numbers (``metrics.PrecisionRecall``: improved precision and recall over k-NN balls
+    with density and coverage, in uint8 image space; the reference reports none): every ``prd_ticks`` ticks and at the end,
+    ``num_samples`` images of ``G.forward(sample_fn(n).cuda())``, ``minibatch`` at a time -- of the smoothed generator when the trainer
+    keeps one (``smoothed`` as in ``Evaluation``) -- against ``num_real`` training images (``metric_kwargs``; default: all).
+    ``dataset``: a ``DeviceImageDataset`` or a ``DeviceStripDataset``; the reals and their radii are taken from ``level_stack()`` of the
+    current growth stage and REFITTED when the stage's resolution differs from the fitted one (once per stage, not per evaluation).
+    Writes ``stats['precision']``, ``stats['recall']``, ``stats['density']`` and ``stats['coverage']`` under the stat-dict convention of
+    the other monitors.  Defined per image vector: one-channel networks are measured like RGB ones.  Rank 0 evaluates (replicas are
+    identical; the reals are rank 0's shard).  Opt-in: a run that does not register it pays nothing.  ``metric_kwargs`` go to
+    ``PrecisionRecall`` (num_real, max_resolution, seed, drange).
+
+    ``max_resolution`` defaults to 256 HERE (``PrecisionRecall`` itself keeps the stage's resolution): above 256^2 both sets are
+    reduced with ``ops.pyramid_level_u8`` before they are compared.  The tile kernel gives every 128 x 128 tile of pairs to one
+    workgroup for all of D, so a few thousand images of 3 x 1024^2 bytes leave most of the device idle (docs/experiments_prd.md: 1024
+    against 1024 at 3 x 1024^2 took 23.6 ms and 25.4 ms per pass, 0.73x and 0.68x the composition from ``ops.l2dist_u8``), while at
+    3 x 256^2 and below the fused passes measured 2.9x to 40x faster than that composition.
+
+    The defaults follow docs/experiments_prd.md: with 4096 samples against 4096 reals the metric's own part of an evaluation measured
+    0.007 s at 1 x 256^2 (feed 2.9 ms for 256 batches of 16, the radii of the fakes and the ball pass 3.7 ms with the host read) and
+    the fit 2.0 ms; at 3 x 256^2 a radii pass over 4096 images took 6.2 ms and the ball pass 4096 x 4096 6.2 ms, i.e. for 30 000
+    reals by proportion (that size itself was not run) 6.2 x (30000 / 4096)^2 = 0.33 s for the fit, once per stage, and
+    6.2 + 6.2 x 30000 / 4096 = 52 ms per evaluation.  The 4096 generator passes are bounded by 4096 images at the 296 img/s of a
+    whole measured train step at 1024^2, 13.8 s.  An evaluation is under 13.8 + 0.1 + 0.33 = 14.3 s, and under 1 % of a 3.3 s tick of
+    1 kimg (the rule of docs/experiments_swd.md) needs ticks >= 100 x 14.3 / 3.3 = 433: 450.  ``num_samples=1024, prd_ticks=110``
+    costs the same share with noisier numbers; k-NN statistics need both sets in the thousands to be stable.
+
+    ``precision``: 'fp32' (default) or 'bf16', as in ``Evaluation`` (unrelated to the statistic of that name)."""
+
+    def __init__(self, dataset, sample_fn, num_samples=4096, minibatch=16, k=3, prd_ticks=450, smoothed=None, precision='fp32',
+                 **metric_kwargs):
+        super(PRDMonitor, self).__init__(prd_ticks, smoothed, precision)
+        if int(num_samples) < 1 or int(minibatch) < 1:
+            raise ValueError('num_samples and minibatch must be positive')
+        if isinstance(k, bool) or int(k) != k or not 1 <= k < int(num_samples):
+            raise ValueError('k = %r for %d samples (the radii of the samples need k + 1 of them)' % (k, num_samples))
+        self.dataset, self.sample_fn = dataset, sample_fn
+        self.num_samples, self.minibatch, self.k = int(num_samples), int(minibatch), int(k)
+        self.metric_kwargs = dict(metric_kwargs)
+        self.metric_kwargs.setdefault('max_resolution', 256)
+
+    def _stage_resolution(self):
+        stage = getattr(self.dataset, '_stage', None)
+        if stage is None:
+            return int(self.dataset.level_stack().shape[-1])
+        _, shift, depthdiff = stage()                                        # (no level is made for the answer)
+        return int(self.dataset.shape[-1]) >> (shift + depthdiff)
+
+    def evaluate(self, tick):
+        from .metrics import PrecisionRecall
+        metric = self.cached('all stages', lambda: PrecisionRecall(self.dataset, k=self.k, **self.metric_kwargs))
+        if metric.resolution != self._stage_resolution():
+            metric.fit()                                                     # (once per stage: reals and radii are retaken, the object stays)
+        metric.reset()
+        gen = self.generator()
+        for start in range(0, self.num_samples, self.minibatch):
+            metric.feed(gen.forward(self.sample_fn(min(self.minibatch, self.num_samples - start)).cuda()))
+        res = metric.result()
+        for name in ('precision', 'recall', 'density', 'coverage'):
+            self.stat(name, res[name], '{val:.3f}')
+
+
 class ProjectionMonitor(Evaluation):
     """Recall-style measure per tick (``projection.Projector``; the reference reports none): every ``projection_ticks`` ticks and at the
     end, a FIXED set of ``num_images`` real images is projected into the latent space of the generator -- of the smoothed generator when
