@@ -7,17 +7,12 @@ results are exact and the same from run to run.  No CPU fallback (``metrics.NDB(
 import torch
 
 from . import _lib, ops
-from .ops import _stream, require_gpu
+from .ops import _dev_tensor, _image_bytes, _stream, _u8_images, require_gpu
 
 _C = _lib.CLUSTER_CONSTANTS          # every #define PG_* that include/pggan_hip_cluster.h carries
 
 MAX_IMAGES = _C['PG_CLUSTER_MAX_IMAGES']                       # images of one fit: an int32 sum of that many bytes cannot overflow
 MAX_BINS = ops.NN_MAX_QUERIES                                   # centroids are the queries of one pass of ops.l2dist_u8
-
-
-def _u8_images(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 4 or t.shape[0] < 1:
-        raise ValueError('%s: expected a contiguous, non-empty uint8 device tensor [n,C,r,r]' % what)
 
 
 def _bins(K, what):
@@ -49,15 +44,10 @@ def cluster_sums_u8(stack_u8, label, K):
     (one 1-element host read)."""
     _u8_images(stack_u8, 'cluster_sums_u8 stack')
     K = _bins(K, 'cluster_sums_u8')
-    M = stack_u8.shape[0]
-    D = stack_u8.numel() // M
-    if M > MAX_IMAGES:
-        raise ValueError('cluster_sums_u8: %d images (at most %d: the sums are int32)' % (M, MAX_IMAGES))
-    if D % 16:
-        raise ValueError('cluster_sums_u8: an image of %d bytes (a multiple of 16 is required)' % D)
-    if (not torch.is_tensor(label) or label.device != stack_u8.device or label.dtype != torch.int32 or not label.is_contiguous()
-            or tuple(label.shape) != (M,)):
-        raise ValueError('cluster_sums_u8: label must be a contiguous int32 tensor [%d] on the device of the stack' % M)
+    if stack_u8.shape[0] > MAX_IMAGES:
+        raise ValueError('cluster_sums_u8: %d images (at most %d: the sums are int32)' % (stack_u8.shape[0], MAX_IMAGES))
+    M, D = _image_bytes(stack_u8, 'cluster_sums_u8')
+    _dev_tensor(label, torch.int32, (M,), stack_u8.device, 'cluster_sums_u8: label')
     require_gpu()
     if bool(((label < -1) | (label >= K)).any()):
         raise ValueError('cluster_sums_u8: labels must lie in -1 .. %d' % (K - 1))
@@ -77,15 +67,9 @@ def centroids_u8(sums, counts, previous):
     centroid (pg_cluster_centroids_u8, which updates the copy of ``previous`` made here in place)."""
     _u8_images(previous, 'centroids_u8 previous')
     K = _bins(previous.shape[0], 'centroids_u8')
-    D = previous.numel() // K
-    if D % 16:
-        raise ValueError('centroids_u8: an image of %d bytes (a multiple of 16 is required)' % D)
-    if (not torch.is_tensor(sums) or sums.device != previous.device or sums.dtype != torch.int32 or not sums.is_contiguous()
-            or tuple(sums.shape) != tuple(previous.shape)):
-        raise ValueError('centroids_u8: sums must be a contiguous int32 tensor %s on the device of the centroids' % (tuple(previous.shape),))
-    if (not torch.is_tensor(counts) or counts.device != previous.device or counts.dtype != torch.int64 or not counts.is_contiguous()
-            or tuple(counts.shape) != (K,)):
-        raise ValueError('centroids_u8: counts must be a contiguous int64 tensor [%d] on the device of the centroids' % K)
+    _, D = _image_bytes(previous, 'centroids_u8')
+    _dev_tensor(sums, torch.int32, previous.shape, previous.device, 'centroids_u8: sums')
+    _dev_tensor(counts, torch.int64, (K,), previous.device, 'centroids_u8: counts')
     require_gpu()
     out = torch.empty_like(previous)
     out.copy_(previous)

@@ -33,41 +33,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pggan_hip.h"
+#include "u8l2.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+using namespace u8l2;                      // v4i, v16i, SHIFT, I64_MAX, shifted, sumsq16, load16, grid_for
 
 constexpr int CHUNK = 128;                 // bytes of every image per step: 4 MFMAs of 32
 constexpr int TILE_M = 128;                // stack images per workgroup (4 waves x 32)
 constexpr int MAX_SLICE_CHUNKS = 512;      // 65536 terms per int32 accumulator lifetime (see Bounds)
 constexpr int MIN_SLICE_CHUNKS = 32;       // a slice shorter than 4 KiB per image is all epilogue
 constexpr int TARGET_WORKGROUPS = 1024;    // 4 per CU (768 = the 3 per CU the 64-query form admits measured the same)
-constexpr unsigned SHIFT = 0x80808080u;
-
-__device__ __forceinline__ v4i shifted(const uint4& v)
-{
-    v4i r;
-    r.x = (int)(v.x ^ SHIFT); r.y = (int)(v.y ^ SHIFT); r.z = (int)(v.z ^ SHIFT); r.w = (int)(v.w ^ SHIFT);
-    return r;
-}
-
-__device__ __forceinline__ int sumsq16(const v4i& v, int acc)
-{
-    acc = __builtin_amdgcn_sdot4(v.x, v.x, acc, false);
-    acc = __builtin_amdgcn_sdot4(v.y, v.y, acc, false);
-    acc = __builtin_amdgcn_sdot4(v.z, v.z, acc, false);
-    return __builtin_amdgcn_sdot4(v.w, v.w, acc, false);
-}
-
-// 16 bytes at p when valid, else the bytes that shift to zero
-__device__ __forceinline__ uint4 load16(const uint8_t* p, bool valid)
-{
-    uint4 v = make_uint4(SHIFT, SHIFT, SHIFT, SHIFT);
-    if (valid) v = *reinterpret_cast<const uint4*>(p);
-    return v;
-}
 
 template <int KT>
 __global__ __launch_bounds__(256) void l2dist_u8_kernel(const uint8_t* __restrict__ stack, const uint8_t* __restrict__ queries,
@@ -203,7 +179,6 @@ __global__ __launch_bounds__(256) void quantize_u8x4_kernel(const float4* __rest
 // registers (compile-time indices only); then k rounds of a workgroup-wide minimum over the threads' heads, the winner dropping
 // its head.  Keys are unique (the index breaks ties), so every round has exactly one winner: no atomics, no dependence on timing.
 constexpr int TOPK_LOADS = 8;
-constexpr long long I64_MAX = 0x7fffffffffffffffLL;
 
 __device__ __forceinline__ bool key_less(long long v, int i, long long w, int j) { return v < w || (v == w && i < j); }
 
@@ -262,14 +237,6 @@ __global__ __launch_bounds__(256) void topk_smallest_i64_kernel(const long long*
             idx[(long long)blockIdx.x * k + round] = bi;
         }
     }
-}
-
-inline int grid_for(long long total, int block = 256, int cap = 4096)
-{
-    long long g = (total + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 }  // namespace

@@ -42,45 +42,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pggan_hip_prd.h"
+#include "u8l2.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+using namespace u8l2;                      // v4i, v16i, SHIFT, I64_MAX, shifted, sumsq16, load16, grid_for
 
 constexpr int CHUNK = 128;                 // bytes of every image per step: 4 MFMAs of 32
 constexpr int TILE = PG_PRD_TILE;          // rows and columns per workgroup
 constexpr int WIDEN_CHUNKS = 512;          // 65536 terms per int32 accumulator lifetime (see Bounds)
 constexpr int BUF = 2048;                  // 16-byte slots of one staging buffer: [side 2][tile 4][piece 4][lane 64]
 constexpr int BAND = 8;                    // row tiles per rasterisation band
-constexpr unsigned SHIFT = 0x80808080u;
-constexpr long long I64_MAX = 0x7fffffffffffffffLL;
 // the epilogues' LDS, in 8-byte words of the staging area: T [32][128] | norms a [128] | norms b [128] | radii a [128] | 4 x [128] int32
 constexpr int LDS_NORM = 4096, LDS_RAD = LDS_NORM + 2 * TILE, LDS_CNT = LDS_RAD + TILE;
 static_assert(TILE == 128, "the tile kernel is written for 128 x 128");
-
-__device__ __forceinline__ v4i shifted(const uint4& v)
-{
-    v4i r;
-    r.x = (int)(v.x ^ SHIFT); r.y = (int)(v.y ^ SHIFT); r.z = (int)(v.z ^ SHIFT); r.w = (int)(v.w ^ SHIFT);
-    return r;
-}
-
-__device__ __forceinline__ int sumsq16(const v4i& v)
-{
-    int acc = __builtin_amdgcn_sdot4(v.x, v.x, 0, false);
-    acc = __builtin_amdgcn_sdot4(v.y, v.y, acc, false);
-    acc = __builtin_amdgcn_sdot4(v.z, v.z, acc, false);
-    return __builtin_amdgcn_sdot4(v.w, v.w, acc, false);
-}
-
-// 16 bytes at p when valid, else the bytes that shift to zero
-__device__ __forceinline__ uint4 load16(const uint8_t* p, bool valid)
-{
-    uint4 v = make_uint4(SHIFT, SHIFT, SHIFT, SHIFT);
-    if (valid) v = *reinterpret_cast<const uint4*>(p);
-    return v;
-}
 
 struct BallArgs {
     const long long* rad_a;
@@ -161,8 +136,8 @@ __global__ __launch_bounds__(256) void prd_tile_kernel(const uint8_t* __restrict
             const v4i va = shifted(ga[t]), vb = shifted(gb[t]);
             dst[t * 256 + wslot] = va;
             dst[1024 + t * 256 + wslot] = vb;
-            sna[t] += sumsq16(va);
-            snb[t] += sumsq16(vb);
+            sna[t] += sumsq16(va, 0);
+            snb[t] += sumsq16(vb, 0);
         }
     };
     auto compute = [&](int j) {

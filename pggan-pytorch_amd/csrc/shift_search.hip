@@ -33,28 +33,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pggan_hip_shift.h"
+#include "u8l2.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+using namespace u8l2;                      // v4i, v16i, SHIFT, I64_MAX, shifted, sumsq16, load16, grid_for
 
 constexpr int TILE = PG_SHIFT_TILE;
 constexpr int STEP = 256;                   // bytes of every query per step: 8 MFMAs of 32
 constexpr int WIDEN_STEPS = 256;            // 65536 terms per int32 accumulator lifetime (see Bounds)
 constexpr int XLDS_DWORDS = 8 * 4 * (32 / 4 + 31);   // the largest step: S = 32, 8 rows x 4 copies x 39 dwords
-constexpr unsigned SHIFT = 0x80808080u;
-constexpr long long I64_MAX = 0x7fffffffffffffffLL;
 
 static_assert(TILE == 128, "the wave / copy mapping below is written for 4 waves x 32 starts");
-
-__device__ __forceinline__ int sumsq16(const v4i& v, int acc)
-{
-    acc = __builtin_amdgcn_sdot4(v.x, v.x, acc, false);
-    acc = __builtin_amdgcn_sdot4(v.y, v.y, acc, false);
-    acc = __builtin_amdgcn_sdot4(v.z, v.z, acc, false);
-    return __builtin_amdgcn_sdot4(v.w, v.w, acc, false);
-}
 
 // the strip whose tiles hold workgroup `tile`: the last m with segtab[m].first_tile <= tile
 __device__ __forceinline__ int strip_of_tile(const int64_t* __restrict__ segtab, int M, long long tile)
@@ -271,14 +261,6 @@ __global__ __launch_bounds__(256) void shift_l2min_small_kernel(const uint8_t* _
         }
         atomicMin(out + (long long)k * G, ((long long)d << PG_SHIFT_POS_BITS) + (u - gl * seg));
     }
-}
-
-inline int grid_for(long long total, int block = 256, int cap = 4096)
-{
-    long long g = (total + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 }  // namespace

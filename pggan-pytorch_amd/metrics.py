@@ -120,9 +120,7 @@ class ChannelSlicedWasserstein(object):
 
     @staticmethod
     def _channels(num_channels):
-        if isinstance(num_channels, bool) or int(num_channels) != num_channels or not 1 <= num_channels <= ops.SWD_MAX_CHANNELS:
-            raise ValueError('num_channels must be an integer in 1 .. %d, got %r' % (ops.SWD_MAX_CHANNELS, num_channels))
-        return int(num_channels)
+        return _int_in(num_channels, 1, ops.SWD_MAX_CHANNELS, 'num_channels must be an integer in 1 .. %d, got %r' % (ops.SWD_MAX_CHANNELS, num_channels))
 
     def _op(self, phase, fn, *args, **kw):
         return fn(*args, **kw) if self.phase_hook is None else self.phase_hook(phase, fn, *args, **kw)
@@ -270,6 +268,108 @@ def _quantise_host(x, drange):
     return np.clip(np.round(y), 0, 255).astype(np.uint8)
 
 
+def _int_in(v, lo, hi, message):
+    """``int(v)`` of an integer (a bool is none) with lo <= v <= hi (None: no bound on that side), else ``ValueError(message)``."""
+    if isinstance(v, bool) or int(v) != v or (lo is not None and v < lo) or (hi is not None and v > hi):
+        raise ValueError(message)
+    return int(v)
+
+
+class _LevelMetric(object):
+    """What the metrics over the 0..255 levels of the saved image share (``NearestNeighbours``, ``ShiftNearestNeighbours``, ``NDB``,
+    ``PrecisionRecall``): ``drange`` and the ``device`` rule (None = where the source is, 'cpu' = the numpy twin), the one place that
+    quantises samples (``_levels``), the sample check and the host merge of a mirrored search.  A new metric states its own source
+    and arguments, then calls ``__init__`` here."""
+
+    def __init__(self, source, src_device, drange, device):
+        if not float(drange[1]) > float(drange[0]):
+            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
+        self.source, self.drange = source, (float(drange[0]), float(drange[1]))
+        self.device = torch.device(src_device if device is None else device)
+
+    @staticmethod
+    def _check_range_in(source):
+        if tuple(source.range_in) != (0, 255):
+            raise ValueError('source: the data set holds range_in = %r; the metric compares 0..255 levels' % (tuple(source.range_in),))
+
+    def _levels(self, samples, mirror=False):
+        """fp32 samples in ``drange`` -> their uint8 levels on ``device`` (``ops.quantize_u8``, or its numpy twin in host mode);
+        ``mirror``: followed by the left-right flipped copies."""
+        if self.device.type == 'cuda':
+            q = ops.quantize_u8(samples.to(self.device).contiguous(), self.drange)
+        else:
+            q = torch.from_numpy(_quantise_host(samples.cpu().numpy(), self.drange))
+        return torch.cat([q, q.flip(-1)]) if mirror else q
+
+    @staticmethod
+    def _check_samples(samples, shape):
+        if not torch.is_tensor(samples) or samples.dtype != torch.float32 or samples.dim() != 4 or samples.shape[0] < 1 \
+                or tuple(samples.shape[1:]) != tuple(shape):
+            raise ValueError('expected float32 samples [K,%d,%d,%d], got %s'
+                             % (tuple(shape) + (tuple(samples.shape) if torch.is_tensor(samples) else type(samples),)))
+
+    @staticmethod
+    def _merge_mirrored(*columns):
+        """The two sorted lists of k per sample of a mirrored search -> the k smallest keys of both.  ``columns``: arrays [2 K, k] in
+        KEY ORDER (most significant first), rows K .. 2 K - 1 the mirrored queries'; ``mirrored`` is the last, least significant key.
+        Returns the merged columns [K, k] and ``mirrored`` bool [K, k]."""
+        K, k = columns[0].shape[0] // 2, columns[0].shape[1]
+        both = [np.concatenate([a[:K], a[K:]], axis=1) for a in columns]
+        both.append(np.concatenate([np.zeros((K, k), dtype=bool), np.ones((K, k), dtype=bool)], axis=1))
+        order = np.stack([np.lexsort([a[i] for a in reversed(both)])[:k] for i in range(K)])      # (lexsort: the LAST key is primary)
+        return [np.take_along_axis(a, order, axis=1) for a in both]
+
+
+class _StackSource(object):
+    """The source of the metrics over an image stack: a uint8 tensor [M,C,r,r] or a data set with ``level_stack()``."""
+
+    @staticmethod
+    def _stack_source(source):
+        """(M, device) of a valid source."""
+        if torch.is_tensor(source):
+            if source.dtype != torch.uint8 or source.dim() != 4 or source.shape[0] < 1:
+                raise ValueError('source: expected a device dataset or a uint8 tensor [M,C,r,r]')
+            return source.shape[0], source.device
+        if not hasattr(source, 'level_stack'):
+            raise ValueError('source: expected a device dataset or a uint8 tensor [M,C,r,r], got %s' % type(source))
+        _LevelMetric._check_range_in(source)
+        return len(source), source.device
+
+    def stack(self):
+        """The uint8 stack [M,C,r,r] a search or a fit made now would read, on ``device``."""
+        s = self.source if torch.is_tensor(self.source) else self.source.level_stack()
+        return s if s.device == self.device else s.to(self.device)
+
+
+class _FittedFeed(object):
+    """The feed of the metrics that are fitted on the training stack once per stage and then fed generated images (``NDB``,
+    ``PrecisionRecall``).  The class supplies ``fit()`` -- which sets ``shape``, the [C,r,r] of the fitted stage -- ``reset()`` --
+    which zeroes ``_fed`` and ``_result`` -- ``_take(images_u8)``, what it does with a checked uint8 batch on ``device``, and
+    ``result()``."""
+
+    def _fitted(self, images, dtype, what):
+        if self.shape is None:
+            raise RuntimeError('fit() first')
+        if not torch.is_tensor(images) or images.dtype != dtype or images.dim() != 4 or images.shape[0] < 1 \
+                or tuple(images.shape[1:]) != self.shape:
+            raise ValueError('%s: expected %s images [n,%d,%d,%d] (the fitted stage), got %s'
+                             % ((what, str(dtype).replace('torch.', '')) + self.shape
+                                + (tuple(images.shape) if torch.is_tensor(images) else type(images),)))
+        if self._result is not None:
+            raise RuntimeError('result() was taken: reset() before feeding again')
+
+    def feed(self, samples):
+        """Generated fp32 images [n,C,r,r] in ``drange``, n >= 1."""
+        self._fitted(samples, torch.float32, 'feed')
+        self.feed_u8(self._levels(samples))
+
+    def feed_u8(self, images):
+        """Generated images as 0..255 levels, uint8 [n,C,r,r], n >= 1."""
+        self._fitted(images, torch.uint8, 'feed_u8')
+        self._take(images.to(self.device))
+        self._fed += images.shape[0]
+
+
 def _search_host(stack, queries, k):
     """``ops.nn_search_u8`` in numpy int64: (sqdist [K,k], index [K,k]), ascending by (distance, index)."""
     M = stack.shape[0]
@@ -284,7 +384,7 @@ def _search_host(stack, queries, k):
     return np.stack(sq).astype(np.int64), np.stack(ix).astype(np.int64)
 
 
-class NearestNeighbours(object):
+class NearestNeighbours(_StackSource, _LevelMetric):
     """``search(samples)``: the ``k`` nearest training images of every generated sample.
 
     ``source``: a ``DeviceImageDataset`` -- the stack of its current ``model_depth`` is taken at every call (``level_stack()``), so the
@@ -298,60 +398,23 @@ class NearestNeighbours(object):
     ``device``: None = where the source is; 'cpu' = the numpy twin in int64 (the same definition, no device)."""
 
     def __init__(self, source, k=1, mirror=False, drange=(-1, 1), device=None):
-        if torch.is_tensor(source):
-            if source.dtype != torch.uint8 or source.dim() != 4 or source.shape[0] < 1:
-                raise ValueError('source: expected a DeviceImageDataset or a uint8 tensor [M,C,r,r]')
-            M, src_device = source.shape[0], source.device
-        elif hasattr(source, 'level_stack'):
-            if tuple(source.range_in) != (0, 255):
-                raise ValueError('source: the data set holds range_in = %r; the search compares 0..255 levels' % (tuple(source.range_in),))
-            M, src_device = len(source), source.device
-        else:
-            raise ValueError('source: expected a DeviceImageDataset or a uint8 tensor [M,C,r,r], got %s' % type(source))
-        if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(M, ops.NN_MAX_TOPK):
-            raise ValueError('k = %r for %d images (1 <= k <= min(M, %d))' % (k, M, ops.NN_MAX_TOPK))
-        if not float(drange[1]) > float(drange[0]):
-            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
-        self.source, self.k, self.mirror = source, int(k), bool(mirror)
-        self.drange = (float(drange[0]), float(drange[1]))
-        self.device = torch.device(src_device if device is None else device)
-
-    def stack(self):
-        """The uint8 stack [M,C,r,r] a search made now would read, on ``device``."""
-        s = self.source if torch.is_tensor(self.source) else self.source.level_stack()
-        return s if s.device == self.device else s.to(self.device)
-
-    def _check(self, samples, stack):
-        if not torch.is_tensor(samples) or samples.dtype != torch.float32 or samples.dim() != 4 or samples.shape[0] < 1 \
-                or tuple(samples.shape[1:]) != tuple(stack.shape[1:]):
-            raise ValueError('expected float32 samples [K,%d,%d,%d], got %s'
-                             % (tuple(stack.shape[1:]) + (tuple(samples.shape) if torch.is_tensor(samples) else type(samples),)))
+        M, src_device = self._stack_source(source)
+        self.k = _int_in(k, 1, min(M, ops.NN_MAX_TOPK), 'k = %r for %d images (1 <= k <= min(M, %d))' % (k, M, ops.NN_MAX_TOPK))
+        self.mirror = bool(mirror)
+        super(NearestNeighbours, self).__init__(source, src_device, drange, device)
 
     def search(self, samples):
         """{'index': int64 [K,k], 'sqdist': int64 [K,k], 'rms': float64 [K,k] = sqrt(sqdist / D) in 0..255 levels (fp64, host),
         'mirrored': bool [K,k] (the neighbour matches the sample's mirror image)} as host tensors.  One device synchronisation."""
         stack = self.stack()
-        self._check(samples, stack)
+        self._check_samples(samples, stack.shape[1:])
         K, k = samples.shape[0], self.k
+        q = self._levels(samples, self.mirror)
         if self.device.type == 'cuda':
-            q = ops.quantize_u8(samples.to(self.device).contiguous(), self.drange)
-            if self.mirror:
-                q = torch.cat([q, q.flip(-1)])
-            sq, ix = ops.nn_search_u8(stack.contiguous(), q, k)
-            both = torch.stack([sq, ix]).cpu().numpy()
-            sq, ix = both[0], both[1]
+            sq, ix = torch.stack(ops.nn_search_u8(stack.contiguous(), q, k)).cpu().numpy()
         else:
-            q = _quantise_host(samples.cpu().numpy(), self.drange)
-            if self.mirror:
-                q = np.concatenate([q, q[..., ::-1]])
-            sq, ix = _search_host(stack.numpy(), q, k)
-        mirrored = np.zeros((K, k), dtype=bool)
-        if self.mirror:                                                  # two sorted lists of k per sample -> the k smallest keys of both
-            sq2 = np.concatenate([sq[:K], sq[K:]], axis=1)
-            ix2 = np.concatenate([ix[:K], ix[K:]], axis=1)
-            mr2 = np.concatenate([np.zeros((K, k), dtype=bool), np.ones((K, k), dtype=bool)], axis=1)
-            order = np.stack([np.lexsort((mr2[i], ix2[i], sq2[i]))[:k] for i in range(K)])
-            sq, ix, mirrored = (np.take_along_axis(a, order, axis=1) for a in (sq2, ix2, mr2))
+            sq, ix = _search_host(stack.numpy(), q.numpy(), k)
+        sq, ix, mirrored = self._merge_mirrored(sq, ix) if self.mirror else (sq, ix, np.zeros((K, k), dtype=bool))
         D = int(np.prod(stack.shape[1:]))
         return {'index': torch.from_numpy(np.ascontiguousarray(ix)), 'sqdist': torch.from_numpy(np.ascontiguousarray(sq)),
                 'rms': torch.from_numpy(np.sqrt(sq.astype(np.float64) / D)), 'mirrored': torch.from_numpy(np.ascontiguousarray(mirrored))}
@@ -395,7 +458,7 @@ def _topk_host(keys, k):
     return np.take_along_axis(keys, order, axis=1), order.astype(np.int64)
 
 
-class ShiftNearestNeighbours(object):
+class ShiftNearestNeighbours(_LevelMetric):
     """``search(samples)``: the ``k`` nearest training WINDOWS of every generated sample over every start column of the recordings --
     what ``NearestNeighbours`` on ``level_stack()`` cannot see, because that stack holds only the windows whose start is a multiple
     of the window width.
@@ -422,21 +485,16 @@ class ShiftNearestNeighbours(object):
         if isinstance(source, StripLevel):
             src_device, S, cols = source.buffer.device, source.S, source.cols
         elif hasattr(source, '_stage') and hasattr(source, 'lengths'):
-            if tuple(source.range_in) != (0, 255):
-                raise ValueError('source: the data set holds range_in = %r; the search compares 0..255 levels' % (tuple(source.range_in),))
+            self._check_range_in(source)
             src_device, S, cols = source.device, source.shape[2], source.lengths
         else:
             raise ValueError('source: expected a DeviceStripDataset or a StripLevel, got %s' % type(source))
         if seg is not None:
             ops._shift_seg(S, seg)
         G = len(ops.shift_segments(cols, S, seg)[0])                     # (the same at every stage when seg is None: T and S shrink together)
-        if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(G, ops.NN_MAX_TOPK):
-            raise ValueError('k = %r for %d segments (1 <= k <= min(G, %d))' % (k, G, ops.NN_MAX_TOPK))
-        if not float(drange[1]) > float(drange[0]):
-            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
-        self.source, self.k, self.mirror, self.seg = source, int(k), bool(mirror), None if seg is None else int(seg)
-        self.drange = (float(drange[0]), float(drange[1]))
-        self.device = torch.device(src_device if device is None else device)
+        self.k = _int_in(k, 1, min(G, ops.NN_MAX_TOPK), 'k = %r for %d segments (1 <= k <= min(G, %d))' % (k, G, ops.NN_MAX_TOPK))
+        self.mirror, self.seg = bool(mirror), None if seg is None else int(seg)
+        super(ShiftNearestNeighbours, self).__init__(source, src_device, drange, device)
         self._made = (None, None)                                        # ('direct' below the source: (stage key, the level made for it))
 
     # ------------------------------------------------------------------------------------------------- the level
@@ -482,34 +540,19 @@ class ShiftNearestNeighbours(object):
         reversed in time)} as host tensors.  One device synchronisation."""
         level, scale = self.level()
         C, S, cols = self._dims(level)
-        if not torch.is_tensor(samples) or samples.dtype != torch.float32 or samples.dim() != 4 or samples.shape[0] < 1 \
-                or tuple(samples.shape[1:]) != (C, S, S):
-            raise ValueError('expected float32 samples [K,%d,%d,%d], got %s'
-                             % (C, S, S, tuple(samples.shape) if torch.is_tensor(samples) else type(samples)))
+        self._check_samples(samples, (C, S, S))
         seg = self._seg(S)
         seg_strip, seg_start, _ = ops.shift_segments(cols, S, seg)
         K, k = samples.shape[0], self.k
         if k > seg_strip.size:
             raise ValueError('k = %d for %d segments at this stage' % (k, seg_strip.size))
+        q = self._levels(samples, self.mirror)
         if self.device.type == 'cuda':
-            q = ops.quantize_u8(samples.to(self.device).contiguous(), self.drange)
-            if self.mirror:
-                q = torch.cat([q, q.flip(-1)])
-            val, ix = ops.topk_smallest_i64(ops.shift_l2min_u8(level, q, seg), k)
-            both = torch.stack([val, ix]).cpu().numpy()
-            val, ix = both[0], both[1]
+            val, ix = torch.stack(ops.topk_smallest_i64(ops.shift_l2min_u8(level, q, seg), k)).cpu().numpy()
         else:
-            q = _quantise_host(samples.cpu().numpy(), self.drange)
-            if self.mirror:
-                q = np.concatenate([q, q[..., ::-1]])
-            val, ix = _topk_host(_shift_keys_host(level, q, seg), k)
+            val, ix = _topk_host(_shift_keys_host(level, q.numpy(), seg), k)
         sq, off = val >> ops.SHIFT_POS_BITS, val & (ops.SHIFT_MAX_SEG - 1)
-        mirrored = np.zeros((K, k), dtype=bool)
-        if self.mirror:                                                  # two sorted lists of k per sample -> the k smallest of both
-            sq2, ix2, off2 = (np.concatenate([a[:K], a[K:]], axis=1) for a in (sq, ix, off))
-            mr2 = np.concatenate([np.zeros((K, k), dtype=bool), np.ones((K, k), dtype=bool)], axis=1)
-            order = np.stack([np.lexsort((mr2[i], off2[i], ix2[i], sq2[i]))[:k] for i in range(K)])
-            sq, ix, off, mirrored = (np.take_along_axis(a, order, axis=1) for a in (sq2, ix2, off2, mr2))
+        sq, ix, off, mirrored = self._merge_mirrored(sq, ix, off) if self.mirror else (sq, ix, off, np.zeros((K, k), dtype=bool))
         D = C * S * S
         start = (seg_start[ix] + off) << scale
         return {'strip': torch.from_numpy(np.ascontiguousarray(seg_strip[ix])), 'start': torch.from_numpy(np.ascontiguousarray(start)),
@@ -536,11 +579,16 @@ class ShiftNearestNeighbours(object):
 Z_THRESHOLD_05 = 1.959963984540054                 # two-sided alpha = 0.05 of the standard normal: Phi^-1(0.975)
 
 
+def _d2_host(a, b):
+    """int64 [Na,Nb]: the exact squared L2 distances between the rows of two uint8 arrays [n,D]."""
+    a64, b64 = a.astype(np.int64), b.astype(np.int64)
+    return (a64 * a64).sum(axis=1)[:, None] - 2 * (a64 @ b64.T) + (b64 * b64).sum(axis=1)[None]
+
+
 def _assign_host(x, c):
     """``cluster.assign_u8`` in numpy int64: x [M,D], c [K,D] uint8 -> (label int32 [M], sqdist int64 [M]); argmin takes the first
     (lowest k) of equal distances."""
-    x64, c64 = x.astype(np.int64), c.astype(np.int64)
-    dist = (x64 * x64).sum(axis=1)[:, None] - 2 * (x64 @ c64.T) + (c64 * c64).sum(axis=1)[None]
+    dist = _d2_host(x, c)
     label = dist.argmin(axis=1)
     return label.astype(np.int32), dist[np.arange(x.shape[0]), label]
 
@@ -578,7 +626,7 @@ def ndb_statistic(ref, gen, z_threshold=Z_THRESHOLD_05):
     return {'ndb': ndb, 'ndb_over_k': ndb / float(len(ref)), 'jsd': 0.5 * kl_p + 0.5 * kl_q, 'z': z}
 
 
-class NDB(object):
+class NDB(_StackSource, _FittedFeed, _LevelMetric):
     """Number of statistically different bins (NDB/k) and the Jensen-Shannon divergence of the bin histograms (Richardson & Weiss 2018,
     "On GANs and GMMs"): does the generator cover the modes of the training set in the data's proportions?  ``fit()`` clusters the
     training images into ``k`` Voronoi cells by k-means in pixel space; ``feed`` counts generated images per cell; ``result()`` counts the
@@ -604,32 +652,17 @@ class NDB(object):
     levels.  Batches of any size >= 1.  ``device``: None = where the source is; 'cpu' = the numpy twin in int64, equal bit for bit."""
 
     def __init__(self, source, k=50, holdout=0, seed=0, max_iter=30, z_threshold=Z_THRESHOLD_05, drange=(-1, 1), device=None):
-        if torch.is_tensor(source):
-            if source.dtype != torch.uint8 or source.dim() != 4 or source.shape[0] < 1:
-                raise ValueError('source: expected a DeviceImageDataset or a uint8 tensor [M,C,r,r]')
-            M, src_device = source.shape[0], source.device
-        elif hasattr(source, 'level_stack'):
-            if tuple(source.range_in) != (0, 255):
-                raise ValueError('source: the data set holds range_in = %r; the bins are fitted on 0..255 levels' % (tuple(source.range_in),))
-            M, src_device = len(source), source.device
-        else:
-            raise ValueError('source: expected a DeviceImageDataset or a uint8 tensor [M,C,r,r], got %s' % type(source))
+        M, src_device = self._stack_source(source)
         from . import cluster
         if not 1 <= M <= cluster.MAX_IMAGES:
             raise ValueError('%d images (1 <= M <= %d: the per-bin sums are int32)' % (M, cluster.MAX_IMAGES))
-        if isinstance(k, bool) or int(k) != k or not 2 <= k <= ops.NN_MAX_QUERIES:
-            raise ValueError('k = %r (2 <= k <= %d)' % (k, ops.NN_MAX_QUERIES))
-        if isinstance(holdout, bool) or int(holdout) != holdout or not 0 <= holdout < M - int(k) + 1:
-            raise ValueError('holdout = %r for %d images and k = %d (0 <= holdout < M - k + 1)' % (holdout, M, k))
-        if isinstance(max_iter, bool) or int(max_iter) != max_iter or max_iter < 1:
-            raise ValueError('max_iter must be a positive integer, got %r' % (max_iter,))
+        self.k = _int_in(k, 2, ops.NN_MAX_QUERIES, 'k = %r (2 <= k <= %d)' % (k, ops.NN_MAX_QUERIES))
+        self.holdout = _int_in(holdout, 0, M - self.k, 'holdout = %r for %d images and k = %d (0 <= holdout < M - k + 1)' % (holdout, M, self.k))
+        self.max_iter = _int_in(max_iter, 1, None, 'max_iter must be a positive integer, got %r' % (max_iter,))
         if not float(z_threshold) > 0:
             raise ValueError('z_threshold must be positive, got %r' % (z_threshold,))
-        if not float(drange[1]) > float(drange[0]):
-            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
-        self.source, self.k, self.holdout, self.seed, self.max_iter = source, int(k), int(holdout), int(seed), int(max_iter)
-        self.z_threshold, self.drange = float(z_threshold), (float(drange[0]), float(drange[1]))
-        self.device = torch.device(src_device if device is None else device)
+        self.seed, self.z_threshold = int(seed), float(z_threshold)
+        super(NDB, self).__init__(source, src_device, drange, device)
         self.num_images = M
         self.centroids = self.labels = self.ref = self.iterations = self.converged = self.resolution = self.shape = None
         self.reset()
@@ -639,11 +672,6 @@ class NDB(object):
         perm = torch.randperm(self.num_images, generator=torch.Generator().manual_seed(self.seed))
         return perm[:self.holdout], perm[self.holdout:]
 
-    def stack(self):
-        """The uint8 stack [M,C,r,r] a fit made now would cluster, on ``device``."""
-        s = self.source if torch.is_tensor(self.source) else self.source.level_stack()
-        return s if s.device == self.device else s.to(self.device)
-
     def fit(self):
         """Cluster the stack of the current stage; stores ``centroids`` uint8 [k,C,r,r] and ``labels`` int32 [M] (on ``device``), ``ref``
         (int64 [k], host), ``iterations``, ``converged``, ``resolution``; forgets what was fed.  Returns self."""
@@ -651,9 +679,7 @@ class NDB(object):
         M, K = stack.shape[0], self.k
         if M != self.num_images:
             raise ValueError('the source holds %d images now, %d at construction' % (M, self.num_images))
-        D = stack.numel() // M
-        if D % 16:
-            raise ValueError('an image of %d bytes (a multiple of 16 is required)' % D)
+        _, D = ops._image_bytes(stack, 'NDB.fit')
         held, fit = self.split()
         init = fit[torch.randperm(fit.numel(), generator=torch.Generator().manual_seed(self.seed + 1))[:K]]
         if self.device.type == 'cuda':
@@ -710,40 +736,19 @@ class NDB(object):
         self._fed = 0
         self._result = None
 
-    def _fitted(self, images, dtype, what):
-        if self.centroids is None:
-            raise RuntimeError('fit() first')
-        if not torch.is_tensor(images) or images.dtype != dtype or images.dim() != 4 or images.shape[0] < 1 \
-                or tuple(images.shape[1:]) != self.shape:
-            raise ValueError('%s: expected %s images [n,%d,%d,%d] (the fitted resolution), got %s'
-                             % ((what, str(dtype).replace('torch.', '')) + self.shape
-                                + (tuple(images.shape) if torch.is_tensor(images) else type(images),)))
-        if self._result is not None:
-            raise RuntimeError('result() was taken: reset() before feeding again')
-
-    def feed(self, samples):
-        """Generated fp32 images [n,C,r,r] in ``drange``, n >= 1."""
-        self._fitted(samples, torch.float32, 'feed')
-        if self.device.type == 'cuda':
-            self.feed_u8(ops.quantize_u8(samples.to(self.device).contiguous(), self.drange))
-        else:
-            self.feed_u8(torch.from_numpy(_quantise_host(samples.cpu().numpy(), self.drange)))
-
-    def feed_u8(self, images):
-        """Generated images as 0..255 levels, uint8 [n,C,r,r], n >= 1."""
-        self._fitted(images, torch.uint8, 'feed_u8')
+    def _take(self, images):
+        """Count a batch per bin."""
         n = images.shape[0]
         if self.device.type == 'cuda':
             from . import cluster
-            images = images.to(self.device).contiguous()
+            images = images.contiguous()
             for a in range(0, n, ops.NN_MAX_QUERIES * 64):              # (any size: the distances of a chunk are [k, chunk] int64)
                 label, _ = cluster.assign_u8(images[a:a + ops.NN_MAX_QUERIES * 64], self.centroids)
                 counts = torch.bincount(label.to(torch.int64), minlength=self.k)
                 self._counts = counts if self._counts is None else self._counts + counts
         else:
-            label, _ = _assign_host(images.cpu().numpy().reshape(n, -1), self.centroids.numpy().reshape(self.k, -1))
+            label, _ = _assign_host(images.numpy().reshape(n, -1), self.centroids.numpy().reshape(self.k, -1))
             self.gen = self.gen + np.bincount(label, minlength=self.k).astype(np.int64)
-        self._fed += n
 
     def result(self):
         """{'ndb', 'ndb_over_k', 'jsd', 'z' (float64 [k]), 'ref', 'gen' (int64 [k]), 'k', 'num_samples', 'iterations', 'converged'}
@@ -763,12 +768,6 @@ class NDB(object):
 
 
 # ------------------------------------------------------------------------- precision / recall / density / coverage (k-NN balls)
-def _d2_host(a, b):
-    """int64 [Na,Nb]: the exact squared L2 distances between the rows of two uint8 arrays [n,D]."""
-    a64, b64 = a.astype(np.int64), b.astype(np.int64)
-    return (a64 * a64).sum(axis=1)[:, None] - 2 * (a64 @ b64.T) + (b64 * b64).sum(axis=1)[None]
-
-
 def _radii_host(x, k):
     """``ops.prd_kth_u8`` in numpy int64: x [N,D] uint8 -> int64 [N], the k-th smallest distance to an image at ANOTHER INDEX."""
     d = _d2_host(x, x)
@@ -799,7 +798,7 @@ def prd_statistic(fake_cnt, real_hit, real_cnt, k):
             'coverage': int((real_hit > 0).sum()) / float(nr), 'recall': int((real_cnt > 0).sum()) / float(nr)}
 
 
-class PrecisionRecall(object):
+class PrecisionRecall(_StackSource, _FittedFeed, _LevelMetric):
     """Improved precision and recall (Kynkaanniemi et al. 2019) with density and coverage (Naeem et al. 2020) in uint8 image space:
     fidelity and coverage as separate numbers on one scale.  Every image carries the ball whose radius is the distance to its ``k``-th
     nearest neighbour in its own set (``rad_k``: the k-th smallest exact squared L2 distance to an image at another index; a probe ON
@@ -822,37 +821,20 @@ class PrecisionRecall(object):
     published tables (those are over VGG features)."""
 
     def __init__(self, source, k=3, num_real=None, max_resolution=None, seed=0, drange=(-1, 1), device=None):
-        if torch.is_tensor(source):
-            if source.dtype != torch.uint8 or source.dim() != 4 or source.shape[0] < 1:
-                raise ValueError('source: expected a device dataset or a uint8 tensor [M,C,r,r]')
-            src_device = source.device
-        elif hasattr(source, 'level_stack'):
-            if tuple(source.range_in) != (0, 255):
-                raise ValueError('source: the data set holds range_in = %r; the balls are over 0..255 levels' % (tuple(source.range_in),))
-            src_device = source.device
-        else:
-            raise ValueError('source: expected a device dataset or a uint8 tensor [M,C,r,r], got %s' % type(source))
-        if isinstance(k, bool) or int(k) != k or not 1 <= k <= ops.NN_MAX_TOPK:
-            raise ValueError('k = %r (1 <= k <= %d)' % (k, ops.NN_MAX_TOPK))
-        if num_real is not None and (isinstance(num_real, bool) or int(num_real) != num_real or num_real < int(k) + 1):
-            raise ValueError('num_real = %r for k = %d (at least k + 1 images)' % (num_real, k))
-        if max_resolution is not None and (isinstance(max_resolution, bool) or int(max_resolution) != max_resolution
-                                           or max_resolution < 1 or max_resolution & (max_resolution - 1)):
-            raise ValueError('max_resolution must be a power of two, got %r' % (max_resolution,))
-        if not float(drange[1]) > float(drange[0]):
-            raise ValueError('drange must be (lo, hi) with hi > lo, got %r' % (drange,))
-        self.source, self.k, self.seed = source, int(k), int(seed)
-        self.num_real = None if num_real is None else int(num_real)
-        self.max_resolution = None if max_resolution is None else int(max_resolution)
-        self.drange = (float(drange[0]), float(drange[1]))
-        self.device = torch.device(src_device if device is None else device)
+        _, src_device = self._stack_source(source)
+        self.k = _int_in(k, 1, ops.NN_MAX_TOPK, 'k = %r (1 <= k <= %d)' % (k, ops.NN_MAX_TOPK))
+        self.num_real = self.max_resolution = None
+        if num_real is not None:
+            self.num_real = _int_in(num_real, self.k + 1, None, 'num_real = %r for k = %d (at least k + 1 images)' % (num_real, self.k))
+        if max_resolution is not None:
+            message = 'max_resolution must be a power of two, got %r' % (max_resolution,)
+            self.max_resolution = _int_in(max_resolution, 1, None, message)
+            if self.max_resolution & (self.max_resolution - 1):
+                raise ValueError(message)
+        self.seed = int(seed)
+        super(PrecisionRecall, self).__init__(source, src_device, drange, device)
         self.reals = self.radii = self.resolution = self.shape = self.indices = None
         self.reset()
-
-    def stack(self):
-        """The uint8 stack [M,C,r,r] a fit made now would draw from, on ``device``."""
-        s = self.source if torch.is_tensor(self.source) else self.source.level_stack()
-        return s if s.device == self.device else s.to(self.device)
 
     def _reduce(self, images):
         """uint8 [n,C,r,r] at the stage's resolution -> at min(r, max_resolution), on ``device``."""
@@ -876,8 +858,7 @@ class PrecisionRecall(object):
             raise ValueError('%d of %d images for k = %d (k + 1 <= num_real <= M)' % (n, M, self.k))
         self.indices = torch.randperm(M, generator=torch.Generator().manual_seed(self.seed))[:n]
         reals = self._reduce(stack.index_select(0, self.indices.to(self.device)))
-        if (reals.numel() // n) % 16:
-            raise ValueError('an image of %d bytes (a multiple of 16 is required)' % (reals.numel() // n))
+        ops._image_bytes(reals, 'PrecisionRecall.fit')
         if self.device.type == 'cuda':
             self.radii = ops.prd_kth_u8(reals, self.k)
         else:
@@ -890,30 +871,9 @@ class PrecisionRecall(object):
         """Forget what was fed; the fit is kept."""
         self._fakes, self._fed, self._result = [], 0, None
 
-    def _fitted(self, images, dtype, what):
-        if self.reals is None:
-            raise RuntimeError('fit() first')
-        if not torch.is_tensor(images) or images.dtype != dtype or images.dim() != 4 or images.shape[0] < 1 \
-                or tuple(images.shape[1:]) != self.shape:
-            raise ValueError('%s: expected %s images [n,%d,%d,%d] (the fitted stage), got %s'
-                             % ((what, str(dtype).replace('torch.', '')) + self.shape
-                                + (tuple(images.shape) if torch.is_tensor(images) else type(images),)))
-        if self._result is not None:
-            raise RuntimeError('result() was taken: reset() before feeding again')
-
-    def feed(self, samples):
-        """Generated fp32 images [n,C,r,r] in ``drange``, n >= 1."""
-        self._fitted(samples, torch.float32, 'feed')
-        if self.device.type == 'cuda':
-            self.feed_u8(ops.quantize_u8(samples.to(self.device).contiguous(), self.drange))
-        else:
-            self.feed_u8(torch.from_numpy(_quantise_host(samples.cpu().numpy(), self.drange)))
-
-    def feed_u8(self, images):
-        """Generated images as 0..255 levels, uint8 [n,C,r,r], n >= 1."""
-        self._fitted(images, torch.uint8, 'feed_u8')
-        self._fakes.append(self._reduce(images.to(self.device)))
-        self._fed += images.shape[0]
+    def _take(self, images):
+        """Keep a batch, reduced like the reals."""
+        self._fakes.append(self._reduce(images))
 
     def result(self):
         """{'precision', 'recall', 'density', 'coverage' (fp64), 'num_real', 'num_fake', 'k'}.  One device synchronisation."""

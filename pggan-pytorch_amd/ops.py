@@ -1216,6 +1216,24 @@ def _u8_images(t, what):
         raise ValueError('%s: expected a contiguous, non-empty uint8 device tensor [n,C,r,r]' % what)
 
 
+def _image_bytes(images_u8, who):
+    """(n, D) of a checked uint8 image tensor [n,C,r,r]: D = C r^2 bytes per image, a multiple of 16 (the kernels load 16 bytes at a
+    time); ``who`` is the refusing call."""
+    n = images_u8.shape[0]
+    D = images_u8.numel() // n
+    if D % 16:
+        raise ValueError('%s: an image of %d bytes (a multiple of 16 is required)' % (who, D))
+    return n, D
+
+
+def _dev_tensor(t, dtype, shape, device, what):
+    """``t`` when it is a contiguous ``dtype`` tensor of ``shape`` on ``device``, where the call's images are; ``what`` = 'call: argument'."""
+    if not torch.is_tensor(t) or t.device != device or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError('%s must be a contiguous %s tensor %s on the device of the other operands (%s)'
+                         % (what, str(dtype).replace('torch.', ''), list(shape), device))
+    return t
+
+
 def quantize_u8(images, drange=(-1, 1)):
     """fp32 device images [n,C,r,r] in ``drange`` -> the uint8 levels of the saved image in the same layout (pg_quantize_u8):
     ``(x - lo) * (255 / (hi - lo))`` in fp32 with one rounding per operation, round half to even, clip to [0, 255] -- the arithmetic of
@@ -1241,15 +1259,11 @@ def l2dist_u8(stack_u8, queries_u8, out=None):
     if queries_u8.device != stack_u8.device or tuple(queries_u8.shape[1:]) != tuple(stack_u8.shape[1:]):
         raise ValueError('l2dist_u8: queries %s on %s do not match the stack %s on %s'
                          % (tuple(queries_u8.shape), queries_u8.device, tuple(stack_u8.shape), stack_u8.device))
-    M, K = stack_u8.shape[0], queries_u8.shape[0]
-    D = stack_u8.numel() // M
-    if D % 16:
-        raise ValueError('l2dist_u8: an image of %d bytes (a multiple of 16 is required)' % D)
+    (M, D), K = _image_bytes(stack_u8, 'l2dist_u8'), queries_u8.shape[0]
     if out is None:
         out = torch.empty((K, M), device=stack_u8.device, dtype=torch.int64)
-    elif (not torch.is_tensor(out) or out.device != stack_u8.device or out.dtype != torch.int64 or not out.is_contiguous()
-          or tuple(out.shape) != (K, M)):
-        raise ValueError('l2dist_u8: out must be a contiguous int64 tensor [%d,%d] on the device of the stack' % (K, M))
+    else:
+        _dev_tensor(out, torch.int64, (K, M), stack_u8.device, 'l2dist_u8: out')
     require_gpu()
     s = _stream()
     for k0 in range(0, K, NN_MAX_QUERIES):
@@ -1289,11 +1303,7 @@ PRD_TILE = PRD['TILE']                                         # columns of one 
 
 
 def _prd_radii(rad, n, device, what):
-    if rad is None:
-        return None
-    if not torch.is_tensor(rad) or rad.device != device or rad.dtype != torch.int64 or not rad.is_contiguous() or tuple(rad.shape) != (n,):
-        raise ValueError('prd_ball_u8: %s must be a contiguous int64 tensor [%d] on the device of the images' % (what, n))
-    return rad
+    return None if rad is None else _dev_tensor(rad, torch.int64, (n,), device, 'prd_ball_u8: ' + what)
 
 
 def prd_kth_u8(x_u8, k):
@@ -1304,11 +1314,9 @@ def prd_kth_u8(x_u8, k):
     synchronisation."""
     _u8_images(x_u8, 'prd_kth_u8')
     N = x_u8.shape[0]
-    D = x_u8.numel() // N
     if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(N - 1, NN_MAX_TOPK):
         raise ValueError('prd_kth_u8: k = %r for %d images (1 <= k <= min(N - 1, %d))' % (k, N, NN_MAX_TOPK))
-    if D % 16:
-        raise ValueError('prd_kth_u8: an image of %d bytes (a multiple of 16 is required)' % D)
+    _, D = _image_bytes(x_u8, 'prd_kth_u8')
     k = int(k)
     require_gpu()
     blocks = (N + PRD_TILE - 1) // PRD_TILE
@@ -1329,10 +1337,7 @@ def prd_ball_u8(a_u8, b_u8, rad_a=None, rad_b=None):
     if b_u8.device != a_u8.device or tuple(b_u8.shape[1:]) != tuple(a_u8.shape[1:]):
         raise ValueError('prd_ball_u8: b %s on %s does not match a %s on %s'
                          % (tuple(b_u8.shape), b_u8.device, tuple(a_u8.shape), a_u8.device))
-    Na, Nb = a_u8.shape[0], b_u8.shape[0]
-    D = a_u8.numel() // Na
-    if D % 16:
-        raise ValueError('prd_ball_u8: an image of %d bytes (a multiple of 16 is required)' % D)
+    (Na, D), Nb = _image_bytes(a_u8, 'prd_ball_u8'), b_u8.shape[0]
     rad_a = _prd_radii(rad_a, Na, a_u8.device, 'rad_a')
     rad_b = _prd_radii(rad_b, Nb, a_u8.device, 'rad_b')
     if rad_a is None and rad_b is None:
@@ -1437,10 +1442,8 @@ def shift_l2min_u8(level, queries_u8, seg=None, table=None):
                          % (tuple(queries_u8.shape), queries_u8.device, C, S, S, level.buffer.device))
     if table is None:
         table = shift_table(level, seg)
-    elif (not torch.is_tensor(table) or table.device != level.buffer.device or table.dtype != torch.int64 or not table.is_contiguous()
-          or tuple(table.shape) != (M + 1, SHIFT['SEGTAB_WORDS'])):
-        raise ValueError('shift_l2min_u8: table must be the int64 tensor [%d,%d] of shift_table on the device of the level'
-                         % (M + 1, SHIFT['SEGTAB_WORDS']))
+    else:
+        _dev_tensor(table, torch.int64, (M + 1, SHIFT['SEGTAB_WORDS']), level.buffer.device, 'shift_l2min_u8: table (of shift_table)')
     tiles = sum(-(-(T - S + 1) // SHIFT_TILE) for T in level.cols)
     G = sum(-(-(T - S + 1) // seg) for T in level.cols)
     K = queries_u8.shape[0]

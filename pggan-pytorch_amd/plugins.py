@@ -12,6 +12,9 @@ import warnings
 from datetime import timedelta
 from glob import glob
 
+from . import metrics
+from .metrics import _int_in
+
 
 class Plugin(object):
     """The plugin protocol ``Trainer`` dispatches on: ``trigger_interval`` = list of (period, unit) pairs, ``register(trainer)``,
@@ -346,6 +349,12 @@ class Evaluation(Plugin):
         return self._metric_obj
 
 
+def _batches(total, minibatch):
+    """The batch sizes of ``total`` items taken ``minibatch`` at a time, in order: all ``minibatch`` but a smaller last one."""
+    for start in range(0, total, minibatch):
+        yield min(minibatch, total - start)
+
+
 class OutputGenerator(Evaluation):
     """Sample-grid hook (plugins.py:177-195): every ``output_snapshot_ticks`` ticks run G on fresh latents and
     hand the fp32 ``[n,C,H,W]`` array to each postprocessor as ``proc(out, kimg)``.  A postprocessor exposing
@@ -395,7 +404,6 @@ class SWDMonitor(Evaluation):
         self.metric_kwargs = metric_kwargs
 
     def evaluate(self, tick):
-        from . import metrics
         resolution, channels = 4 * 2 ** self.trainer.G.depth, int(getattr(self.trainer.G, 'num_channels', 3))
         if resolution < 16:
             return
@@ -406,8 +414,7 @@ class SWDMonitor(Evaluation):
         metric = self.cached((resolution, channels), make)
         metric.reset()
         gen = self.generator()
-        for start in range(0, self.num_images, self.minibatch):
-            n = min(self.minibatch, self.num_images - start)
+        for n in _batches(self.num_images, self.minibatch):
             metric.feed_real(self.real_batch_fn(n))
             metric.feed_fake(gen.forward(self.sample_fn(n).cuda()))
         res = metric.result()
@@ -442,16 +449,14 @@ class MSSSIMMonitor(Evaluation):
         self.metric_kwargs = metric_kwargs
 
     def evaluate(self, tick):
-        from .metrics import MultiScaleSSIM
         resolution, channels = 4 * 2 ** self.trainer.G.depth, int(self.trainer.G.num_channels)
         if resolution < 16:
             return
         metric = self.cached((resolution, channels),
-                             lambda: MultiScaleSSIM(resolution, self.num_pairs, num_channels=channels, **self.metric_kwargs))
+                             lambda: metrics.MultiScaleSSIM(resolution, self.num_pairs, num_channels=channels, **self.metric_kwargs))
         metric.reset()
         gen = self.generator()
-        for start in range(0, self.num_pairs, self.minibatch):
-            n = min(self.minibatch, self.num_pairs - start)
+        for n in _batches(self.num_pairs, self.minibatch):
             a = gen.forward(self.sample_fn(n).cuda())
             metric.feed(a, gen.forward(self.sample_fn(n).cuda()))
         res = metric.result()
@@ -459,7 +464,44 @@ class MSSSIMMonitor(Evaluation):
         self.stat('msssim_std', res['std'], '{val:.4f}')
 
 
-class NNMonitor(Evaluation):
+class _NeighbourSheet(Evaluation):
+    """What ``NNMonitor`` and ``ShiftNNMonitor`` share: ``num_samples`` generated images are searched for their ``k`` nearest training
+    items, two stats are written and the post-processors get the sheet of (k + 1)^2 images.  A subclass declares ``metric`` (the name of
+    the class in ``metrics``; it is made once, with ``metric_kwargs`` on top of k, mirror and drange), ``stat_prefix`` and ``sheet_prefix`` (the
+    prefixes of the stat names and of the description) and ``fields`` (the result fields ``neighbours()`` takes)."""
+
+    metric = stat_prefix = sheet_prefix = fields = None
+
+    def __init__(self, ticks, dataset, sample_fn, num_samples, k, postprocessors, smoothed, mirror, drange, precision, **metric_kwargs):
+        super(_NeighbourSheet, self).__init__(ticks, smoothed, precision)
+        self.k = _int_in(k, 1, None, 'k must be a positive integer, got %r' % (k,))
+        if int(num_samples) != num_samples or int(num_samples) < self.k + 1:
+            raise ValueError('num_samples = %r: the sheet shows k + 1 = %d samples' % (num_samples, self.k + 1))
+        self.dataset, self.sample_fn, self.num_samples = dataset, sample_fn, int(num_samples)
+        self.postprocessors = postprocessors
+        self.mirror = bool(getattr(dataset, 'mirror_augment', False)) if mirror is None else bool(mirror)
+        self.drange, self.metric_kwargs = drange, metric_kwargs
+
+    def evaluate(self, tick):
+        import torch
+        from .utils import run_postprocessors
+        nn = self.cached('all stages', lambda: getattr(metrics, self.metric)(self.dataset, k=self.k, mirror=self.mirror, drange=self.drange,
+                                                                            **self.metric_kwargs))
+        samples = self.generator().forward(self.sample_fn(self.num_samples).cuda())
+        res = nn.search(samples)
+        nearest = res['rms'][:, 0].numpy()                                 # fp64 on the host
+        self.stat(self.stat_prefix + 'rms', float(nearest.mean()))
+        self.stat(self.stat_prefix + 'rms_min', float(nearest.min()))
+        if not self.postprocessors:
+            return
+        rows = self.k + 1
+        near = nn.neighbours({name: res[name][:rows] for name in self.fields})                    # [rows, k, C, r, r]
+        shown = samples[:rows].to(near.device)
+        batch = torch.cat([shown.unsqueeze(1), near], dim=1).reshape((rows * rows,) + tuple(shown.shape[1:]))
+        run_postprocessors(batch, '%s%06d' % (self.sheet_prefix, self.trainer.cur_nimg // 1000), self.postprocessors)
+
+
+class NNMonitor(_NeighbourSheet):
     """Novelty check per tick (``metrics.NearestNeighbours``; the reference reports none): every ``nn_ticks`` ticks and at the end,
     ``num_samples`` images of ``G.forward(sample_fn(num_samples).cuda())`` -- of the smoothed generator when the trainer keeps one
     (``smoothed`` as in ``Evaluation``) -- are searched for their ``k`` nearest training images in ``dataset`` (a
@@ -480,39 +522,14 @@ class NNMonitor(Evaluation):
 
     ``precision``: 'fp32' (default) or 'bf16', as in ``Evaluation``."""
 
+    metric, stat_prefix, sheet_prefix, fields = 'NearestNeighbours', 'nn_', 'nn_', ('index', 'mirrored')
+
     def __init__(self, dataset, sample_fn, num_samples=64, k=3, nn_ticks=10, postprocessors=(), smoothed=None, mirror=None,
                  drange=(-1, 1), precision='fp32'):
-        super(NNMonitor, self).__init__(nn_ticks, smoothed, precision)
-        if isinstance(k, bool) or int(k) != k or int(k) < 1:
-            raise ValueError('k must be a positive integer, got %r' % (k,))
-        if int(num_samples) != num_samples or int(num_samples) < int(k) + 1:
-            raise ValueError('num_samples = %r: the sheet shows k + 1 = %d samples' % (num_samples, int(k) + 1))
-        self.dataset, self.sample_fn = dataset, sample_fn
-        self.num_samples, self.k = int(num_samples), int(k)
-        self.postprocessors = postprocessors
-        self.mirror = bool(getattr(dataset, 'mirror_augment', False)) if mirror is None else bool(mirror)
-        self.drange = drange
-
-    def evaluate(self, tick):
-        import torch
-        from .metrics import NearestNeighbours
-        from .utils import run_postprocessors
-        nn = self.cached('all stages', lambda: NearestNeighbours(self.dataset, k=self.k, mirror=self.mirror, drange=self.drange))
-        samples = self.generator().forward(self.sample_fn(self.num_samples).cuda())
-        res = nn.search(samples)
-        nearest = res['rms'][:, 0].numpy()                                 # fp64 on the host
-        self.stat('nn_rms', float(nearest.mean()))
-        self.stat('nn_rms_min', float(nearest.min()))
-        if not self.postprocessors:
-            return
-        rows = self.k + 1
-        near = nn.neighbours({name: res[name][:rows] for name in ('index', 'mirrored')})          # [rows, k, C, r, r]
-        shown = samples[:rows].to(near.device)
-        batch = torch.cat([shown.unsqueeze(1), near], dim=1).reshape((rows * rows,) + tuple(shown.shape[1:]))
-        run_postprocessors(batch, 'nn_%06d' % (self.trainer.cur_nimg // 1000), self.postprocessors)
+        super(NNMonitor, self).__init__(nn_ticks, dataset, sample_fn, num_samples, k, postprocessors, smoothed, mirror, drange, precision)
 
 
-class ShiftNNMonitor(Evaluation):
+class ShiftNNMonitor(_NeighbourSheet):
     """``NNMonitor`` for strip data sets (``metrics.ShiftNearestNeighbours``): every ``nn_ticks`` ticks and at the end, ``num_samples``
     generated images are searched for their ``k`` nearest training windows over EVERY start column of the recordings of ``dataset`` (a
     ``DeviceStripDataset``; the level of the current growth stage is searched), not only the non-overlapping windows ``NNMonitor``
@@ -534,40 +551,46 @@ class ShiftNNMonitor(Evaluation):
 
     ``precision``: 'fp32' (default) or 'bf16', as in ``Evaluation``."""
 
+    metric, stat_prefix, sheet_prefix, fields = 'ShiftNearestNeighbours', 'nn_shift_', 'nnshift_', ('strip', 'start', 'mirrored')
+
     def __init__(self, dataset, sample_fn, num_samples=64, k=3, nn_ticks=20, postprocessors=(), smoothed=None, mirror=None,
                  drange=(-1, 1), precision='fp32', seg=None):
-        super(ShiftNNMonitor, self).__init__(nn_ticks, smoothed, precision)
-        if isinstance(k, bool) or int(k) != k or int(k) < 1:
-            raise ValueError('k must be a positive integer, got %r' % (k,))
-        if int(num_samples) != num_samples or int(num_samples) < int(k) + 1:
-            raise ValueError('num_samples = %r: the sheet shows k + 1 = %d samples' % (num_samples, int(k) + 1))
+        super(ShiftNNMonitor, self).__init__(nn_ticks, dataset, sample_fn, num_samples, k, postprocessors, smoothed, mirror, drange, precision,
+                                             seg=seg)
+        self.seg = seg
+
+
+class _FittedSamples(Evaluation):
+    """What ``NDBMonitor`` and ``PRDMonitor`` share: one metric object for all stages, fitted on ``dataset`` again when the stage's
+    resolution differs from the fitted one, then fed ``num_samples`` generated images ``minibatch`` at a time.  A subclass writes
+    ``make_metric()`` (a ``fit()`` / ``reset()`` / ``feed()`` / ``result()`` metric with ``resolution``) and ``write_stats(result)``."""
+
+    def __init__(self, ticks, dataset, sample_fn, num_samples, minibatch, smoothed, precision):
+        super(_FittedSamples, self).__init__(ticks, smoothed, precision)
+        if int(num_samples) < 1 or int(minibatch) < 1:
+            raise ValueError('num_samples and minibatch must be positive')
         self.dataset, self.sample_fn = dataset, sample_fn
-        self.num_samples, self.k = int(num_samples), int(k)
-        self.postprocessors = postprocessors
-        self.mirror = bool(getattr(dataset, 'mirror_augment', False)) if mirror is None else bool(mirror)
-        self.drange, self.seg = drange, seg
+        self.num_samples, self.minibatch = int(num_samples), int(minibatch)
+
+    def _stage_resolution(self):
+        stage = getattr(self.dataset, '_stage', None)
+        if stage is None:
+            return int(self.dataset.level_stack().shape[-1])
+        _, shift, depthdiff = stage()                                        # (no level is made for the answer)
+        return int(self.dataset.shape[-1]) >> (shift + depthdiff)
 
     def evaluate(self, tick):
-        import torch
-        from .metrics import ShiftNearestNeighbours
-        from .utils import run_postprocessors
-        nn = self.cached('all stages', lambda: ShiftNearestNeighbours(self.dataset, k=self.k, mirror=self.mirror, drange=self.drange,
-                                                                      seg=self.seg))
-        samples = self.generator().forward(self.sample_fn(self.num_samples).cuda())
-        res = nn.search(samples)
-        nearest = res['rms'][:, 0].numpy()                                 # fp64 on the host
-        self.stat('nn_shift_rms', float(nearest.mean()))
-        self.stat('nn_shift_rms_min', float(nearest.min()))
-        if not self.postprocessors:
-            return
-        rows = self.k + 1
-        near = nn.neighbours({name: res[name][:rows] for name in ('strip', 'start', 'mirrored')})   # [rows, k, C, r, r]
-        shown = samples[:rows].to(near.device)
-        batch = torch.cat([shown.unsqueeze(1), near], dim=1).reshape((rows * rows,) + tuple(shown.shape[1:]))
-        run_postprocessors(batch, 'nnshift_%06d' % (self.trainer.cur_nimg // 1000), self.postprocessors)
+        metric = self.cached('all stages', self.make_metric)
+        if metric.resolution != self._stage_resolution():
+            metric.fit()                                                     # (once per stage: the fit is retaken, the object stays)
+        metric.reset()
+        gen = self.generator()
+        for n in _batches(self.num_samples, self.minibatch):
+            metric.feed(gen.forward(self.sample_fn(n).cuda()))
+        self.write_stats(metric.result())
 
 
-class NDBMonitor(Evaluation):
+class NDBMonitor(_FittedSamples):
     """Mode-coverage metric per tick (``metrics.NDB``: NDB/k and the JS divergence over k-means bins of the training images; the
     reference reports none): every ``ndb_ticks`` ticks and at the end, ``num_samples`` images of ``G.forward(sample_fn(n).cuda())``,
     ``minibatch`` at a time -- of the smoothed generator when the trainer keeps one (``smoothed`` as in ``Evaluation``) -- are counted
@@ -591,37 +614,21 @@ class NDBMonitor(Evaluation):
 
     def __init__(self, dataset, sample_fn, num_samples=8192, minibatch=16, k=50, holdout=None, ndb_ticks=850, smoothed=None,
                  precision='fp32', **metric_kwargs):
-        super(NDBMonitor, self).__init__(ndb_ticks, smoothed, precision)
-        if int(num_samples) < 1 or int(minibatch) < 1:
-            raise ValueError('num_samples and minibatch must be positive')
-        self.dataset, self.sample_fn = dataset, sample_fn
-        self.num_samples, self.minibatch, self.k = int(num_samples), int(minibatch), k
+        super(NDBMonitor, self).__init__(ndb_ticks, dataset, sample_fn, num_samples, minibatch, smoothed, precision)
+        self.k = k
         self.holdout = min(len(dataset) // 5, self.num_samples) if holdout is None else holdout
         self.metric_kwargs = metric_kwargs
 
-    def _stage_resolution(self):
-        stage = getattr(self.dataset, '_stage', None)
-        if stage is None:
-            return int(self.dataset.level_stack().shape[-1])
-        _, shift, depthdiff = stage()                                        # (no level is made for the answer)
-        return int(self.dataset.shape[-1]) >> (shift + depthdiff)
+    def make_metric(self):
+        return metrics.NDB(self.dataset, k=self.k, holdout=self.holdout, **self.metric_kwargs)
 
-    def evaluate(self, tick):
-        from .metrics import NDB
-        metric = self.cached('all stages', lambda: NDB(self.dataset, k=self.k, holdout=self.holdout, **self.metric_kwargs))
-        if metric.resolution != self._stage_resolution():
-            metric.fit()                                                     # (once per stage: the bins are refitted, the object stays)
-        metric.reset()
-        gen = self.generator()
-        for start in range(0, self.num_samples, self.minibatch):
-            metric.feed(gen.forward(self.sample_fn(min(self.minibatch, self.num_samples - start)).cuda()))
-        res = metric.result()
+    def write_stats(self, res):
         self.stat('ndb', res['ndb'], '{val:d}')
         self.stat('ndb_over_k', res['ndb_over_k'], '{val:.3f}')
         self.stat('jsd', res['jsd'], '{val:.4f}')
 
 
-class PRDMonitor(Evaluation):
+class PRDMonitor(_FittedSamples):
     """Fidelity and coverage per tick as separate numbers (``metrics.PrecisionRecall``: improved precision and recall over k-NN balls
     with density and coverage, in uint8 image space; the reference reports none): every ``prd_ticks`` ticks and at the end,
     ``num_samples`` images of ``G.forward(sample_fn(n).cuda())``, ``minibatch`` at a time -- of the smoothed generator when the trainer
@@ -652,33 +659,15 @@ class PRDMonitor(Evaluation):
 
     def __init__(self, dataset, sample_fn, num_samples=4096, minibatch=16, k=3, prd_ticks=450, smoothed=None, precision='fp32',
                  **metric_kwargs):
-        super(PRDMonitor, self).__init__(prd_ticks, smoothed, precision)
-        if int(num_samples) < 1 or int(minibatch) < 1:
-            raise ValueError('num_samples and minibatch must be positive')
-        if isinstance(k, bool) or int(k) != k or not 1 <= k < int(num_samples):
-            raise ValueError('k = %r for %d samples (the radii of the samples need k + 1 of them)' % (k, num_samples))
-        self.dataset, self.sample_fn = dataset, sample_fn
-        self.num_samples, self.minibatch, self.k = int(num_samples), int(minibatch), int(k)
+        super(PRDMonitor, self).__init__(prd_ticks, dataset, sample_fn, num_samples, minibatch, smoothed, precision)
+        self.k = _int_in(k, 1, self.num_samples - 1, 'k = %r for %d samples (the radii of the samples need k + 1 of them)' % (k, num_samples))
         self.metric_kwargs = dict(metric_kwargs)
         self.metric_kwargs.setdefault('max_resolution', 256)
 
-    def _stage_resolution(self):
-        stage = getattr(self.dataset, '_stage', None)
-        if stage is None:
-            return int(self.dataset.level_stack().shape[-1])
-        _, shift, depthdiff = stage()                                        # (no level is made for the answer)
-        return int(self.dataset.shape[-1]) >> (shift + depthdiff)
+    def make_metric(self):
+        return metrics.PrecisionRecall(self.dataset, k=self.k, **self.metric_kwargs)
 
-    def evaluate(self, tick):
-        from .metrics import PrecisionRecall
-        metric = self.cached('all stages', lambda: PrecisionRecall(self.dataset, k=self.k, **self.metric_kwargs))
-        if metric.resolution != self._stage_resolution():
-            metric.fit()                                                     # (once per stage: reals and radii are retaken, the object stays)
-        metric.reset()
-        gen = self.generator()
-        for start in range(0, self.num_samples, self.minibatch):
-            metric.feed(gen.forward(self.sample_fn(min(self.minibatch, self.num_samples - start)).cuda()))
-        res = metric.result()
+    def write_stats(self, res):
         for name in ('precision', 'recall', 'density', 'coverage'):
             self.stat(name, res[name], '{val:.3f}')
 
@@ -715,10 +704,8 @@ class ProjectionMonitor(Evaluation):
         if precision != 'fp32':
             raise ValueError("ProjectionMonitor(precision=%r): the projection needs the generator's backward sweep, which the bf16 "
                              "sampler does not have; only 'fp32' is taken" % (precision,))
-        if isinstance(num_images, bool) or int(num_images) != num_images or int(num_images) < 1:
-            raise ValueError('num_images must be a positive integer, got %r' % (num_images,))
-        if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
-            raise ValueError('steps must be a positive integer, got %r' % (steps,))
+        num_images = _int_in(num_images, 1, None, 'num_images must be a positive integer, got %r' % (num_images,))
+        steps = _int_in(steps, 1, None, 'steps must be a positive integer, got %r' % (steps,))
         if not callable(source) and not (hasattr(source, 'items') and hasattr(source, '__len__')):
             raise ValueError('ProjectionMonitor: source must be a device dataset or a function n -> real batch, got %s' % type(source).__name__)
         if not callable(source) and len(source) < int(num_images):
