@@ -858,6 +858,7 @@ class _DForwardBuffers(object):
     def __init__(self):
         self.arena = ops.Arena()
         self.x3 = None
+        self.g_out = None                   # [N,C,r,r] scratch G(z) is written to when the step augments (the fake third is its augmented form)
         self.key = None
         self.owner = None                   # weakref to the _ArenaUse token of the D-loss state whose activations live in these buffers
 
@@ -1217,13 +1218,14 @@ def _assign_grads(net, layers, linear=False):
 REAL_THIRD_IN_STEP = True      # False: reference half of tests/test_e2e_gpu.py::test_three_pass_d_forward_matches_whole_batch_forward
 
 
-class Objective(_collections.namedtuple('Objective', 'kind drift penalty weight target family', defaults=('pinned',))):
+class Objective(_collections.namedtuple('Objective', 'kind drift penalty weight target family augment', defaults=('pinned', None))):
     """What the loss block of a step computes: ``kind`` a key of ``ops.GAN_KINDS``, ``drift`` the weight of the
     s_r^2 term, ``penalty`` 'gp' | 'r1' | None with its ``weight`` (lambda / gamma) and, for 'gp', the ``target`` norm.  ``family`` names
     the kernels of the loss block: 'pinned' (csrc/gan_losses.hip, every rounding spelled out: what ``gan_losses`` builds) or 'original'
     (``pg_d_loss`` / ``pg_g_loss`` of csrc/elementwise.hip, contraction left to the compiler: WGAN-GP as ``wgan_gp_D_loss`` /
     ``wgan_gp_G_loss`` state it, kind 'wgan' with penalty 'gp' only).  The two are not bit-equal, so the family stays a property of the
-    objective.  Immutable and hashable: it is part of the key of a launch plan."""
+    objective.  ``augment``: the ``augment.Augmenter`` every image D sees goes through (None: none, and not one launch differs), hashed
+    by identity -- a plan bakes in the address of its accumulator.  Immutable and hashable: it is part of the key of a launch plan."""
     __slots__ = ()
 
 
@@ -1246,17 +1248,44 @@ def _penalty_seed(obj, gimg, ss, N):
     return ops.gp_seed(gimg, ss, obj.weight, obj.target, 1.0 / N)        # :29-31
 
 
-def d_loss_forward(D, G, real, latents, mix, objective):
+def _augmented(aug, x, table, out=None):
+    """``x`` as D sees it under the Augmenter ``aug``: rows of ``table`` applied image by image (one launch on the current stream)."""
+    return ops.augment_apply(x, table, aug.channel_mask, out=out)
+
+
+def _step_table(objective, table, rows):
+    """The parameter table of a step of ``objective``: None without an Augmenter, else ``table`` [rows, 8] int32 (a missing one is an error:
+    the tables are drawn eagerly by the caller, wgan_gp_loss._d_loss / _g_loss, never inside a schedule)."""
+    if objective.augment is None:
+        if table is not None:
+            raise ValueError('an augmentation table for an objective without an Augmenter')
+        return None
+    if table is None or tuple(table.shape) != (rows, ops.AUGMENT_COLS):
+        raise ValueError('an objective with an Augmenter needs a table of %d rows (got %s)' % (rows, None if table is None else tuple(table.shape)))
+    return table
+
+
+def _count_real_signs(aug, s, N):
+    """With a controller attached: the signs of the real scores into the Augmenter's accumulator, behind the loss block on this stream."""
+    if aug is not None and aug.controller is not None:
+        ops.score_signs(s[:N], aug.acc)
+
+
+def d_loss_forward(D, G, real, latents, mix, objective, table=None):
     """Forward half of a D loss (wgan_gp_loss.py:36-65): three D passes batched as [real | fake | mixed], G without graph, and the first
     backward of the gradient penalty, with the loss block and the penalty seed of ``objective``.  R1 is the penalty at ``mix`` == 0, i.e.
-    at the real images; an objective without a penalty takes one pass over [real | fake] (``_d_plain_loss_forward``; ``mix`` is not read)."""
+    at the real images; an objective without a penalty takes one pass over [real | fake] (``_d_plain_loss_forward``; ``mix`` is not read).
+    With ``objective.augment``: ``table`` [2N, 8] (reals, then fakes) -- the real third is the augmented real batch (in the place of the
+    copy), the generator writes to a scratch tensor whose augmented form is the fake third; everything behind the two is untouched, so the
+    penalty is taken at augmented images."""
     if objective.penalty is None:
-        return _d_plain_loss_forward(D, G, real, latents, objective)
+        return _d_plain_loss_forward(D, G, real, latents, objective, table)
     ops.require_gpu()
     real = _check_dev(real, 'real images')
     latents = _check_dev(latents, 'latents')
     mix = _check_dev(mix, 'mixing factors').view(-1)
     N = real.shape[0]
+    aug, table = objective.augment, _step_table(objective, table, 2 * real.shape[0])
     D._sync_version()
     fake_done = None
     arena_st = None
@@ -1272,18 +1301,29 @@ def d_loss_forward(D, G, real, latents, mix, objective):
         step_start = torch.cuda.Event()
         _record_event(step_start, main)                                       # (everything the previous step left on the main stream)
         probe('D.start')
-        d_step_generator(D, G, latents, x3[N:2 * N])                        # :51-52  -- issued first: the host feeds the critical path before the side work
+        if aug is None:
+            d_step_generator(D, G, latents, x3[N:2 * N])                    # :51-52  -- issued first: the host feeds the critical path before the side work
+        else:                                                                 # (G(z) into the buffers' scratch, its augmented form into the fake third: on the generator's stream, ahead of the edges that release it)
+            if st.g_out is None:
+                st.g_out = torch.empty_like(x3[:N])
+            d_step_generator(D, G, latents, st.g_out)
+            _augmented(aug, st.g_out, table[N:], out=x3[N:2 * N])
         probe('D.g_fwd_end')
         with torch.cuda.stream(side):
             _wait_event(side, step_start)
             probe('D.side_start')
-            ops.axpby_mask(real, a=1.0, out=x3[:N])                           # (the copy into the batched image buffer too, so that the generator starts at once: -0.03 ms)
+            if aug is None:
+                ops.axpby_mask(real, a=1.0, out=x3[:N])                       # (the copy into the batched image buffer too, so that the generator starts at once: -0.03 ms)
+            else:
+                _augmented(aug, real, table[:N], out=x3[:N])                  # (in the copy's place)
             real_copied = torch.cuda.Event()
             _record_event(real_copied, side)
             with st.arena.pass_(0):
                 s_r, ctx_r = d_forward(D, x3[:N], groups=1)                   # :47
             probe('D.real_end')
         real.record_stream(side)
+        if aug is not None:
+            table.record_stream(side)                                         # (read by the real third's gather on that stream)
         _wait_stream(side, main)
         with torch.cuda.stream(side):
             probe('D.fake_start')
@@ -1303,8 +1343,12 @@ def d_loss_forward(D, G, real, latents, mix, objective):
         s = s_r._base if s_r._base is not None else s_r
     else:
         x3 = torch.empty((3 * N,) + tuple(real.shape[1:]), device=real.device, dtype=torch.float32)
-        ops.axpby_mask(real, a=1.0, out=x3[:N])                               # device copy (plumbing; a C-ABI launch so that plans.py records it)
-        d_step_generator(D, G, latents, x3[N:2 * N])                        # :51-52  (no graph kept)
+        if aug is None:
+            ops.axpby_mask(real, a=1.0, out=x3[:N])                           # device copy (plumbing; a C-ABI launch so that plans.py records it)
+            d_step_generator(D, G, latents, x3[N:2 * N])                    # :51-52  (no graph kept)
+        else:
+            _augmented(aug, real, table[:N], out=x3[:N])
+            _augmented(aug, d_step_generator(D, G, latents, torch.empty_like(real)), table[N:], out=x3[N:2 * N])
         ops.gp_mix(x3[:N], x3[N:2 * N], mix, out=x3[2 * N:])                  # :19
         s, ctx = d_forward(D, x3, groups=3)                                   # :47,54,20
     sub = ctx.slice(2 * N, 3 * N, 2, 3)
@@ -1315,6 +1359,7 @@ def d_loss_forward(D, G, real, latents, mix, objective):
     if fake_done is not None:
         _wait_event(torch.cuda.current_stream(torch._C._cuda_getDevice()), fake_done)
     d_cost, d_real_loss, d_fake_loss, gscore = _d_loss_block(objective, s, gp, N)
+    _count_real_signs(aug, s, N)
     probe('D.loss_end')
     state = saved.DLossState(D=D, ctx=ctx, sub=sub, adj=adj, u=u, gscore=gscore, N=N, scores=s, gp=gp)
     if arena_st is not None:
@@ -1496,26 +1541,34 @@ def d_loss_backward(state, scale=1.0):
     _backward(D, scale, sweep, ('D.sweep_end', 'D.wgrad_end'), linear=True, may_skip_join=True)
 
 
-def _d_plain_loss_forward(D, G, real, latents, objective):
+def _d_plain_loss_forward(D, G, real, latents, objective, table=None):
     """The D step of an objective without a penalty: ONE whole-batch pass over [real | fake], then the loss block.  No mixed third, no
-    first backward, no tangent pass."""
+    first backward, no tangent pass.  ``table``: as in ``d_loss_forward``."""
     ops.require_gpu()
     real = _check_dev(real, 'real images')
     latents = _check_dev(latents, 'latents')
     N = real.shape[0]
+    aug, table = objective.augment, _step_table(objective, table, 2 * real.shape[0])
     D._sync_version()
     x2 = torch.empty((2 * N,) + tuple(real.shape[1:]), device=real.device, dtype=torch.float32)
-    ops.axpby_mask(real, a=1.0, out=x2[:N])
-    d_step_generator(D, G, latents, x2[N:])
+    if aug is None:
+        ops.axpby_mask(real, a=1.0, out=x2[:N])
+        d_step_generator(D, G, latents, x2[N:])
+    else:
+        _augmented(aug, real, table[:N], out=x2[:N])
+        _augmented(aug, d_step_generator(D, G, latents, torch.empty_like(real)), table[N:], out=x2[N:])
     s, ctx = d_forward(D, x2, groups=2)
     d_cost, d_real_loss, d_fake_loss, gscore = _d_loss_block(objective, s, None, N)
+    _count_real_signs(aug, s, N)
     return d_cost, d_real_loss, d_fake_loss, saved.DLossState(D=D, ctx=ctx, gscore=gscore, N=N, scores=s)
 
 
-def g_loss_forward(G, D, latents, objective):
-    """wgan_gp_G_loss (wgan_gp_loss.py:68-74) with the generator term of ``objective`` (-s for the 'wgan' kind)."""
+def g_loss_forward(G, D, latents, objective, table=None):
+    """wgan_gp_G_loss (wgan_gp_loss.py:68-74) with the generator term of ``objective`` (-s for the 'wgan' kind).  With
+    ``objective.augment``: D scores the fakes augmented by ``table`` [N, 8], which the state keeps for the transpose in the backward."""
     ops.require_gpu()
     latents = _check_dev(latents, 'latents')
+    table = _step_table(objective, table, latents.shape[0])
     D._sync_version()
     G._sync_version()
     probe('G.start')
@@ -1525,10 +1578,12 @@ def g_loss_forward(G, D, latents, objective):
     else:
         fake, gctx = generator_forward(G, latents, save=True)
     probe('G.g_fwd_end')
+    if table is not None:
+        fake = _augmented(objective.augment, fake, table)
     s, dctx = d_forward(D, fake, 1, keep_input=False)
     g_cost, gscore = _g_loss_block(objective, s)
     probe('G.d_fwd_end')
-    return g_cost, saved.GLossState(G=G, D=D, gctx=gctx, dctx=dctx, gscore=gscore)
+    return g_cost, saved.GLossState(G=G, D=D, gctx=gctx, dctx=dctx, gscore=gscore, table=table)
 
 
 def g_loss_backward(state, scale=1.0):
@@ -1538,6 +1593,8 @@ def g_loss_backward(state, scale=1.0):
 
     def sweep():
         gimg, _ = d_backward(D, state.dctx, state.gscore, full=False, want_gimg=True)
+        if state.table is not None:
+            gimg = ops.augment_adjoint(gimg, state.table)     # back through the augmentation: the same table, the exact transpose
         probe('G.d_bwd_end')
         return generator_backward(G, state.gctx, gimg)
     state.active_g = _backward(G, scale, sweep, ('G.g_bwd_end', 'G.wgrad_end'))

@@ -9,16 +9,23 @@ penalty the step is one pass over [real | fake] and runs eagerly.  Both function
 dispatcher of wgan_gp_loss.py, which WGAN-GP on the original kernels takes too: the objective (``engine.Objective``) is all that differs.
 
 ``gan_losses('wgan', penalty='gp')`` with default arguments IS the pair ``(wgan_gp_D_loss, wgan_gp_G_loss)``: Trainer's deferred D
-update and early generator pass are keyed to those two objects and stay with them."""
+update and early generator pass are keyed to those two objects and stay with them.
+
+``augment=`` an ``augment.Augmenter``: everything D sees goes through it -- reals and fakes in the D step, fakes in the G step, whose
+gradient returns through the transpose -- and the pair is ALWAYS a pair of new closures, on the 'pinned' kernels."""
 from . import engine, ops, wgan_gp_loss
 
 PENALTIES = ('gp', 'r1', None)
 
 
-def gan_losses(kind='wgan', penalty='gp', penalty_weight=10.0, drift=None, gp_target=1.0):
+SIGN_KINDS = ('logistic', 'hinge')     # the kinds whose decision boundary is score 0: what plugins.AugmentController may steer by
+
+
+def gan_losses(kind='wgan', penalty='gp', penalty_weight=10.0, drift=None, gp_target=1.0, augment=None):
     """``(D_loss, G_loss)`` of the objective.  ``penalty_weight``: lambda of 'gp', gamma of 'r1'; ``drift``: weight of the s_r^2 term
-    (default 0.001 for 'wgan', 0 otherwise); ``gp_target``: the target norm of 'gp'.  ValueError for an unknown name, a non-positive
-    weight or target, a negative drift."""
+    (default 0.001 for 'wgan', 0 otherwise); ``gp_target``: the target norm of 'gp'; ``augment``: an ``augment.Augmenter`` or None.
+    ValueError for an unknown name, a non-positive weight or target, a negative drift, an Augmenter with a controller attached under a
+    kind whose real scores do not sit around a boundary at 0 ('wgan', 'lsgan': those run with a fixed ``p``)."""
     if kind not in ops.GAN_KINDS:
         raise ValueError('gan_losses: kind %r (one of %s)' % (kind, ', '.join(sorted(ops.GAN_KINDS))))
     if penalty not in PENALTIES:
@@ -32,9 +39,17 @@ def gan_losses(kind='wgan', penalty='gp', penalty_weight=10.0, drift=None, gp_ta
         raise ValueError('gan_losses: gp_target %r must be positive' % gp_target)
     if not drift >= 0.0:
         raise ValueError('gan_losses: drift %r must not be negative' % drift)
-    if (kind, drift, penalty, penalty_weight, gp_target) == engine.WGAN_GP[:5]:
+    if augment is None and (kind, drift, penalty, penalty_weight, gp_target) == engine.WGAN_GP[:5]:
         return wgan_gp_loss.wgan_gp_D_loss, wgan_gp_loss.wgan_gp_G_loss
-    obj = engine.Objective(kind, drift, penalty, penalty_weight, gp_target)
+    if augment is not None:
+        from .augment import Augmenter
+        if not isinstance(augment, Augmenter):
+            raise ValueError('gan_losses: augment %r is not an Augmenter' % (augment,))
+        if augment.controller is not None and kind not in SIGN_KINDS:
+            raise ValueError('gan_losses: the Augmenter is steered by an AugmentController, which reads the sign of the real scores: '
+                             "valid for %s, not for %r (run it with a fixed p)" % (' and '.join(SIGN_KINDS), kind))
+        augment.kind = kind                                              # (what a controller attached later is checked against)
+    obj = engine.Objective(kind, drift, penalty, penalty_weight, gp_target, augment=augment)
 
     def D_loss(D, G, real_images_in, fake_latents_in, return_all=True):
         return wgan_gp_loss._d_loss(obj, D, G, real_images_in, fake_latents_in, return_all)

@@ -21,6 +21,7 @@ class _Graphed(object):
         self.graph = None
         self.static_in = None
         self.static_out = None
+        self.static_table = None      # int32 [rows, 8]: the step's augmentation table (objective.augment), rewritten before every replay
         self.keep = None
         self.warm = 0
 
@@ -33,19 +34,32 @@ def clear():
     ops.release_capture_workspaces()          # the capture streams are gone with the graphs
 
 
-def d_step(D, G, real, latents, mix, objective):
+def _static_table(g, table):
+    if table is not None:
+        if g.static_table is None:
+            g.static_table = torch.empty_like(table)
+        g.static_table.copy_(table)
+    return g.static_table
+
+
+def _aug_tag(objective):
+    return objective.augment is not None and objective.augment.controller is not None      # (the controller's sign count is a captured launch)
+
+
+def d_step(D, G, real, latents, mix, objective, table=None):
     """Graphed ``d_loss_forward`` + ``d_loss_backward``.  Returns (d_cost, d_real_loss, d_fake_loss).  ``objective`` (engine.Objective with a
-    penalty) is part of the graph's key."""
-    key = ('D', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(D.depth), tuple(real.shape), tuple(latents.shape), objective)
+    penalty) is part of the graph's key.  ``table``: the step's augmentation table (``objective.augment``), a static input like ``mix``."""
+    key = ('D', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(D.depth), tuple(real.shape), tuple(latents.shape), objective, _aug_tag(objective))
     g = _CACHE.get(key)
     if g is None:
         g = _CACHE[key] = _Graphed()
         g.static_in = (torch.empty_like(real), torch.empty_like(latents), torch.empty_like(mix))
     for dst, src in zip(g.static_in, (real, latents, mix)):
         dst.copy_(src)
+    table = _static_table(g, table)
     if g.graph is None:
         def body():
-            c, rl, fl, state = engine.d_loss_forward(D, G, g.static_in[0], g.static_in[1], g.static_in[2], objective)
+            c, rl, fl, state = engine.d_loss_forward(D, G, g.static_in[0], g.static_in[1], g.static_in[2], objective, table)
             engine.d_loss_backward(state)
             return c, rl, fl
         if g.warm < 2:                       # eager warm-up (sets kernel attributes, fills caches, allocator pools)
@@ -69,17 +83,18 @@ def d_step(D, G, real, latents, mix, objective):
     return tuple(t.clone() for t in g.static_out)
 
 
-def g_step(G, D, latents, objective):
-    """Graphed ``g_loss_forward`` + ``g_loss_backward``.  Returns g_cost.  ``objective``: as in ``d_step``."""
+def g_step(G, D, latents, objective, table=None):
+    """Graphed ``g_loss_forward`` + ``g_loss_backward``.  Returns g_cost.  ``objective``, ``table``: as in ``d_step``."""
     key = ('G', D._flat_param.data_ptr(), G._flat_param.data_ptr(), int(G.depth), tuple(latents.shape), objective)
     g = _CACHE.get(key)
     if g is None:
         g = _CACHE[key] = _Graphed()
         g.static_in = (torch.empty_like(latents),)
     g.static_in[0].copy_(latents)
+    table = _static_table(g, table)
     if g.graph is None:
         def body():
-            c, state = engine.g_loss_forward(G, D, g.static_in[0], objective)
+            c, state = engine.g_loss_forward(G, D, g.static_in[0], objective, table)
             engine.g_loss_backward(state)
             return c, state.active_g
         if g.warm < 2:

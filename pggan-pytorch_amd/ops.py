@@ -1716,3 +1716,55 @@ def pyramid_loss(img, target, weights=None, want_grad=True, scratch=None):
     _lib.call('pg_pyr_loss_grad', img.data_ptr(), target.data_ptr(), ctypes.cast(wbuf, ctypes.c_void_p) if wbuf is not None else None, nlev,
               grad.data_ptr() if grad is not None else None, loss.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, N, C, r, _stream())
     return loss, grad
+
+
+# ------------------------------------------------------------------------- differentiable augmentation of D's inputs (csrc/augment.hip)
+AUGMENT = {name[len('PG_AUGMENT_'):]: value for name, value in _lib.AUGMENT_CONSTANTS.items() if name.startswith('PG_AUGMENT_')}   # the addition's own table
+AUGMENT_COLS, AUGMENT_FLIP, AUGMENT_GAIN = AUGMENT['COLS'], AUGMENT['FLIP'], AUGMENT['GAIN']
+AUGMENT_MAX_SIZE, AUGMENT_MAX_SCORES = AUGMENT['MAX_SIZE'], AUGMENT['MAX_SCORES']
+
+
+def _augment_table(table, n, what):
+    if (not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.int32 or not table.is_contiguous()
+            or tuple(table.shape) != (n, AUGMENT_COLS)):
+        raise ValueError('%s: the table must be a contiguous int32 device tensor [%d, %d]' % (what, n, AUGMENT_COLS))
+    return table.data_ptr()
+
+
+def augment_apply(x, table, channel_mask=0, out=None):
+    """``out[n]`` = image ``x[n]`` [C,H,W] flipped, shifted with zero padding, cut out and (channels of ``channel_mask``) raised by the
+    gain, as row ``n`` of the int32 ``table`` [N,8] says (pg_augment_apply; include/pggan_hip_augment.h has the definition).  One launch
+    on the current stream, every element of ``out`` written."""
+    y = out if out is not None else torch.empty_like(x)
+    N, C, H, W = x.shape
+    _lib.call('pg_augment_apply', _p(x), _augment_table(table, N, 'augment_apply'), _p(y), N, C, H, W, int(channel_mask), _stream())
+    return y
+
+
+def augment_adjoint(gy, table, out=None):
+    """The exact transpose of ``augment_apply`` under the same ``table``: ``gx[p] = gy[q]`` for the one output pixel q whose source is p,
+    +0.0 where there is none or q lies in the cutout (pg_augment_adjoint)."""
+    gx = out if out is not None else torch.empty_like(gy)
+    N, C, H, W = gy.shape
+    _lib.call('pg_augment_adjoint', _p(gy), _augment_table(table, N, 'augment_adjoint'), _p(gx), N, C, H, W, _stream())
+    return gx
+
+
+def augment_table(U, H, W, ry, rx, ch, cw, gain, flip, p, out=None):
+    """U[0,1) draws ``U`` [rows,8] (``uniform_``) -> the int32 parameter table [rows,8] of a policy at probability ``p`` (pg_augment_table)."""
+    if not torch.is_tensor(U) or not U.is_cuda or U.dtype != torch.float32 or not U.is_contiguous() or U.dim() != 2 or U.shape[1] != AUGMENT_COLS:
+        raise ValueError('augment_table: expected a contiguous float32 device tensor [rows, %d]' % AUGMENT_COLS)
+    rows = U.shape[0]
+    table = out if out is not None else torch.empty((rows, AUGMENT_COLS), device=U.device, dtype=torch.int32)
+    _lib.call('pg_augment_table', _p(U), rows, H, W, ry, rx, ch, cw, gain, int(bool(flip)), p, _augment_table(table, rows, 'augment_table'),
+              _stream())
+    return table
+
+
+def score_signs(scores, acc):
+    """``acc[0] += sum sign(scores)`` (sign(+-0) = 0), ``acc[1] += scores.numel()`` on the fp64 device accumulator ``acc`` [2]
+    (pg_score_signs: one workgroup, exact)."""
+    if not torch.is_tensor(acc) or not acc.is_cuda or acc.dtype != torch.float64 or not acc.is_contiguous() or acc.numel() != 2:
+        raise ValueError('score_signs: the accumulator must be a contiguous float64 device tensor of 2 elements')
+    _lib.call('pg_score_signs', _p(scores), scores.numel(), acc.data_ptr(), _stream())
+    return acc

@@ -23,7 +23,9 @@ Not in a plan: Adam and the derived-weight refresh (host scalars / version check
 the RCCL exchange (``GradExchange.finish``: what the sweep has not sent, and the join -- part of the update Trainer runs eagerly; the bucket
 collectives the sweep itself issues ARE recorded, round 6: ``pg_allreduce_sum_f32`` is a C-ABI call like any other and the edges to the
 exchange stream go through ``engine._wait_stream``), fade-in phases (a new alpha per
-iteration), the mixing-factor draw (a counter-based RNG call with a new counter per step, written into the static buffer)."""
+iteration), the mixing-factor draw (a counter-based RNG call with a new counter per step, written into the static buffer) and, with an
+Augmenter, the draw of the step's augmentation table (two launches, copied into a static buffer the same way: the table is read per step,
+so neither a new table nor a new probability ``p`` records anything)."""
 import collections
 
 import torch
@@ -39,6 +41,7 @@ class _Plan(object):
         self.keep = {}               # id -> tensor: everything whose pointer is baked into the entries
         self.static_in = None
         self.static_out = None
+        self.static_table = None     # int32 [rows, 8]: the step's augmentation table (objective.augment), rewritten before every issue
         self.dp_state = None         # (GradExchange snapshot, collectives, bytes) of the recorded step under data parallelism
         self.early_g = None          # engine.EarlyG the recorded D step leaves for the G step (its tensors are rewritten by every replay)
         self.warm = 0
@@ -199,8 +202,22 @@ def _dp_replayed(g, ex):
         ex.dp.stats['bytes'] += nbytes
 
 
-def d_step(D, G, real, latents, mix, objective):
-    """Plan-replayed ``d_loss_forward`` + ``d_loss_backward`` of ``objective`` (with a penalty).  Returns (d_cost, d_real_loss, d_fake_loss)."""
+def _aug_tag(objective):
+    """What a plan recorded with an Augmenter depends on besides its identity (part of ``objective``): whether a controller's sign count rides along."""
+    return objective.augment is not None and objective.augment.controller is not None
+
+
+def _static_table(g, table):
+    if table is not None:
+        if g.static_table is None:
+            g.static_table = torch.empty_like(table)
+        g.static_table.copy_(table)
+    return g.static_table
+
+
+def d_step(D, G, real, latents, mix, objective, table=None):
+    """Plan-replayed ``d_loss_forward`` + ``d_loss_backward`` of ``objective`` (with a penalty).  Returns (d_cost, d_real_loss, d_fake_loss).
+    ``table``: the step's augmentation table when ``objective.augment`` is set (copied into a static buffer, like ``mix``)."""
     _prologue(D, G)
     dp_tag, ex = _dp_tag(D)
     # the G step's generator pass rides in this step on the second stream (engine.request_early_g): its latents are a fourth static input
@@ -208,7 +225,7 @@ def d_step(D, G, real, latents, mix, objective):
     if req is not None and engine.early_g_mode(req[0].depth) is None:
         req = D._rt.early_g_request = None
     zg = engine._check_dev(req[1], 'latents') if req is not None else None
-    key = _key('D', D, G, (int(D.depth), tuple(real.shape), tuple(latents.shape)), (dp_tag, (req[0]._flat_param.data_ptr(), tuple(zg.shape)) if req is not None else 0, objective))
+    key = _key('D', D, G, (int(D.depth), tuple(real.shape), tuple(latents.shape)), (dp_tag, (req[0]._flat_param.data_ptr(), tuple(zg.shape)) if req is not None else 0, _aug_tag(objective), objective))
     g = _CACHE.get(key)
     if g is None:
         g = _new_plan(key)
@@ -220,6 +237,7 @@ def d_step(D, G, real, latents, mix, objective):
         D._rt.early_g_request = (req[0], g.static_in[3])
     for dst, src in zip(g.static_in, (real, latents, mix)):
         dst.copy_(src)
+    table = _static_table(g, table)
 
     def body():
         # The plan itself never joins the weight-gradient stream: whether the caller's next launch needs the join is not known
@@ -228,7 +246,7 @@ def d_step(D, G, real, latents, mix, objective):
         caller = D._rt.skip_join
         D._rt.skip_join = True
         try:
-            c, rl, fl, state = engine.d_loss_forward(D, G, g.static_in[0], g.static_in[1], g.static_in[2], objective)
+            c, rl, fl, state = engine.d_loss_forward(D, G, g.static_in[0], g.static_in[1], g.static_in[2], objective, table)
             engine.d_loss_backward(state)
         finally:
             D._rt.skip_join = caller
@@ -271,8 +289,8 @@ def d_step(D, G, real, latents, mix, objective):
     return tuple(t.clone() for t in g.static_out)
 
 
-def g_step(G, D, latents, objective):
-    """Plan-replayed ``g_loss_forward`` + ``g_loss_backward``.  Returns g_cost.  ``objective``: as in ``d_step``."""
+def g_step(G, D, latents, objective, table=None):
+    """Plan-replayed ``g_loss_forward`` + ``g_loss_backward``.  Returns g_cost.  ``objective``, ``table``: as in ``d_step``."""
     dp_tag, ex = _dp_tag(G)
     # the generator pass may already be through (engine.EarlyG, left by the D step for exactly these latents): a plan of its own, whose
     # body starts from that pass's tensors -- stable addresses: the D step's plan rewrites them at every replay
@@ -291,6 +309,7 @@ def g_step(G, D, latents, objective):
             # recorded against the tensors of another generator pass (the D step's plan was re-recorded): record again, now
             g.entries, g.keep, g.warm = None, {}, 2
     g.static_in[0].copy_(latents)
+    table = _static_table(g, table)
     if eg is not None:
         eg.latents = g.static_in[0]          # (what the body hands to g_loss_forward; identity is all take_early_g compares)
         if g.entries is not None:            # replay: the wait on the pass's event is one of the recorded entries
@@ -301,7 +320,7 @@ def g_step(G, D, latents, objective):
     _prologue(G)
 
     def body():
-        c, state = engine.g_loss_forward(G, D, g.static_in[0], objective)
+        c, state = engine.g_loss_forward(G, D, g.static_in[0], objective, table)
         engine.g_loss_backward(state)
         return c, state.active_g
     if g.entries is None:

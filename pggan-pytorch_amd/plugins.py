@@ -898,3 +898,62 @@ class HealthMonitor(Evaluation):
             if self.on_nonfinite == 'raise':
                 raise TrainingDiverged(msg)
             warnings.warn(msg, RuntimeWarning)
+
+
+class AugmentController(Plugin):
+    """Adaptive augmentation probability (Karras et al. 2020, "Training GANs with limited data"): steers ``augmenter.p`` so that the
+    overfitting signal ``r_t = E[sign(D(real))]`` stays at ``target``.  The D steps of an Augmenter with a controller count the signs of the
+    real scores into its 16-byte device accumulator (pg_score_signs, one launch behind the loss block); every ``interval`` iterations this
+    plugin reads it -- the only host synchronisation the feature adds --, forms ``r_t`` over the scores since the last read and moves
+    ``p`` by ``sign(r_t - target) * images since the last read / (1000 * adjust_kimg)``, clipped to ``[0, p_max]``: ``p`` can cross [0, 1] in
+    ``adjust_kimg`` thousand images.  ``p_max`` defaults to 0.8: above it flips and cutouts begin to leak into what G learns (DESIGN.md
+    section 7).  Writes ``augment_p`` and ``augment_rt`` into ``trainer.stats``.  A new ``p`` enters the next table draw; no plan is
+    re-recorded.  Under data parallelism every rank steers the ``p`` of its own Augmenter from its own shard's scores.
+
+    Valid for the 'logistic' and 'hinge' kinds, whose decision boundary is score 0.  Under 'wgan' and 'lsgan' the drift term pins the real
+    scores near 0 and their sign says nothing: ValueError here (an Augmenter already handed to such an objective) or in ``gan_losses``
+    (the other order); those kinds run with a fixed ``p``."""
+
+    def __init__(self, augmenter, target=0.6, adjust_kimg=500, interval=16, p_max=0.8):
+        from .augment import Augmenter
+        from .gan_losses import SIGN_KINDS
+        if not isinstance(augmenter, Augmenter):
+            raise ValueError('AugmentController: %r is not an Augmenter' % (augmenter,))
+        if augmenter.kind is not None and augmenter.kind not in SIGN_KINDS:
+            raise ValueError("AugmentController: the Augmenter belongs to a %r objective; the sign of the real scores is a signal for %s "
+                             'only (run it with a fixed p)' % (augmenter.kind, ' and '.join(SIGN_KINDS)))
+        if augmenter.controller is not None:
+            raise ValueError('AugmentController: the Augmenter already has a controller')
+        target, adjust_kimg, p_max = float(target), float(adjust_kimg), float(p_max)
+        if not -1.0 < target < 1.0:
+            raise ValueError('AugmentController: target = %r outside (-1, 1), the open range of a mean of signs' % target)
+        if not 0.0 < adjust_kimg < float('inf'):
+            raise ValueError('AugmentController: adjust_kimg = %r must be positive' % adjust_kimg)
+        if not 0.0 <= p_max <= 1.0:
+            raise ValueError('AugmentController: p_max = %r outside [0, 1]' % p_max)
+        interval = _int_in(interval, 1, None, 'AugmentController: interval')
+        super(AugmentController, self).__init__([(interval, 'iteration')])
+        self.augmenter, self.target, self.adjust_kimg, self.interval, self.p_max = augmenter, target, adjust_kimg, interval, p_max
+        self.last = None                 # (sum of signs, scores counted, trainer.cur_nimg) at the last read
+        self.r_t = float('nan')
+        augmenter.controller = self
+
+    def register(self, trainer):
+        self.trainer = trainer
+        self.last = self.augmenter.read() + (trainer.cur_nimg,)
+        self._write()
+
+    def _write(self):
+        _stat(self.trainer.stats, 'augment_p', float(self.augmenter.p), '{val:.4f}')
+        _stat(self.trainer.stats, 'augment_rt', self.r_t, '{val:.4f}')
+
+    def iteration(self, i, *losses):
+        signs, count = self.augmenter.read()
+        nimg = self.trainer.cur_nimg
+        d_signs, d_count, d_nimg = signs - self.last[0], count - self.last[1], nimg - self.last[2]
+        if d_count > 0:                  # (no D step of this Augmenter since the last read: nothing to steer by)
+            self.last = (signs, count, nimg)
+            self.r_t = d_signs / d_count
+            step = (self.r_t > self.target) - (self.r_t < self.target)
+            self.augmenter.p = min(max(float(self.augmenter.p) + step * d_nimg / (1000.0 * self.adjust_kimg), 0.0), self.p_max)
+        self._write()

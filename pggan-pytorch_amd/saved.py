@@ -181,6 +181,7 @@ class GLossState(_Record):
         'gctx': None,       # GContext of G(z)
         'dctx': None,       # DContext of D(G(z)), keep_input=False
         'gscore': IMG,      # d loss / d score
+        'table': IMG,       # int32 [N, 8] augmentation table the forward applied to G(z) (None: no Augmenter); the backward transposes with it
         'active_g': None,   # layers of G that received a gradient (generator_backward)
     }
     __slots__ = tuple(LAYOUT)

@@ -148,19 +148,24 @@ def _step_mode(net, D, x):
 
 
 def _d_loss(objective, D, G, real_images_in, fake_latents_in, return_all):
-    """reference wgan_gp_loss.py:36-65 with the loss block and penalty of ``objective`` (engine.Objective)."""
+    """reference wgan_gp_loss.py:36-65 with the loss block and penalty of ``objective`` (engine.Objective).  With an Augmenter the step's
+    parameter table (2N rows: reals, then fakes) is made HERE, eagerly -- the uniforms launch and the table launch, outside every plan and
+    graph -- and handed down beside the mixing factors."""
     D.zero_grad()                                                        # :42
     G.zero_grad()                                                        # :43
+    table = None
+    if objective.augment is not None:
+        table = objective.augment.next_table('d', 2 * real_images_in.size(0), real_images_in.size(2), real_images_in.size(3))
     mix = mode = None                                                    # no penalty: one pass over [real | fake], eager in every mode
     if objective.penalty is not None:
         mix = _mixing_factors(objective.penalty, real_images_in.size(0), real_images_in.device)
         mode = _step_mode(D, D, real_images_in)
     if mode is None:
-        d_cost, d_real_loss, d_fake_loss, state = engine.d_loss_forward(D, G, real_images_in, fake_latents_in, mix, objective)
+        d_cost, d_real_loss, d_fake_loss, state = engine.d_loss_forward(D, G, real_images_in, fake_latents_in, mix, objective, table)
         d_cost = LossTensor.wrap(d_cost, lambda scale: engine.d_loss_backward(state, scale))
     else:
         d_cost, d_real_loss, d_fake_loss = (graphs if mode == 'graph' else plans).d_step(
-            D, G, engine._check_dev(real_images_in, 'real images'), engine._check_dev(fake_latents_in, 'latents'), mix.contiguous(), objective)
+            D, G, engine._check_dev(real_images_in, 'real images'), engine._check_dev(fake_latents_in, 'latents'), mix.contiguous(), objective, table)
         d_cost = LossTensor.wrap(d_cost, _replayed_backward(D))  # gradients are already in param.grad
     return (d_cost, d_real_loss, d_fake_loss) if return_all else d_cost
 
@@ -168,11 +173,15 @@ def _d_loss(objective, D, G, real_images_in, fake_latents_in, return_all):
 def _g_loss(objective, G, D, fake_latents_in):
     """reference wgan_gp_loss.py:68-74 with the generator term of ``objective``."""
     G.zero_grad()                                                        # :69
+    table = None
+    if objective.augment is not None:                                    # (N rows, drawn eagerly from the G stream of the Augmenter: as in _d_loss)
+        r = 4 * 2 ** int(G.depth)
+        table = objective.augment.next_table('g', fake_latents_in.size(0), r, r)
     mode = _step_mode(G, D, fake_latents_in)
     if mode is None:
-        g_cost, state = engine.g_loss_forward(G, D, fake_latents_in, objective)
+        g_cost, state = engine.g_loss_forward(G, D, fake_latents_in, objective, table)
         return LossTensor.wrap(g_cost, lambda scale: engine.g_loss_backward(state, scale))
-    g_cost = (graphs if mode == 'graph' else plans).g_step(G, D, engine._check_dev(fake_latents_in, 'latents'), objective)
+    g_cost = (graphs if mode == 'graph' else plans).g_step(G, D, engine._check_dev(fake_latents_in, 'latents'), objective, table)
     return LossTensor.wrap(g_cost, _replayed_backward(G))
 
 
