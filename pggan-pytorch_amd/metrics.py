@@ -39,7 +39,12 @@ k-means on the device-resident stack: exact and reproducible; UNPINNED like the 
 
 ``PrecisionRecall``: improved precision and recall with density and coverage over k-NN balls in uint8 image space (Kynkaanniemi et al.
 2019, Naeem et al. 2020) -- fidelity and coverage as separate numbers on one scale.  Three tile passes of exact integer distances of which
-no distance is stored; UNPINNED as well."""
+no distance is stored; UNPINNED as well.
+
+``FrechetDistance``: the Frechet distance ``fd`` between the feature moments of the two sets over ``RandomEmbedding``, a randomly
+initialised convolutional embedding (Naeem et al. 2020) -- the one metric here that is not in pixel space.  bf16 matrix cores for the
+embedding, fp64 matrix cores for the moments, the statistic in fp64 on the host; reproducible from the seed; UNPINNED: it is not the
+Inception distance and is not comparable with published FID tables."""
 import math
 
 import numpy as np
@@ -343,7 +348,7 @@ class _StackSource(object):
 
 class _FittedFeed(object):
     """The feed of the metrics that are fitted on the training stack once per stage and then fed generated images (``NDB``,
-    ``PrecisionRecall``).  The class supplies ``fit()`` -- which sets ``shape``, the [C,r,r] of the fitted stage -- ``reset()`` --
+    ``PrecisionRecall``, ``FrechetDistance``).  The class supplies ``fit()`` -- which sets ``shape``, the [C,r,r] of the fitted stage -- ``reset()`` --
     which zeroes ``_fed`` and ``_result`` -- ``_take(images_u8)``, what it does with a checked uint8 batch on ``device``, and
     ``result()``."""
 
@@ -894,5 +899,271 @@ class PrecisionRecall(_StackSource, _FittedFeed, _LevelMetric):
             nr = self.reals.shape[0]
             res = prd_statistic(counts[:self._fed], counts[self._fed:self._fed + nr], counts[self._fed + nr:], self.k)
             res.update(num_real=nr, num_fake=self._fed, k=self.k)
+            self._result = res
+        return self._result
+
+
+# ------------------------------------------------------------------------- Frechet distance over a random convolutional embedding
+EMBED_FEATURES = 128                # features of an embedded image: the width of the 4x4 layer
+EMBED_SLOPE, EMBED_EPS = 0.2, 1e-8
+EMBED_MAX_RESOLUTION = 512          # embed_width(1024) = 4 is no multiple of 8: pg_smp_conv3_bf16 does not take it
+
+
+def embed_width(H):
+    """Output channels of the embedding's 3x3 layer at map size ``H``."""
+    return min(EMBED_FEATURES, 4096 // H)
+
+
+def _pow2_at_least_4(v, message):
+    v = _int_in(v, 4, None, message)
+    if v & (v - 1):
+        raise ValueError(message)
+    return v
+
+
+def _rne_bf16_host(t):
+    """Round an fp64 tensor of finite values to nearest even onto the bf16 grid (subnormals included); fp64 out."""
+    _, e = torch.frexp(t)
+    u = torch.ldexp(torch.ones_like(t), e.clamp(min=-125) - 8)
+    return torch.round(t / u) * u
+
+
+def _moments_host(x):
+    """``ops.fd_moments_f64`` in numpy float64: (mean [F], cov [F,F]), cov mirrored from its upper triangle."""
+    x = np.asarray(x, dtype=np.float64)
+    mean = x.sum(axis=0) / x.shape[0]
+    a = x - mean
+    cov = np.triu(a.T.dot(a) / (x.shape[0] - 1))
+    return mean, cov + np.triu(cov, 1).T
+
+
+class RandomEmbedding(object):
+    """A randomly initialised convolutional embedding of uint8 images (Naeem et al. 2020 propose one for data far from ImageNet):
+    ``embedding(images_u8 [n,C,r,r]) -> features [n,128]`` in fp32, on ``device``.  r a power of two >= 4; above ``max_resolution`` the
+    images are first reduced with ``ops.pyramid_level_u8``.  1 <= C <= 4.
+
+    The network: the stem ``rne_bf16((x - 127.5) / 127.5)`` into 8 NHWC channels (zeros above C; ``ops.emb_stem_u8_bf16``); then for
+    H = r, r/2, ..., 4 one 3x3 pad-1 layer of ``embed_width(H) = min(128, 4096 // H)`` output channels on the bf16 matrix cores
+    (``sampling.conv3_bf16``: no bias, leaky ReLU 0.2, fused PixelNorm with eps 1e-8, scale sqrt(2 / (9 Cin)), ONE rounding to bf16),
+    followed while H > 4 by the 2x2 mean ``ops.emb_pool2_bf16``; the 4x4 map is averaged in fp32 (``ops.emb_gap_f32``).  The layer at
+    map size H with Cin input channels has the weights ``torch.randn(Cout, Cin, 3, 3)`` of a CPU generator seeded
+    ``seed * 1000003 + H``, permuted to [3,3,Cout,Cin] and rounded to bf16 once; they are uploaded once and kept.  A layer below the
+    first therefore has the same weights whatever r is, and the same seed gives the same embedding on every machine; the first layer
+    (Cin = 8, the padded stem) is a draw of its own from the same seed.  ``max_resolution`` <= 512: at 1024 the rule gives 4 output
+    channels, which the conv kernel does not take.
+
+    Images are embedded ``chunk`` at a time, which bounds the activations (64 images of 256^2 x 16 channels are 128 MiB in bf16).  Every
+    stage has one writer per element and a fixed order: two calls give the same bits, whatever ``chunk`` is.
+
+    ``device='cpu'`` evaluates the same contract on the host -- torch CPU convolutions in float64 over the bf16-rounded operands with
+    the same rounding points; stem, pool and mean exactly as the kernels -- which is CLOSE to the device, not equal: a conv output
+    within a rounding error of a bf16 tie may round the other way."""
+
+    def __init__(self, channels, seed=0, max_resolution=256, chunk=64, device=None):
+        self.channels = _int_in(channels, 1, ops.EMB_MAX_C, 'channels = %r (1 <= channels <= %d)' % (channels, ops.EMB_MAX_C))
+        self.seed = _int_in(seed, None, None, 'seed = %r (an integer)' % (seed,))
+        message = 'max_resolution = %r (a power of two, 4 <= max_resolution <= %d)' % (max_resolution, EMBED_MAX_RESOLUTION)
+        self.max_resolution = _pow2_at_least_4(max_resolution, message)
+        if self.max_resolution > EMBED_MAX_RESOLUTION:
+            raise ValueError(message)
+        self.chunk = _int_in(chunk, 1, None, 'chunk = %r (at least 1)' % (chunk,))
+        self.device = torch.device('cuda' if device is None else device)
+        self._weights = {}
+
+    def layers(self, r):
+        """[(H, Cin, Cout)] of the 3x3 layers for images of (reduced) resolution ``r``."""
+        out, cin = [], ops.EMB_STEM_CH
+        while r >= 4:
+            out.append((r, cin, embed_width(r)))
+            cin, r = embed_width(r), r // 2
+        return out
+
+    def weights(self, H, cin):
+        """bf16 [3,3,Cout,Cin] of the layer at map size ``H`` with ``cin`` inputs, on ``device``."""
+        key = (H, cin)
+        if key not in self._weights:
+            g = torch.Generator().manual_seed(self.seed * 1000003 + H)
+            w = torch.randn(embed_width(H), cin, 3, 3, generator=g)
+            self._weights[key] = w.permute(2, 3, 0, 1).contiguous().to(torch.bfloat16).to(self.device)
+        return self._weights[key]
+
+    def _check(self, images):
+        if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] < 1 \
+                or images.shape[1] != self.channels or images.shape[2] != images.shape[3]:
+            raise ValueError('expected uint8 images [n,%d,r,r], got %s'
+                             % (self.channels, tuple(images.shape) if torch.is_tensor(images) else type(images)))
+        _pow2_at_least_4(int(images.shape[-1]), 'images of %d x %d (r a power of two >= 4)' % tuple(images.shape[2:]))
+
+    def _reduce(self, images):
+        r = int(images.shape[-1])
+        if r <= self.max_resolution:
+            return images.contiguous()
+        depthdiff = (r // self.max_resolution).bit_length() - 1
+        if self.device.type == 'cuda':
+            return ops.pyramid_level_u8(images.contiguous(), depthdiff)
+        from .dataset import level_host
+        return torch.from_numpy(np.ascontiguousarray(level_host(images.numpy(), depthdiff)))
+
+    def _device_chunk(self, images, trace):
+        from . import sampling
+        n, r = images.shape[0], int(images.shape[-1])
+        x = ops.emb_stem_u8_bf16(images)
+        trace.append(('stem', x))
+        for H, cin, _ in self.layers(r):
+            x = sampling.conv3_bf16(x, self.weights(H, cin), None, n, H, H, math.sqrt(2.0 / (9 * cin)), EMBED_SLOPE, EMBED_EPS,
+                                    pixelnorm=True)
+            trace.append(('conv%d' % H, x))
+            if H > 4:
+                x = ops.emb_pool2_bf16(x)
+                trace.append(('pool%d' % H, x))
+        f = ops.emb_gap_f32(x)
+        trace.append(('gap', f))
+        return f
+
+    def _host_chunk(self, images, trace):
+        import torch.nn.functional as F
+        r, C = int(images.shape[-1]), self.channels
+        x32 = (images.to(torch.float32) - 127.5) / 127.5                    # float32: one rounding per operation, as the stem kernel
+        x = x32.to(torch.bfloat16).double()                                 # NCHW; the stem's zero channels contribute nothing
+        trace.append(('stem', x))
+        for H, cin, _ in self.layers(r):
+            w = self.weights(H, cin).double().permute(2, 3, 0, 1)[:, :x.shape[1]]
+            v = math.sqrt(2.0 / (9 * cin)) * F.conv2d(x, w, None, 1, 1)
+            v = torch.where(v > 0, v, v * EMBED_SLOPE)
+            x = _rne_bf16_host(v / torch.sqrt(torch.mean(v * v, 1, keepdim=True) + EMBED_EPS))
+            trace.append(('conv%d' % H, x))
+            if H > 4:
+                a = x.float()                                               # bf16 values: exact in float32
+                p = ((a[:, :, 0::2, 0::2] + a[:, :, 0::2, 1::2]) + (a[:, :, 1::2, 0::2] + a[:, :, 1::2, 1::2])) * 0.25
+                x = p.to(torch.bfloat16).double()
+                trace.append(('pool%d' % H, x))
+        a = x.float()
+        s = torch.zeros(a.shape[:2], dtype=torch.float32)
+        for h in range(a.shape[2]):
+            for w_ in range(a.shape[3]):
+                s = s + a[:, :, h, w_]
+        f = s * (torch.ones((), dtype=torch.float32) / float(a.shape[2] * a.shape[3]))
+        trace.append(('gap', f))
+        return f
+
+    def trace(self, images):
+        """[(name, tensor)] of every stage's output for ONE chunk of images: 'stem', then 'conv<H>' and 'pool<H>' per layer, 'gap'.
+        Device mode: bf16 NHWC maps; host mode: fp64 NCHW maps of bf16 values (the stem without its zero channels)."""
+        self._check(images)
+        out = []
+        images = self._reduce(images.to(self.device))
+        (self._device_chunk if self.device.type == 'cuda' else self._host_chunk)(images, out)
+        return out
+
+    def __call__(self, images):
+        self._check(images)
+        images = images.to(self.device)
+        run = self._device_chunk if self.device.type == 'cuda' else self._host_chunk
+        out = [run(self._reduce(images[s:s + self.chunk]), []) for s in range(0, images.shape[0], self.chunk)]
+        return out[0] if len(out) == 1 else torch.cat(out)
+
+
+def frechet_statistic(mu1, cov1, mu2, cov2):
+    """The Frechet distance between two Gaussians from their moments, in fp64 on the host:
+
+        fd = |mu1 - mu2|^2 + tr cov1 + tr cov2 - 2 sum_k sqrt(max(lambda_k, 0))
+
+    with lambda the eigenvalues of S cov2 S and S = cov1^(1/2) from a symmetric eigendecomposition whose negative eigenvalues are
+    clamped to 0 -- S cov2 S is symmetric and has the eigenvalues of cov1 cov2, so only ``eigh`` / ``eigvalsh`` are needed and no general
+    matrix square root.  Returns {'fd', 'mean_term', 'cov_term'}: fd = mean_term + cov_term, as computed -- NOT clamped at 0 (equal
+    moments give a value within rounding of 0, of either sign)."""
+    mu1, mu2 = np.asarray(mu1, dtype=np.float64), np.asarray(mu2, dtype=np.float64)
+    cov1, cov2 = np.asarray(cov1, dtype=np.float64), np.asarray(cov2, dtype=np.float64)
+    F = mu1.size
+    if mu1.shape != (F,) or mu2.shape != (F,) or cov1.shape != (F, F) or cov2.shape != (F, F):
+        raise ValueError('frechet_statistic: mu [F] and cov [F,F] of both sets, got %s, %s, %s, %s' % (mu1.shape, cov1.shape, mu2.shape, cov2.shape))
+    lam, V = np.linalg.eigh(cov1)
+    S = (V * np.sqrt(np.maximum(lam, 0.0))).dot(V.T)
+    A = S.dot(cov2).dot(S)
+    lam = np.linalg.eigvalsh(0.5 * (A + A.T))
+    mean_term = float(((mu1 - mu2) ** 2).sum())
+    cov_term = float(np.trace(cov1) + np.trace(cov2) - 2.0 * np.sqrt(np.maximum(lam, 0.0)).sum())
+    return {'fd': mean_term + cov_term, 'mean_term': mean_term, 'cov_term': cov_term}
+
+
+class FrechetDistance(_StackSource, _FittedFeed, _LevelMetric):
+    """The Frechet distance ``fd`` between the training images and generated images over the features of a ``RandomEmbedding``: the
+    distance between the Gaussians with the two sets' feature means and covariances.  It is NOT the Inception distance: no pretrained
+    network is involved (none can be shipped, and ImageNet features would be the wrong ones for one- and two-channel spectrograms), so
+    the value is UNPINNED like the SWD, MS-SSIM, NDB and PRD -- comparable between runs of this project with the same seed and
+    ``max_resolution``, not with published FID tables.  1- to 4-channel networks are measured alike.
+
+    ``source``: a ``DeviceImageDataset`` or a ``DeviceStripDataset`` (``fit()`` takes ``level_stack()`` of the current ``model_depth``;
+    ``range_in`` must be (0, 255)) or a uint8 tensor [M,C,r,r].  ``fit()`` embeds ``num_real`` images (None: all) -- the first entries of
+    ``torch.randperm(M)`` from a CPU generator seeded ``seed`` -- and keeps their mean and covariance (``ops.fd_moments_f64``: fp64, on
+    the fp64 matrix cores, reproducible).  ``feed(samples_fp32)`` rounds to the 0..255 levels of the saved image (``ops.quantize_u8``
+    with ``drange``); ``feed_u8`` takes levels; batches of any size >= 1, at the stage's resolution; their [n,128] features are kept.
+    ``result()`` needs at least 2 fed images: one moments call over all fed features, one host read, ``frechet_statistic`` in fp64 on
+    the host.  ``embedding``: a ``RandomEmbedding`` to use (and share between metrics) instead of one made from ``seed`` and
+    ``max_resolution`` at ``fit()``.  ``device='cpu'``: the host twin (the embedding's host mode and numpy moments), close to the device
+    but not equal.
+
+    With fewer samples than the 128 features on either side a covariance estimate is rank deficient: the value is finite and still
+    ordered sensibly, but biased; use thousands of images per set, and compare values taken with the same counts."""
+
+    def __init__(self, source, num_real=None, max_resolution=256, seed=0, drange=(-1, 1), device=None, embedding=None):
+        _, src_device = self._stack_source(source)
+        self.num_real = None if num_real is None else _int_in(num_real, 2, None, 'num_real = %r (at least 2 images)' % (num_real,))
+        self.seed = _int_in(seed, None, None, 'seed = %r (an integer)' % (seed,))
+        super(FrechetDistance, self).__init__(source, src_device, drange, device)
+        if embedding is None:
+            RandomEmbedding(1, self.seed, max_resolution, device=self.device)     # (the argument check; made for C channels at fit())
+        elif not isinstance(embedding, RandomEmbedding) or embedding.device.type != self.device.type:
+            raise ValueError('embedding: expected a RandomEmbedding on %s' % self.device.type)
+        self.max_resolution, self.embedding = max_resolution, embedding
+        self.mean = self.cov = self.resolution = self.shape = self.indices = None
+        self.reset()
+
+    def _moments(self, feats):
+        if self.device.type == 'cuda':
+            return ops.fd_moments_f64(feats.contiguous())
+        return tuple(torch.from_numpy(v) for v in _moments_host(feats.numpy()))
+
+    def fit(self, block=1024):
+        """Embed the reals of the current stage, ``block`` at a time, and keep their moments: ``mean`` [128] and ``cov`` [128,128] (fp64,
+        on ``device``), ``indices`` (int64, host: the images taken), ``resolution`` (the STAGE's, what ``feed`` expects); forgets what was
+        fed.  Returns self."""
+        stack = self.stack()
+        M, C = stack.shape[0], stack.shape[1]
+        n = M if self.num_real is None else self.num_real
+        if not 2 <= n <= M:
+            raise ValueError('%d of %d images (2 <= num_real <= M)' % (n, M))
+        if self.embedding is None:
+            self.embedding = RandomEmbedding(C, self.seed, self.max_resolution, device=self.device)
+        if self.embedding.channels != C:
+            raise ValueError('the embedding takes %d channels, the stack has %d' % (self.embedding.channels, C))
+        self.indices = torch.randperm(M, generator=torch.Generator().manual_seed(self.seed))[:n]
+        idx = self.indices.to(self.device)
+        feats = [self.embedding(stack.index_select(0, idx[s:s + block])) for s in range(0, n, block)]
+        self.mean, self.cov = self._moments(feats[0] if len(feats) == 1 else torch.cat(feats))
+        self.shape, self.resolution = tuple(stack.shape[1:]), int(stack.shape[-1])
+        self.reset()
+        return self
+
+    def reset(self):
+        """Forget what was fed; the fit is kept."""
+        self._feats, self._fed, self._result = [], 0, None
+
+    def _take(self, images):
+        self._feats.append(self.embedding(images))
+
+    def result(self):
+        """{'fd', 'mean_term', 'cov_term' (fp64), 'num_real', 'num_fake'}.  One device synchronisation."""
+        if self._result is None:
+            if self.mean is None:
+                raise RuntimeError('fit() first')
+            if self._fed < 2:
+                raise RuntimeError('%d images were fed; a covariance needs 2' % self._fed)
+            mean, cov = self._moments(self._feats[0] if len(self._feats) == 1 else torch.cat(self._feats))
+            F = mean.numel()
+            host = torch.cat([self.mean, self.cov.reshape(-1), mean, cov.reshape(-1)]).cpu().numpy()
+            mu1, cov1, mu2, cov2 = host[:F], host[F:F + F * F], host[F + F * F:2 * F + F * F], host[2 * F + F * F:]
+            res = frechet_statistic(mu1, cov1.reshape(F, F), mu2, cov2.reshape(F, F))
+            res.update(num_real=int(self.indices.numel()), num_fake=self._fed)
             self._result = res
         return self._result

@@ -1356,6 +1356,78 @@ def prd_ball_u8(a_u8, b_u8, rad_a=None, rad_b=None):
     return a_cnt, a_hit, b_cnt, b_hit
 
 
+# ------------------------------------------------------------------------- random embedding and fp64 moments: the Frechet distance (csrc/embed.hip)
+EMBED = {name[len('PG_'):]: value for name, value in _lib.EMBED_CONSTANTS.items()}   # the addition's own table
+EMB_STEM_CH, EMB_MAX_C = EMBED['EMB_STEM_CH'], EMBED['EMB_MAX_C']
+FD_SLICE, FD_TILE, FD_MIN_F, FD_MAX_F = EMBED['FD_SLICE'], EMBED['FD_TILE'], EMBED['FD_MIN_F'], EMBED['FD_MAX_F']
+
+
+def _bf16_map(x, who):
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.bfloat16 or not x.is_contiguous() or x.dim() != 4 or x.numel() < 1:
+        raise ValueError('%s: expected a contiguous, non-empty bfloat16 device tensor [N,H,W,Ch]' % who)
+    return tuple(x.shape)
+
+
+def emb_stem_u8_bf16(x_u8):
+    """uint8 device images ``x_u8`` [M,C,H,W], 1 <= C <= ``EMB_MAX_C`` -> the bf16 NHWC input [M,H,W,``EMB_STEM_CH``] of the embedding's
+    first 3x3 layer (pg_emb_stem_u8_bf16): ``rne_bf16((float(x) - 127.5f) / 127.5f)`` in channels 0 .. C - 1, zeros above."""
+    _u8_images(x_u8, 'emb_stem_u8_bf16')
+    M, C, H, W = x_u8.shape
+    if not 1 <= C <= EMB_MAX_C:
+        raise ValueError('emb_stem_u8_bf16: %d image channels (1 <= C <= %d)' % (C, EMB_MAX_C))
+    require_gpu()
+    y = torch.empty((M, H, W, EMB_STEM_CH), device=x_u8.device, dtype=torch.bfloat16)
+    _lib.call('pg_emb_stem_u8_bf16', x_u8.data_ptr(), y.data_ptr(), M, C, H, W, _stream())
+    return y
+
+
+def emb_pool2_bf16(x):
+    """bf16 device map ``x`` [N,H,W,Ch] (H, W even, Ch % 8 == 0) -> its 2x2 mean [N,H/2,W/2,Ch] in bf16 (pg_emb_pool2_bf16):
+    ``rne_bf16(((a00 + a01) + (a10 + a11)) * 0.25f)`` in fp32, in that order."""
+    N, H, W, Ch = _bf16_map(x, 'emb_pool2_bf16')
+    if H % 2 or W % 2 or Ch % 8:
+        raise ValueError('emb_pool2_bf16: a map %s (H and W even, Ch a multiple of 8)' % ((N, H, W, Ch),))
+    require_gpu()
+    y = torch.empty((N, H // 2, W // 2, Ch), device=x.device, dtype=torch.bfloat16)
+    _lib.call('pg_emb_pool2_bf16', x.data_ptr(), y.data_ptr(), N, H, W, Ch, _stream())
+    return y
+
+
+def emb_gap_f32(x):
+    """bf16 device map ``x`` [N,H,W,Ch] -> its mean over the pixels [N,Ch] in fp32 (pg_emb_gap_f32): the fp32 sum over (h, w) in
+    ascending row-major order from 0, times ``1.0f / (H W)``."""
+    N, H, W, Ch = _bf16_map(x, 'emb_gap_f32')
+    require_gpu()
+    f = torch.empty((N, Ch), device=x.device, dtype=torch.float32)
+    _lib.call('pg_emb_gap_f32', x.data_ptr(), f.data_ptr(), N, H, W, Ch, _stream())
+    return f
+
+
+def fd_moments_scratch(M, F):
+    """The fp64 values of scratch pg_fd_moments_f64 needs for [M,F] features: the column sums and the covariance tiles on or above the
+    diagonal of every slice of ``FD_SLICE`` rows."""
+    S, B = (M + FD_SLICE - 1) // FD_SLICE, (F + FD_TILE - 1) // FD_TILE
+    return S * (F + B * (B + 1) // 2 * FD_TILE * FD_TILE)
+
+
+def fd_moments_f64(x):
+    """fp32 device features ``x`` [M,F] (M >= 2, F a multiple of 16, ``FD_MIN_F`` <= F <= ``FD_MAX_F``) -> ``(mean [F], cov [F,F])`` in
+    fp64 (pg_fd_moments_f64): ``cov = sum_r (x_r - mean)(x_r - mean)^T / (M - 1)``, centred on the call's own mean, accumulated on the
+    fp64 matrix cores in an order that depends on (M, F) alone; ``cov == cov.T`` bit for bit and two calls give the same bits.  The
+    scratch is allocated here and every element of it is written.  No host synchronisation."""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 2:
+        raise ValueError('fd_moments_f64: expected a contiguous float32 device tensor [M,F]')
+    M, F = x.shape
+    if M < 2 or F % 16 or not FD_MIN_F <= F <= FD_MAX_F:
+        raise ValueError('fd_moments_f64: features [%d,%d] (M >= 2, F a multiple of 16, %d <= F <= %d)' % (M, F, FD_MIN_F, FD_MAX_F))
+    require_gpu()
+    mean = torch.empty((F,), device=x.device, dtype=torch.float64)
+    cov = torch.empty((F, F), device=x.device, dtype=torch.float64)
+    scratch = torch.empty((fd_moments_scratch(M, F),), device=x.device, dtype=torch.float64)
+    _lib.call('pg_fd_moments_f64', x.data_ptr(), M, F, mean.data_ptr(), cov.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream())
+    return mean, cov
+
+
 # ------------------------------------------------------------------------- nearest windows at every start column (csrc/shift_search.hip)
 SHIFT = {name[len('PG_SHIFT_'):]: value for name, value in _lib.SHIFT_CONSTANTS.items() if name.startswith('PG_SHIFT_')}   # the addition's own table
 SHIFT_POS_BITS, SHIFT_MAX_QUERIES, SHIFT_TILE = SHIFT['POS_BITS'], SHIFT['MAX_QUERIES'], SHIFT['TILE']

@@ -561,7 +561,7 @@ class ShiftNNMonitor(_NeighbourSheet):
 
 
 class _FittedSamples(Evaluation):
-    """What ``NDBMonitor`` and ``PRDMonitor`` share: one metric object for all stages, fitted on ``dataset`` again when the stage's
+    """What ``NDBMonitor``, ``PRDMonitor`` and ``FDMonitor`` share: one metric object for all stages, fitted on ``dataset`` again when the stage's
     resolution differs from the fitted one, then fed ``num_samples`` generated images ``minibatch`` at a time.  A subclass writes
     ``make_metric()`` (a ``fit()`` / ``reset()`` / ``feed()`` / ``result()`` metric with ``resolution``) and ``write_stats(result)``."""
 
@@ -670,6 +670,44 @@ class PRDMonitor(_FittedSamples):
     def write_stats(self, res):
         for name in ('precision', 'recall', 'density', 'coverage'):
             self.stat(name, res[name], '{val:.3f}')
+
+
+class FDMonitor(_FittedSamples):
+    """The Frechet distance ``fd`` per tick (``metrics.FrechetDistance``: the distance between the feature moments of training and
+    generated images over a randomly initialised convolutional embedding; the reference reports none): every ``fd_ticks`` ticks and at
+    the end, ``num_samples`` images of ``G.forward(sample_fn(n).cuda())``, ``minibatch`` at a time -- of the smoothed generator when the
+    trainer keeps one (``smoothed`` as in ``Evaluation``) -- against ``num_real`` training images (``metric_kwargs``; default: all).
+    ``dataset``: a ``DeviceImageDataset`` or a ``DeviceStripDataset``; the reals are embedded from ``level_stack()`` of the current
+    growth stage and REFITTED when the stage's resolution differs from the fitted one (once per stage, not per evaluation).  Writes
+    ``stats['fd']`` under the stat-dict convention of the other monitors.  It is NOT the Inception distance (FID): comparable between
+    runs of this project, not with published tables.  1- to 4-channel networks are measured alike.  Rank 0 evaluates (replicas are
+    identical; the reals are rank 0's shard).  Opt-in: a run that does not register it pays nothing.  ``metric_kwargs`` go to
+    ``FrechetDistance`` (num_real, max_resolution, seed, drange, embedding); above ``max_resolution`` = 256 both sets are reduced with
+    ``ops.pyramid_level_u8`` before they are embedded.
+
+    The default period follows docs/experiments_fd.md, from one run that timed the generator passes and the metric together (a default
+    generator, batches of 16, 512 samples timed and scaled): at 3x1024^2 the 4096 generator passes took 0.66 s, feeding them (quantise,
+    reduce to 256^2, embed: 256 batches of 16) 0.08 s more, ``result()`` (the moments of 4096 x 128 features, the host read, the
+    eigenvalues) 0.004 s; the fit measured 0.010 ms per real, i.e. 0.30 s for 30 000 reals by proportion (1024 were timed), once per
+    stage.  At 1x256^2: 0.39 s, 0.07 s, 0.003 s and 0.008 ms per real.  An evaluation is under 0.66 + 0.08 + 0.01 + 0.30 = 1.05 s, and
+    under 1 % of a 3.3 s tick of 1 kimg (the rule of docs/experiments_swd.md) needs ticks >= 100 x 1.05 / 3.3 = 32: 40.  The metric's
+    own part is an eighth of the evaluation; the rest is the generator.  A moment estimate over 128 features needs thousands of samples
+    per side; ``num_samples=1024, fd_ticks=10`` costs the same share with a noisier, more biased value.
+
+    ``precision``: 'fp32' (default) or 'bf16', as in ``Evaluation``."""
+
+    def __init__(self, dataset, sample_fn, num_samples=4096, minibatch=16, fd_ticks=40, smoothed=None, precision='fp32',
+                 **metric_kwargs):
+        super(FDMonitor, self).__init__(fd_ticks, dataset, sample_fn, num_samples, minibatch, smoothed, precision)
+        if self.num_samples < 2:
+            raise ValueError('num_samples = %r (a covariance needs at least 2 samples)' % (num_samples,))
+        self.metric_kwargs = dict(metric_kwargs)
+
+    def make_metric(self):
+        return metrics.FrechetDistance(self.dataset, **self.metric_kwargs)
+
+    def write_stats(self, res):
+        self.stat('fd', res['fd'], '{val:.4f}')
 
 
 class ProjectionMonitor(Evaluation):
