@@ -2,11 +2,11 @@
 
 include/pggan_hip.h (the product boundary), include/pggan_hip_debug.h (thread-local diagnostic exports) and
 include/pggan_hip_cluster.h, include/pggan_hip_gan.h, include/pggan_hip_phase.h, include/pggan_hip_sampling.h,
-include/pggan_hip_projection.h, include/pggan_hip_crop.h, include/pggan_hip_swd.h, include/pggan_hip_mel.h, include/pggan_hip_resample.h, include/pggan_hip_shift.h, include/pggan_hip_prd.h, include/pggan_hip_augment.h and include/pggan_hip_embed.h (the k-means, the GAN-objective, the magnitude +
-instantaneous-frequency, the bf16 sampling, the projection-loss, the strip-crop, the C-channel sliced-Wasserstein, the warped-row sound, the rate-conversion, the shift-search, the k-NN-ball, the augmentation and the random-embedding additions to the boundary) are the one statement
+include/pggan_hip_projection.h, include/pggan_hip_crop.h, include/pggan_hip_swd.h, include/pggan_hip_mel.h, include/pggan_hip_resample.h, include/pggan_hip_shift.h, include/pggan_hip_prd.h, include/pggan_hip_augment.h, include/pggan_hip_embed.h and include/pggan_hip_kid.h (the k-means, the GAN-objective, the magnitude +
+instantaneous-frequency, the bf16 sampling, the projection-loss, the strip-crop, the C-channel sliced-Wasserstein, the warped-row sound, the rate-conversion, the shift-search, the k-NN-ball, the augmentation, the random-embedding and the kernel-distance additions to the boundary) are the one statement
 of the ABI: the compiler holds every definition in csrc/*.hip against them, and this module parses them once into SIGNATURES /
-DEBUG_SIGNATURES / CLUSTER_SIGNATURES / GAN_SIGNATURES / PHASE_SIGNATURES / SAMPLING_SIGNATURES / PROJECTION_SIGNATURES / CROP_SIGNATURES / SWD_SIGNATURES / MEL_SIGNATURES / RESAMPLE_SIGNATURES / SHIFT_SIGNATURES / PRD_SIGNATURES / AUGMENT_SIGNATURES / EMBED_SIGNATURES (name -> argtypes), the
-return types, and CONSTANTS / CLUSTER_CONSTANTS / GAN_CONSTANTS / PHASE_CONSTANTS / SAMPLING_CONSTANTS / PROJECTION_CONSTANTS / CROP_CONSTANTS / SWD_CONSTANTS / MEL_CONSTANTS / RESAMPLE_CONSTANTS / SHIFT_CONSTANTS / PRD_CONSTANTS / AUGMENT_CONSTANTS / EMBED_CONSTANTS (every
+DEBUG_SIGNATURES / CLUSTER_SIGNATURES / GAN_SIGNATURES / PHASE_SIGNATURES / SAMPLING_SIGNATURES / PROJECTION_SIGNATURES / CROP_SIGNATURES / SWD_SIGNATURES / MEL_SIGNATURES / RESAMPLE_SIGNATURES / SHIFT_SIGNATURES / PRD_SIGNATURES / AUGMENT_SIGNATURES / EMBED_SIGNATURES / KID_SIGNATURES (name -> argtypes), the
+return types, and CONSTANTS / CLUSTER_CONSTANTS / GAN_CONSTANTS / PHASE_CONSTANTS / SAMPLING_CONSTANTS / PROJECTION_CONSTANTS / CROP_CONSTANTS / SWD_CONSTANTS / MEL_CONSTANTS / RESAMPLE_CONSTANTS / SHIFT_CONSTANTS / PRD_CONSTANTS / AUGMENT_CONSTANTS / EMBED_CONSTANTS / KID_CONSTANTS (every
 ``#define PG_*`` of the product header / of an addition as an integer).  A new entry point is
 declared in the header, defined in csrc/ and wrapped in ops.py; nothing is restated here.
 
@@ -152,6 +152,9 @@ _RESTYPE_OF.update(_augment_restypes)
 # ... and the ends of the random convolutional embedding with the fp64 moments of its features (csrc/embed.hip, wrapped in ops.py, used by metrics.py)
 EMBED_SIGNATURES, _embed_restypes, EMBED_CONSTANTS = _read_header('pggan_hip_embed.h')
 _RESTYPE_OF.update(_embed_restypes)
+# ... and the tile sums of the cubic polynomial kernel for the unbiased kernel distance (csrc/kid.hip, wrapped in ops.py, used by metrics.py)
+KID_SIGNATURES, _kid_restypes, KID_CONSTANTS = _read_header('pggan_hip_kid.h')
+_RESTYPE_OF.update(_kid_restypes)
 ABI_VERSION = CONSTANTS['PG_ABI_VERSION']          # load() holds the library's pg_abi_version() against it: a stale .so is refused
 
 _lib = None
@@ -174,7 +177,8 @@ def load():
                            + list(GAN_SIGNATURES.items()) + list(PHASE_SIGNATURES.items()) + list(SAMPLING_SIGNATURES.items())
                            + list(PROJECTION_SIGNATURES.items()) + list(CROP_SIGNATURES.items()) + list(SWD_SIGNATURES.items())
                            + list(MEL_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(SHIFT_SIGNATURES.items())
-                           + list(PRD_SIGNATURES.items()) + list(AUGMENT_SIGNATURES.items()) + list(EMBED_SIGNATURES.items())):
+                           + list(PRD_SIGNATURES.items()) + list(AUGMENT_SIGNATURES.items()) + list(EMBED_SIGNATURES.items())
+                           + list(KID_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -44,7 +44,11 @@ no distance is stored; UNPINNED as well.
 ``FrechetDistance``: the Frechet distance ``fd`` between the feature moments of the two sets over ``RandomEmbedding``, a randomly
 initialised convolutional embedding (Naeem et al. 2020) -- the one metric here that is not in pixel space.  bf16 matrix cores for the
 embedding, fp64 matrix cores for the moments, the statistic in fp64 on the host; reproducible from the seed; UNPINNED: it is not the
-Inception distance and is not comparable with published FID tables."""
+Inception distance and is not comparable with published FID tables.
+
+``KernelDistance``: the kernel distance ``kid`` over the same embedding, the unbiased estimator of the squared maximum mean discrepancy
+with a cubic polynomial kernel (Binkowski et al. 2018) -- unbiased at any sample count, where ``fd`` needs thousands of images a set.  The
+kernel sums of 64 x 64 tiles on the fp64 matrix cores (no Gram matrix is written), the statistic in fp64 on the host; UNPINNED as well."""
 import math
 
 import numpy as np
@@ -1165,5 +1169,176 @@ class FrechetDistance(_StackSource, _FittedFeed, _LevelMetric):
             mu1, cov1, mu2, cov2 = host[:F], host[F:F + F * F], host[F + F * F:2 * F + F * F], host[2 * F + F * F:]
             res = frechet_statistic(mu1, cov1.reshape(F, F), mu2, cov2.reshape(F, F))
             res.update(num_real=int(self.indices.numel()), num_fake=self._fed)
+            self._result = res
+        return self._result
+
+
+# ------------------------------------------------------------------------- kernel distance: unbiased MMD^2 over the same embedding
+KID_SUBSET = 1024                   # rows of one subset of ``kid_statistic``: the default of Binkowski et al. is 1000; a multiple of the tile
+
+
+def _kid_tilesums_host(x, y=None, gamma=None, coef0=1.0, skip_diagonal=False):
+    """``ops.kid_tilesums_f64`` in numpy float64: [A,B] sums of ``(gamma x_i . y_j + coef0)^3`` per 64 x 64 tile, the kernel function
+    applied before the pairs of a ragged tile (and i == j under ``skip_diagonal``) are left out.  1024 rows at a time: the Gram matrix
+    of 30 000 reals never exists here either.  The order of the sums is numpy's, not the device's."""
+    T = ops.KID_TILE
+    x = np.asarray(x, dtype=np.float64)
+    self_form = y is None
+    y = x if self_form else np.asarray(y, dtype=np.float64)
+    if skip_diagonal and not self_form:
+        raise ValueError('skip_diagonal is for the self form (y = None)')
+    (M, F), N = x.shape, y.shape[0]
+    gamma = 1.0 / F if gamma is None else float(gamma)
+    A, B = (M + T - 1) // T, (N + T - 1) // T
+    out = np.zeros((A, B), dtype=np.float64)
+    for r0 in range(0, M, 16 * T):
+        t = gamma * x[r0:r0 + 16 * T].dot(y.T) + float(coef0)
+        k = (t * t) * t
+        if skip_diagonal:
+            i = np.arange(r0, r0 + k.shape[0])
+            k[i - r0, i] = 0.0
+        rows = (k.shape[0] + T - 1) // T
+        padded = np.zeros((rows * T, B * T), dtype=np.float64)
+        padded[:k.shape[0], :N] = k
+        out[r0 // T:r0 // T + rows] = padded.reshape(rows, T, B, T).sum(axis=(1, 3))
+    return out
+
+
+def kid_statistic(sxx, syy, sxy, m, n, subset_size=None):
+    """The unbiased estimator of the squared maximum mean discrepancy (the Kernel Inception Distance estimator of Binkowski et al.
+    2018) from the tile sums of the kernel (``ops.kid_tilesums_f64``), in fp64 on the host:
+
+        kid = sum(sxx) / (m (m - 1)) + sum(syy) / (n (n - 1)) - 2 sum(sxy) / (m n)
+
+    ``sxx`` [A,A] and ``syy`` [B,B]: the self forms of the two sets of ``m`` and ``n`` vectors taken with ``skip_diagonal``; ``sxy``
+    [A,B]: the cross form.  Unbiased at any sample count and NOT clamped at 0: two sets from one distribution give values of either
+    sign around 0.  ``subset_size`` (None: ``KID_SUBSET`` = 1024; a multiple of ``ops.KID_TILE``): the same estimator on each of the
+    ``min(m, n) // subset_size`` subsets, subset s being rows [s subset_size, (s + 1) subset_size) of BOTH sets -- read out of the same
+    tile sums, whose tiles are whole there.  Returns {'kid', 'subsets' (their number), 'kid_subset_mean', 'kid_subset_std' (the sample
+    standard deviation, n - 1 in the denominator)}; the last two are None with fewer than 2 subsets."""
+    T = ops.KID_TILE
+    m = _int_in(m, 2, None, 'm = %r (at least 2 vectors a set)' % (m,))
+    n = _int_in(n, 2, None, 'n = %r (at least 2 vectors a set)' % (n,))
+    S = KID_SUBSET if subset_size is None else _int_in(subset_size, T, None, 'subset_size = %r (a positive multiple of %d)' % (subset_size, T))
+    if S % T:
+        raise ValueError('subset_size = %r (a positive multiple of %d)' % (subset_size, T))
+    sxx, syy, sxy = (np.asarray(s, dtype=np.float64) for s in (sxx, syy, sxy))
+    A, B = (m + T - 1) // T, (n + T - 1) // T
+    if sxx.shape != (A, A) or syy.shape != (B, B) or sxy.shape != (A, B):
+        raise ValueError('kid_statistic: tile sums %s, %s, %s for m = %d, n = %d (expected %s, %s, %s)'
+                         % (sxx.shape, syy.shape, sxy.shape, m, n, (A, A), (B, B), (A, B)))
+    kid = float(sxx.sum() / (m * (m - 1.0)) + syy.sum() / (n * (n - 1.0)) - 2.0 * sxy.sum() / (float(m) * n))
+    t = S // T
+    values = []
+    for s in range(min(m, n) // S):
+        b = slice(s * t, (s + 1) * t)
+        values.append(float(sxx[b, b].sum() / (S * (S - 1.0)) + syy[b, b].sum() / (S * (S - 1.0)) - 2.0 * sxy[b, b].sum() / (float(S) * S)))
+    many = len(values) >= 2
+    return {'kid': kid, 'subsets': len(values), 'kid_subset_mean': float(np.mean(values)) if many else None,
+            'kid_subset_std': float(np.std(values, ddof=1)) if many else None}
+
+
+class KernelDistance(_StackSource, _FittedFeed, _LevelMetric):
+    """The kernel distance ``kid`` between the training images and generated images over the features of a ``RandomEmbedding``: the
+    unbiased estimator of the squared maximum mean discrepancy with the cubic polynomial kernel ``k(a, b) = (gamma a . b + coef0)^3``
+    (the Kernel Inception Distance estimator of Binkowski et al. 2018; ``gamma`` None = 1 / 128, ``coef0`` = 1), ``kid_statistic``.
+    Unlike ``fd`` it is unbiased at ANY sample count -- a few dozen images a side give a noisy value around the true one, not a value
+    off by a hundred -- and it comes with a spread over subsets: the number to compare between runs on a small data set.  It is NOT
+    the Inception-feature KID: no pretrained network is involved, so the value is UNPINNED like the other metrics -- comparable between
+    runs of this project with the same seed and ``max_resolution``, not with published tables.  It is not clamped at 0.
+
+    ``source``, ``num_real``, ``max_resolution``, ``seed``, ``drange``, ``embedding`` and the ``fit / reset / feed / feed_u8 / result``
+    protocol are ``FrechetDistance``'s, the same ``torch.randperm(M)`` choice of reals included.  ``fit()`` keeps the reals' features
+    ``features`` [n,128] fp32 (15 MB for 30 000) and their tile sums ``sxx`` (``ops.kid_tilesums_f64``, self form, ``skip_diagonal``: fp64
+    on the fp64 matrix cores, reproducible; no Gram matrix is written).  ``result()`` needs at least 2 fed images: one self call over the fed
+    features (``syy``), one cross call (``sxy``), one host read, ``kid_statistic`` with ``subset_size`` in fp64 on the host.
+    ``with_fd``: also the Frechet distance of the same features (``ops.fd_moments_f64``, ``frechet_statistic``), exactly the ``fd`` of a
+    ``FrechetDistance`` with the same seed, embedding and feeds -- one set of generator passes and one embedding serve both numbers.
+    ``device='cpu'``: the host twin (the embedding's host mode, ``_kid_tilesums_host``), close to the device but not equal: the order
+    of the sums differs."""
+
+    def __init__(self, source, num_real=None, max_resolution=256, seed=0, drange=(-1, 1), device=None, embedding=None, subset_size=1024,
+                 gamma=None, coef0=1.0, with_fd=False):
+        _, src_device = self._stack_source(source)
+        self.num_real = None if num_real is None else _int_in(num_real, 2, None, 'num_real = %r (at least 2 images)' % (num_real,))
+        self.seed = _int_in(seed, None, None, 'seed = %r (an integer)' % (seed,))
+        message = 'subset_size = %r (a positive multiple of %d)' % (subset_size, ops.KID_TILE)
+        self.subset_size = KID_SUBSET if subset_size is None else _int_in(subset_size, ops.KID_TILE, None, message)
+        if self.subset_size % ops.KID_TILE:
+            raise ValueError(message)
+        self.gamma, self.coef0, self.with_fd = None if gamma is None else float(gamma), float(coef0), bool(with_fd)
+        super(KernelDistance, self).__init__(source, src_device, drange, device)
+        if embedding is None:
+            RandomEmbedding(1, self.seed, max_resolution, device=self.device)     # (the argument check; made for C channels at fit())
+        elif not isinstance(embedding, RandomEmbedding) or embedding.device.type != self.device.type:
+            raise ValueError('embedding: expected a RandomEmbedding on %s' % self.device.type)
+        self.max_resolution, self.embedding = max_resolution, embedding
+        self.features = self.sxx = self.syy = self.sxy = self.mean = self.cov = self.resolution = self.shape = self.indices = None
+        self.reset()
+
+    def _tilesums(self, x, y=None, skip_diagonal=False):
+        if self.device.type == 'cuda':
+            return ops.kid_tilesums_f64(x, y, self.gamma, self.coef0, skip_diagonal)
+        return torch.from_numpy(_kid_tilesums_host(x.numpy(), None if y is None else y.numpy(), self.gamma, self.coef0, skip_diagonal))
+
+    def _moments(self, feats):
+        if self.device.type == 'cuda':
+            return ops.fd_moments_f64(feats)
+        return tuple(torch.from_numpy(v) for v in _moments_host(feats.numpy()))
+
+    def fit(self, block=1024):
+        """Embed the reals of the current stage, ``block`` at a time, and keep ``features`` [n,128] (fp32) and ``sxx`` (fp64 tile sums
+        without the diagonal) on ``device`` -- with ``with_fd`` also ``mean`` and ``cov`` -- ``indices`` (int64, host: the images taken)
+        and ``resolution`` (the STAGE's, what ``feed`` expects); forgets what was fed.  Returns self."""
+        stack = self.stack()
+        M, C = stack.shape[0], stack.shape[1]
+        n = M if self.num_real is None else self.num_real
+        if not 2 <= n <= M:
+            raise ValueError('%d of %d images (2 <= num_real <= M)' % (n, M))
+        if self.embedding is None:
+            self.embedding = RandomEmbedding(C, self.seed, self.max_resolution, device=self.device)
+        if self.embedding.channels != C:
+            raise ValueError('the embedding takes %d channels, the stack has %d' % (self.embedding.channels, C))
+        self.indices = torch.randperm(M, generator=torch.Generator().manual_seed(self.seed))[:n]
+        idx = self.indices.to(self.device)
+        feats = [self.embedding(stack.index_select(0, idx[s:s + block])) for s in range(0, n, block)]
+        self.features = (feats[0] if len(feats) == 1 else torch.cat(feats)).contiguous()
+        self.sxx = self._tilesums(self.features, skip_diagonal=True)
+        self.mean, self.cov = self._moments(self.features) if self.with_fd else (None, None)
+        self.shape, self.resolution = tuple(stack.shape[1:]), int(stack.shape[-1])
+        self.reset()
+        return self
+
+    def reset(self):
+        """Forget what was fed; the fit is kept."""
+        self._feats, self._fed, self._result = [], 0, None
+        self.syy = self.sxy = None
+
+    def _take(self, images):
+        self._feats.append(self.embedding(images))
+
+    def result(self):
+        """{'kid', 'subsets', 'kid_subset_mean', 'kid_subset_std' (fp64; ``kid_statistic``), 'num_real', 'num_fake'} and with ``with_fd``
+        'fd', 'mean_term', 'cov_term'.  Leaves the tile sums of this evaluation in ``syy`` and ``sxy``.  One device synchronisation."""
+        if self._result is None:
+            if self.features is None:
+                raise RuntimeError('fit() first')
+            if self._fed < 2:
+                raise RuntimeError('%d images were fed; the estimator needs 2' % self._fed)
+            fake = (self._feats[0] if len(self._feats) == 1 else torch.cat(self._feats)).contiguous()
+            self.syy = self._tilesums(fake, skip_diagonal=True)
+            self.sxy = self._tilesums(self.features, fake)
+            parts = [self.sxx, self.syy, self.sxy]
+            if self.with_fd:
+                parts += [self.mean, self.cov] + list(self._moments(fake))
+            host = torch.cat([p.reshape(-1) for p in parts]).cpu().numpy()
+            split = np.split(host, np.cumsum([p.numel() for p in parts])[:-1])
+            m, n = int(self.indices.numel()), self._fed
+            res = kid_statistic(split[0].reshape(self.sxx.shape), split[1].reshape(self.syy.shape), split[2].reshape(self.sxy.shape), m, n,
+                                self.subset_size)
+            if self.with_fd:
+                F = split[3].size
+                res.update(frechet_statistic(split[3], split[4].reshape(F, F), split[5], split[6].reshape(F, F)))
+            res.update(num_real=m, num_fake=n)
             self._result = res
         return self._result

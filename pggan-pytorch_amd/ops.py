@@ -1428,6 +1428,47 @@ def fd_moments_f64(x):
     return mean, cov
 
 
+# ------------------------------------------------------------------------- tile sums of the cubic kernel: the kernel distance (csrc/kid.hip)
+KID = {name[len('PG_KID_'):]: value for name, value in _lib.KID_CONSTANTS.items()}   # the addition's own table
+KID_TILE, KID_MIN_F, KID_MAX_F = KID['TILE'], KID['MIN_F'], KID['MAX_F']
+
+
+def _kid_features(t, who):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+        raise ValueError('kid_tilesums_f64: expected %s as a contiguous float32 device tensor [rows,F]' % who)
+    return t.shape
+
+
+def kid_tilesums_f64(x, y=None, gamma=None, coef0=1.0, skip_diagonal=False, out=None):
+    """fp32 device features ``x`` [M,F] and ``y`` [N,F] (None: y = x, the self form) -> fp64 ``[A,B]`` with A = ceil(M / ``KID_TILE``),
+    B = ceil(N / ``KID_TILE``) (pg_kid_tilesums_f64): ``sums[a,b]`` = the sum of ``k(x_i, y_j) = (gamma x_i . y_j + coef0)^3`` over the
+    pairs of tile (a, b) with i < M and j < N, without the pairs i == j when ``skip_diagonal`` (the self form only).  ``gamma`` None:
+    ``1.0 / F``.  fp64 throughout, the dot products on the fp64 matrix cores; the Gram matrix is never written.  The order of the sums
+    depends on (M, N, F) alone: two calls give the same bits, and the self form is symmetric bit for bit.  M, N >= 1, F a multiple
+    of 16, ``KID_MIN_F`` <= F <= ``KID_MAX_F``.  ``out``: a contiguous fp64 device tensor [A,B] to write.  No host synchronisation."""
+    M, F = _kid_features(x, 'x')
+    N = M
+    if y is not None:
+        N, Fy = _kid_features(y, 'y')
+        if Fy != F or y.device != x.device:
+            raise ValueError('kid_tilesums_f64: y %s on %s does not match x %s on %s' % (tuple(y.shape), y.device, tuple(x.shape), x.device))
+        if skip_diagonal:
+            raise ValueError('kid_tilesums_f64: skip_diagonal is for the self form (y = None)')
+    if M < 1 or N < 1 or F % 16 or not KID_MIN_F <= F <= KID_MAX_F:
+        raise ValueError('kid_tilesums_f64: features [%d,%d] against [%d,%d] (at least one row a side, F a multiple of 16, %d <= F <= %d)'
+                         % (M, F, N, F, KID_MIN_F, KID_MAX_F))
+    gamma = 1.0 / F if gamma is None else float(gamma)
+    A, B = (M + KID_TILE - 1) // KID_TILE, (N + KID_TILE - 1) // KID_TILE
+    require_gpu()
+    if out is None:
+        out = torch.empty((A, B), device=x.device, dtype=torch.float64)
+    else:
+        _dev_tensor(out, torch.float64, (A, B), x.device, 'kid_tilesums_f64: out')
+    _lib.call('pg_kid_tilesums_f64', x.data_ptr(), M, None if y is None else y.data_ptr(), N, F, gamma, float(coef0),
+              1 if skip_diagonal else 0, out.data_ptr(), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------- nearest windows at every start column (csrc/shift_search.hip)
 SHIFT = {name[len('PG_SHIFT_'):]: value for name, value in _lib.SHIFT_CONSTANTS.items() if name.startswith('PG_SHIFT_')}   # the addition's own table
 SHIFT_POS_BITS, SHIFT_MAX_QUERIES, SHIFT_TILE = SHIFT['POS_BITS'], SHIFT['MAX_QUERIES'], SHIFT['TILE']
